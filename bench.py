@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - DCVC-RT 1080p YUV420 encode+decode throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one frame of a 32-frame-GOP 1080p sequence (configs[1]) ENCODED and DECODED by the HIP
@@ -11,15 +11,26 @@ encoder and the decoder as a two-stage pipeline (two host threads, two HIP strea
 frame n decodes while frame n+1 encodes).  Whatever --steps is, the timed window carries I frames at
 (at least) the GOP's rate: the window is placed in the GOP so that an I frame falls inside it
 (steps < 32: one I frame in the middle, i.e. MORE than the 1-in-32 share; whole GOPs otherwise) - the
-frames needed to get there are extra untimed warm-up (`config.alignment_frames`).  After the timed
-region one whole GOP is run one direction at a time for the per-direction fps (`enc_fps_per_gpu`,
-`dec_fps_per_gpu`, `sequential_*`), which is how the reference times them and what `vs_baseline`
-compares, and for bpp / PSNR (per plane and (6Y+U+V)/8, against the 8-bit source planes, the
-reference's get_distortion).  With N > 1 every rank
+frames needed to get there are extra untimed warm-up (`config.alignment_frames`).  With N > 1 every rank
 codes its own independent stream (weak scaling, no data-path collective; the weights are
 broadcast once from rank 0 over RCCL).  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the outputs of
+--dump-outputs, the line (`value`, `ms_per_step` = milliseconds per timed step, `bpp` of the timed window and
+`gop_weighted_value` = 32 / (t_I + 31 t_P) from the timed window, which does not depend on --steps).
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller, as float32 .npy files
+(rank 0): `x_hat` (the decoded picture, [1, 3, H', W'], padded), `bit_stream` (the frame's packet, one value per
+byte) and `packet` ([is_i, qp, use_ada_i, bytes]).  Inputs and weights are seeded, so two builds run with the same
+arguments can be compared output for output.  64 MB at most: an array that does not fit (x_hat at 4K) is written
+as a fixed, seeded sample of its elements (`<name>_sample` + `<name>_sample_index`, flat indices).
+
+--full adds everything else, as before: one whole GOP run one direction at a time for the per-direction fps
+(`enc_fps_per_gpu`, `dec_fps_per_gpu`, `sequential_*`), which is how the reference times them and what
+`vs_baseline` compares, and for bpp / PSNR (per plane and (6Y+U+V)/8, against the 8-bit source planes, the
+reference's get_distortion), plus the objects below.
+
+Extra objects on the --full line:
   roofline     dominant kernel (dcb_tail128_kernel<256>: the DepthConvBlock tail, C = 256 at 136x240): algorithmic FLOP per
                launch / HIP-event time on its stream, against the 2.5 PFLOP/s dense f16 MFMA peak.
   cpu_baseline the CPU oracle (port of the reference's torch fallback path) on the host cores, real 1080p P frames: all
@@ -27,7 +38,6 @@ Extra objects on the line:
                src/utils/common.py:23) one timed frame (~30 s).
   exact_mode   the fp32 mode that is bit-exact with the CPU oracle: P-frame encode / decode fps and the fraction of the
                157.3 TFLOP/s fp32 MFMA peak.
-  gop_weighted_value   32 / (t_I + 31 t_P) from the timed window: does not depend on --steps.
   reference_gop        bpp / PSNR of the same GOP coded by the reference in .half() on a CPU (fixture tests/golden/bench_gop_f16.json)
                and this line's deviation from it.
 """
@@ -165,6 +175,33 @@ def measure(run, steps, warmup, world, device, sync):
     dist_utils.barrier(world)
     sync()
     return dist_utils.max_over_ranks(time.perf_counter() - t0, device, world), align, local
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+DUMP_SAMPLE_ELEMS = 2 ** 21            # elements of a sampled array (float32 values + float64 flat indices: 24 MB)
+
+
+def dump_outputs(out_dir, pkt, x_hat):
+    """--dump-outputs: what the last timed step handed its caller (the packet from the encoder stage, the picture from
+    the decoder stage) as float32 .npy files in out_dir, DUMP_LIMIT_BYTES at most in all; an array that would not fit
+    is replaced by a fixed, seeded sample of its elements and their flat indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = [("packet", np.asarray([pkt.is_i, pkt.qp, pkt.use_ada_i, len(pkt.bit_stream)], np.float32)),
+              ("bit_stream", np.frombuffer(pkt.bit_stream, np.uint8).astype(np.float32)),
+              ("x_hat", x_hat.float().cpu().numpy())]
+    left = DUMP_LIMIT_BYTES - 4096          # (the .npy headers)
+    for name, a in arrays:
+        if a.nbytes <= left:
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            left -= a.nbytes
+            continue
+        idx = np.sort(np.random.default_rng(0).choice(a.size, min(a.size, DUMP_SAMPLE_ELEMS), replace=False))
+        sample = a.reshape(-1)[idx]
+        if sample.nbytes + 8 * idx.size > left:
+            raise SystemExit("bench.py: --dump-outputs: %s does not fit the %d-byte limit even as a sample" % (name, DUMP_LIMIT_BYTES))
+        np.save(os.path.join(out_dir, name + "_sample.npy"), sample)
+        np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx.astype(np.float64))
+        left -= sample.nbytes + 8 * idx.size
 
 
 def cpu_model():
@@ -338,8 +375,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=256)     # eight whole GOPs (I frames at the GOP's rate, 1 in 32), under a second
     ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-exact-mode", action="store_true", help="skip the fp32 exact-mode leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, 64 MB at most)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the sequential GOP (per-direction fps, PSNR, reference_gop), the roofline, exact-mode "
+                         "and CPU-baseline legs; a plain run times the steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU-baseline leg")
+    ap.add_argument("--no-exact-mode", action="store_true", help="(--full) skip the fp32 exact-mode leg")
     ap.add_argument("--frame", default="1920x1080",
                     help="WxH of the synthetic sequence (default: the BASELINE.json configs[1] size; 3840x2160 = configs[3])")
     ap.add_argument("--roofline-only", action="store_true",
@@ -418,11 +460,13 @@ def main():
                 state["bytes"] += len(pkt.bit_stream)
                 state["n_i"] += int(pkt.is_i)
                 state["kinds"].append(bool(pkt.is_i))
+                state["last_pkt"] = pkt                        # (a reference only: --dump-outputs reads it after the window)
 
-        def on_frame(_):
+        def on_frame(x_hat):
             state["j"] += 1
             if timed:
                 state["done"].append(time.perf_counter())      # (host time of the frame's hand-over by the decoder stage)
+                state["last_x"] = x_hat
 
         pipe.run((frames[k % GOP] for k in range(first, first + nsteps)), on_packet, on_frame)
 
@@ -435,47 +479,51 @@ def main():
     assert state["j"] == args.warmup + align + K
     assert state["n_i"] >= max(1, K // GOP), "the timed window must contain I frames at the GOP's rate"
 
-    # outside the timed region: ONE WHOLE GOP (I frame first) one direction at a time, like the reference times them;
-    # bpp and PSNR of that GOP
-    from opendcvc_amd.harness import yuv420_distortion
-    run_pipelined((-state["i"]) % GOP, False)
-    assert state["i"] % GOP == 0
-    n_seq = GOP
-    # encoder pass, then decoder pass (the reference codes a whole sequence before it decodes it, test_video.py:172-298).
-    # Both run with their deferred forms: a P frame's entropy coding / reconstruction network is finished underneath
-    # the next frame's kernels, so packets and pictures come out one call late; every frame is complete at the end.
-    enc.defer = True
-    pkts, pending = [], []
-    t_seq0 = time.perf_counter()
-    for k in range(n_seq):
-        state["i"] += 1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state["last_pkt"], state["last_x"])
+
+    if args.full:
+        # outside the timed region: ONE WHOLE GOP (I frame first) one direction at a time, like the reference times them;
+        # bpp and PSNR of that GOP
+        from opendcvc_amd.harness import yuv420_distortion
+        run_pipelined((-state["i"]) % GOP, False)
+        assert state["i"] % GOP == 0
+        n_seq = GOP
+        # encoder pass, then decoder pass (the reference codes a whole sequence before it decodes it, test_video.py:172-298).
+        # Both run with their deferred forms: a P frame's entropy coding / reconstruction network is finished underneath
+        # the next frame's kernels, so packets and pictures come out one call late; every frame is complete at the end.
+        enc.defer = True
+        pkts, pending = [], []
+        t_seq0 = time.perf_counter()
+        for k in range(n_seq):
+            state["i"] += 1
+            ta = time.perf_counter()
+            with torch.cuda.stream(s_enc):
+                pkts += enc.encode(frames[k])
+            torch.cuda.synchronize()
+            state["t_enc"] += time.perf_counter() - ta
         ta = time.perf_counter()
-        with torch.cuda.stream(s_enc):
-            pkts += enc.encode(frames[k])
-        torch.cuda.synchronize()
+        pkts += enc.flush()
         state["t_enc"] += time.perf_counter() - ta
-    ta = time.perf_counter()
-    pkts += enc.flush()
-    state["t_enc"] += time.perf_counter() - ta
-    enc.defer = False
-    for pkt in pkts:
+        enc.defer = False
+        for pkt in pkts:
+            tb = time.perf_counter()
+            with torch.cuda.stream(s_dec):
+                pending += dec.decode(pkt)
+            torch.cuda.synchronize()
+            state["t_dec"] += time.perf_counter() - tb
+            state["seq_bytes"] += len(pkt.bit_stream)
         tb = time.perf_counter()
         with torch.cuda.stream(s_dec):
-            pending += dec.decode(pkt)
+            pending += dec.flush()
         torch.cuda.synchronize()
         state["t_dec"] += time.perf_counter() - tb
-        state["seq_bytes"] += len(pkt.bit_stream)
-    tb = time.perf_counter()
-    with torch.cuda.stream(s_dec):
-        pending += dec.flush()
-    torch.cuda.synchronize()
-    state["t_dec"] += time.perf_counter() - tb
-    t_seq = time.perf_counter() - t_seq0
-    assert len(pkts) == n_seq
-    assert len(pending) == n_seq
-    for k, x_hat in enumerate(pending):             # (not timed) the reference's per-plane PSNR on the 8-bit planes
-        state["psnr"].append(yuv420_distortion(x_hat, *planes[k]))
-    psnr = np.mean(np.asarray(state["psnr"], np.float64), axis=0)
+        t_seq = time.perf_counter() - t_seq0
+        assert len(pkts) == n_seq
+        assert len(pending) == n_seq
+        for k, x_hat in enumerate(pending):             # (not timed) the reference's per-plane PSNR on the 8-bit planes
+            state["psnr"].append(yuv420_distortion(x_hat, *planes[k]))
+        psnr = np.mean(np.asarray(state["psnr"], np.float64), axis=0)
 
     # A figure that does not depend on where a short window sits in the GOP: the time of a P frame = the median interval
     # between two completed frames of the timed window, the time of an I frame = what is left of the window per I frame;
@@ -488,18 +536,13 @@ def main():
     if rank == 0:
         N = world
         value = N * K / elapsed
-        seq_value = n_seq / t_seq                   # this rank, encode then decode one after the other
-        if (WIDTH, HEIGHT) == (3840, 2160):       # README complexity table, A100 fp16 at 4K: 35.5 / 29.5 fps
-            base = 1.0 / (1.0 / 35.5 + 1.0 / 29.5)
-        else:
-            base = 1.0 / (1.0 / BASELINE_ENC_FPS + 1.0 / BASELINE_DEC_FPS)
         out = {
             "metric": "%s%s YUV420 encode+decode FPS (frames/s through encode AND decode, whole job)"
                       % ("REHEARSAL (%d ranks sharing %d GPU(s), gloo) - not a measurement of the multi-GPU configuration: "
                          % (world, n_dev) if rehearse else "", "1080p" if (WIDTH, HEIGHT) == (1920, 1080) else args.frame),
             "value": round(value, 3), "unit": "frames/s", "n_gpus": N, "steps": K, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / K, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": round(seq_value / base, 4), "dtype": "f16", "data": "synthetic",
+            "dtype": "f16", "data": "synthetic",
             "rank_fps": {"min": round(min(rank_fps), 3), "max": round(max(rank_fps), 3),
                          "note": "each rank's own K timed frames / its own time (before the closing barrier)"},
             "rccl_ranks": (torch.distributed.get_world_size() if WEIGHTS_VIA["how"].startswith("rccl") else 0) if world > 1 else 1,
@@ -521,49 +564,59 @@ def main():
                                    "decodes while frame n+1 encodes; every timed frame is encoded and decoded; the "
                                    "decoder emits P pictures one call late (their reconstruction network fills the next "
                                    "frame's host-decoding gaps)",
-                       "baseline_note": "vs_baseline = sequential_fps_per_gpu / (1/(1/125.2+1/112.8)) fps (reference README, "
-                                        "A100 fp16, encode and decode timed one after the other as in the reference); the "
-                                        "sequential pass is one whole GOP, encoder loop then decoder loop, each frame "
-                                        "synchronised, P-frame streams / pictures completed one call late"},
-            "sequential_fps_per_gpu": round(seq_value, 3), "sequential_ms_per_step": round(1e3 * t_seq / n_seq, 3),
-            "enc_fps_per_gpu": round(n_seq / state["t_enc"], 2), "dec_fps_per_gpu": round(n_seq / state["t_dec"], 2),
+                       "full": args.full},
             "bpp": round(state["bytes"] * 8.0 / (K * HEIGHT * WIDTH), 5),
-            "gop_bpp": round(state["seq_bytes"] * 8.0 / (n_seq * HEIGHT * WIDTH), 5),
-            "psnr": {"weighted_6y_u_v": round(float(psnr[0]), 4), "y": round(float(psnr[1]), 4), "u": round(float(psnr[2]), 4),
-                     "v": round(float(psnr[3]), 4),
-                     "note": "mean over one GOP, decoded vs the 8-bit source planes (reference get_distortion, "
-                             "test_video.py:94-111); synthetic untrained weights: single-digit dB by construction - the "
-                             "number pins parity with the reference (tests/golden), not picture quality"},
         }
-        # the same GOP coded by the REFERENCE in its fp16 arithmetic on a CPU (tests/golden/make_golden_bench_gop.py): how far the
-        # line's bpp / PSNR are from it (data file only; nothing of the reference runs here)
-        ref_path = os.path.join(REPO, "tests", "golden", "bench_gop_f16.json")
-        if (WIDTH, HEIGHT) == (1920, 1080) and os.path.exists(ref_path):
-            try:
-                ref = json.load(open(ref_path))
-                out["reference_gop"] = {
-                    "bpp": round(ref["gop_bpp"], 5), "psnr_weighted_6y_u_v": round(ref["psnr_mean"][0], 4),
-                    "bpp_rel_dev": round(out["gop_bpp"] / ref["gop_bpp"] - 1.0, 5),
-                    "psnr_dev_db": round(out["psnr"]["weighted_6y_u_v"] - ref["psnr_mean"][0], 5),
-                    "note": "the reference's DMCI / DMC in .half() on a CPU on the same 32 frames, qp and weights "
-                            "(tests/golden/bench_gop_f16.json): gop_bpp and psnr of this line against it"}
-            except Exception:      # noqa: BLE001  (a missing / unreadable fixture must not cost the measurement)
-                pass
-        # whole-frame fractions (conv-hook GFLOP and fused-unit algorithmic bytes of a steady P frame at
-        # 1088x1920, scaled by the padded pixel count) from the per-direction times of the sequential pass
-        scale = ((WIDTH + (-WIDTH) % 16) * (HEIGHT + (-HEIGHT) % 16)) / (1920.0 * 1088.0)
-        t_enc, t_dec = state["t_enc"] / n_seq, state["t_dec"] / n_seq
-        out["frame_roofline"] = {
-            "enc_tflops": round(590.4e9 * scale / t_enc / 1e12, 1), "dec_tflops": round(691.6e9 * scale / t_dec / 1e12, 1),
-            "enc_frac_mfma": round(590.4e9 * scale / t_enc / 1e12 / MFMA_F16_PEAK_TFLOPS, 4),
-            "dec_frac_mfma": round(691.6e9 * scale / t_dec / 1e12 / MFMA_F16_PEAK_TFLOPS, 4),
-            "enc_frac_hbm": round(0.76e9 * scale / t_enc / 8.0e12, 4), "dec_frac_hbm": round(0.78e9 * scale / t_dec / 8.0e12, 4),
-            "note": "P-frame work only; the timed pass includes the GOP's I frame and the host entropy coding"}
-        out["roofline"] = roofline_leg(pe, device, dtype)
-        if world == 1 and not args.no_exact_mode:
-            out["exact_mode"] = exact_mode_leg(device, world, rank, frames)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline_leg()
+        if args.full:
+            seq_value = n_seq / t_seq                   # this rank, encode then decode one after the other
+            if (WIDTH, HEIGHT) == (3840, 2160):       # README complexity table, A100 fp16 at 4K: 35.5 / 29.5 fps
+                base = 1.0 / (1.0 / 35.5 + 1.0 / 29.5)
+            else:
+                base = 1.0 / (1.0 / BASELINE_ENC_FPS + 1.0 / BASELINE_DEC_FPS)
+            out["vs_baseline"] = round(seq_value / base, 4)
+            out["config"]["baseline_note"] = ("vs_baseline = sequential_fps_per_gpu / (1/(1/125.2+1/112.8)) fps (reference README, "
+                                              "A100 fp16, encode and decode timed one after the other as in the reference); the "
+                                              "sequential pass is one whole GOP, encoder loop then decoder loop, each frame "
+                                              "synchronised, P-frame streams / pictures completed one call late")
+            out.update({
+                "sequential_fps_per_gpu": round(seq_value, 3), "sequential_ms_per_step": round(1e3 * t_seq / n_seq, 3),
+                "enc_fps_per_gpu": round(n_seq / state["t_enc"], 2), "dec_fps_per_gpu": round(n_seq / state["t_dec"], 2),
+                "gop_bpp": round(state["seq_bytes"] * 8.0 / (n_seq * HEIGHT * WIDTH), 5),
+                "psnr": {"weighted_6y_u_v": round(float(psnr[0]), 4), "y": round(float(psnr[1]), 4), "u": round(float(psnr[2]), 4),
+                         "v": round(float(psnr[3]), 4),
+                         "note": "mean over one GOP, decoded vs the 8-bit source planes (reference get_distortion, "
+                                 "test_video.py:94-111); synthetic untrained weights: single-digit dB by construction - the "
+                                 "number pins parity with the reference (tests/golden), not picture quality"},
+            })
+            # the same GOP coded by the REFERENCE in its fp16 arithmetic on a CPU (tests/golden/make_golden_bench_gop.py): how far
+            # the line's bpp / PSNR are from it (data file only; nothing of the reference runs here)
+            ref_path = os.path.join(REPO, "tests", "golden", "bench_gop_f16.json")
+            if (WIDTH, HEIGHT) == (1920, 1080) and os.path.exists(ref_path):
+                try:
+                    ref = json.load(open(ref_path))
+                    out["reference_gop"] = {
+                        "bpp": round(ref["gop_bpp"], 5), "psnr_weighted_6y_u_v": round(ref["psnr_mean"][0], 4),
+                        "bpp_rel_dev": round(out["gop_bpp"] / ref["gop_bpp"] - 1.0, 5),
+                        "psnr_dev_db": round(out["psnr"]["weighted_6y_u_v"] - ref["psnr_mean"][0], 5),
+                        "note": "the reference's DMCI / DMC in .half() on a CPU on the same 32 frames, qp and weights "
+                                "(tests/golden/bench_gop_f16.json): gop_bpp and psnr of this line against it"}
+                except Exception:      # noqa: BLE001  (a missing / unreadable fixture must not cost the measurement)
+                    pass
+            # whole-frame fractions (conv-hook GFLOP and fused-unit algorithmic bytes of a steady P frame at
+            # 1088x1920, scaled by the padded pixel count) from the per-direction times of the sequential pass
+            scale = ((WIDTH + (-WIDTH) % 16) * (HEIGHT + (-HEIGHT) % 16)) / (1920.0 * 1088.0)
+            t_enc, t_dec = state["t_enc"] / n_seq, state["t_dec"] / n_seq
+            out["frame_roofline"] = {
+                "enc_tflops": round(590.4e9 * scale / t_enc / 1e12, 1), "dec_tflops": round(691.6e9 * scale / t_dec / 1e12, 1),
+                "enc_frac_mfma": round(590.4e9 * scale / t_enc / 1e12 / MFMA_F16_PEAK_TFLOPS, 4),
+                "dec_frac_mfma": round(691.6e9 * scale / t_dec / 1e12 / MFMA_F16_PEAK_TFLOPS, 4),
+                "enc_frac_hbm": round(0.76e9 * scale / t_enc / 8.0e12, 4), "dec_frac_hbm": round(0.78e9 * scale / t_dec / 8.0e12, 4),
+                "note": "P-frame work only; the timed pass includes the GOP's I frame and the host entropy coding"}
+            out["roofline"] = roofline_leg(pe, device, dtype)
+            if world == 1 and not args.no_exact_mode:
+                out["exact_mode"] = exact_mode_leg(device, world, rank, frames)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline_leg()
         print(json.dumps(out), flush=True)
     if world > 1:
         import torch.distributed as dist

@@ -1,8 +1,6 @@
-"""The oracle's rANS / CDF restatement against the reference's golden vectors (bit-exact) and, when
-oracle/_ref is present, against the reference coder itself on fresh random inputs."""
-import glob
+"""The oracle's rANS / CDF restatement against the reference's golden vectors (bit-exact), and against the streams
+the reference coder itself wrote for random inputs (tests/golden/make_golden_rans_random.py)."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -73,28 +71,19 @@ def test_gaussian_tables_match_reference(golden_dir):
     assert np.array_equal(offset, g["offset"])
 
 
-def test_against_reference_build_random():
-    """Fresh random inputs through oracle/_ref (the reference's coder compiled in place)."""
-    here = os.path.dirname(os.path.abspath(O.__file__))
-    if not glob.glob(os.path.join(here, "_ref", "MLCodec_extensions_cpp*.so")):
-        pytest.skip("oracle/_ref not built")
-    sys.path.insert(0, os.path.join(here, "_ref"))
-    import MLCodec_extensions_cpp as R
-    g = O.gaussian_tables()
-    rng = np.random.default_rng(3)
+def test_against_reference_build_random(golden_dir):
+    """Random inputs through the reference's coder with the reference's gaussian tables (recorded by
+    tests/golden/make_golden_rans_random.py): the oracle writes the same streams and reads them back."""
+    rec = np.load(os.path.join(golden_dir, "rans_random.npz"))
+    t = np.load(os.path.join(golden_dir, "gauss_cdf.npz"))
+    g = (t["cdf"], t["length"], t["offset"])
     for two in (False, True):
         for n in (1000, 50001):
-            idx = rng.integers(0, 128, n).astype(np.uint8)
-            sigma = 0.11 * (16 / 0.11) ** (idx / 127.0)
-            sym = np.clip(np.round(rng.standard_normal(n) * sigma), -128, 127).astype(np.int16)
-            p = ((sym.astype(np.int32) << 8) + idx).astype(np.int16)
-            enc = R.RansEncoder()
-            enc.add_cdf(*g)
-            enc.set_use_two_encoders(two)
-            enc.reset()
-            enc.encode_y(p, 0)
-            enc.flush()
-            ref = np.array(enc.get_encoded_stream()).tobytes()
+            key = "two%d_n%d" % (int(two), n)
+            p, ref = rec[key + "_packed"], rec[key + "_stream"].tobytes()
+            assert p.dtype == np.int16 and p.shape == (n,)
+            idx = (p.astype(np.int32) & 0xFF).astype(np.uint8)
+            sym = p >> 8
             c = O.Coder()
             c.add_cdf(*g)
             c.set_use_two(two)

@@ -8,12 +8,6 @@ for v in 1 0; do
 done
 for r in 1 2; do
   for v in 1 0; do
-    DCVC_DEC_COMPACT=$v python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-exact-mode > gpurun_out/r4_deccompact_${v}_$r.json 2>/dev/null
+    echo "DCVC_DEC_COMPACT=$v run $r $(DCVC_DEC_COMPACT=$v python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-exact-mode 2>/dev/null | python -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["value"], d["gop_weighted_value"], d["enc_fps_per_gpu"], d["dec_fps_per_gpu"])')"
   done
 done
-python - <<'PY'
-import json, glob
-for f in sorted(glob.glob("gpurun_out/r4_deccompact_*.json")):
-    d = json.loads(open(f).read().strip().splitlines()[-1])
-    print(f, d["value"], d["gop_weighted_value"], d["enc_fps_per_gpu"], d["dec_fps_per_gpu"])
-PY

@@ -12,6 +12,6 @@ for rep in 1 2 3; do
 done > gpurun_out/g32w2/kbench.txt 2>&1
 for rep in 1 2 3; do
   for v in $LIBS; do
-    echo "$v $(DCVC_AMD_LIB=$v python3 bench.py --steps 64 --warmup 8 --no-cpu-baseline --no-exact-mode 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("value", d["value"], "enc", d["enc_fps_per_gpu"], "dec", d["dec_fps_per_gpu"], "bpp", d["gop_bpp"], "psnr", d["psnr"]["weighted_6y_u_v"])')"
+    echo "$v $(DCVC_AMD_LIB=$v python3 bench.py --full --steps 64 --warmup 8 --no-cpu-baseline --no-exact-mode 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("value", d["value"], "enc", d["enc_fps_per_gpu"], "dec", d["dec_fps_per_gpu"], "bpp", d["gop_bpp"], "psnr", d["psnr"]["weighted_6y_u_v"])')"
   done
 done > gpurun_out/g32w2/bench.txt 2>&1

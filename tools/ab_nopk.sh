@@ -12,6 +12,6 @@ for rep in 1 2 3; do
 done > gpurun_out/nopk/ab.txt 2>&1
 for rep in 1 2; do
   for v in libdcvc_amd.so $OTHER; do
-    echo "$v $(DCVC_AMD_LIB=$v python3 bench.py --steps 64 --warmup 8 --no-cpu-baseline 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("value", d["value"], "enc", d["enc_fps_per_gpu"], "dec", d["dec_fps_per_gpu"], "roofline_ms", d["roofline"]["kernel_ms"], "exact", d.get("exact_mode", {}).get("enc_fps"), d.get("exact_mode", {}).get("dec_fps"), "bpp", d["gop_bpp"], "psnr", d["psnr"]["weighted_6y_u_v"])')"
+    echo "$v $(DCVC_AMD_LIB=$v python3 bench.py --full --steps 64 --warmup 8 --no-cpu-baseline 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("value", d["value"], "enc", d["enc_fps_per_gpu"], "dec", d["dec_fps_per_gpu"], "roofline_ms", d["roofline"]["kernel_ms"], "exact", d.get("exact_mode", {}).get("enc_fps"), d.get("exact_mode", {}).get("dec_fps"), "bpp", d["gop_bpp"], "psnr", d["psnr"]["weighted_6y_u_v"])')"
   done
 done > gpurun_out/nopk/bench.txt 2>&1

@@ -8,15 +8,15 @@ R=${1:-r03}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/final
 rm -rf $O && mkdir -p $O
-python3 bench.py > $O/${R}_bench.json 2> $O/bench.err
-python3 bench.py --steps 20 --warmup 5 > $O/${R}_bench_steps20.json 2>> $O/bench.err
+python3 bench.py --full > $O/${R}_bench.json 2> $O/bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/${R}_bench_steps20.json 2>> $O/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_roof -- python3 bench.py --roofline-only > $O/${R}_roofline_under_rocprof.json 2>> $O/bench.err
 cp $(find $O/prof_roof -name "*kernel_stats.csv" | head -1) $O/${R}_roofline_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python3 bench.py --steps 64 --warmup 8 --no-cpu-baseline --no-exact-mode > $O/${R}_bench_under_rocprof.json 2>> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python3 bench.py --full --steps 64 --warmup 8 --no-cpu-baseline --no-exact-mode > $O/${R}_bench_under_rocprof.json 2>> $O/bench.err
 cp $(find $O/prof_bench -name "*kernel_stats.csv" | head -1) $O/${R}_bench_kernel_stats.csv
 rm -rf $O/prof_roof $O/prof_bench
 echo "bench + rocprof stats done"
-python3 bench.py --frame 3840x2160 --no-cpu-baseline --no-exact-mode > $O/${R}_bench_4k.json 2>> $O/bench.err
+python3 bench.py --full --frame 3840x2160 --no-cpu-baseline --no-exact-mode > $O/${R}_bench_4k.json 2>> $O/bench.err
 python3 tools/iframe_time.py > $O/${R}_iframe_time.txt 2>> $O/bench.err
 python3 tools/kbench.py 2>/dev/null > $O/${R}_kbench.txt
 DCVC_T128=0 python3 tools/kbench.py 256 136 240 2>/dev/null | sed 's/^/[64-pixel tails, DCVC_T128=0] /' >> $O/${R}_kbench.txt
