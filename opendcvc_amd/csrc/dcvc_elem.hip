@@ -1069,7 +1069,8 @@ int dcvc_prior_dec_restore(int dtype, int n_groups, int step, const int8_t* sym_
 }
 
 namespace {
-// workspace of the compacted decoder hand-off (device): [total: 16 bytes][off16: n16 x 4][cnt16: n16 -> 16][csym: n -> 16]
+// workspace of the compacted decoder hand-off (device): [total: 16 bytes][off16: n16 x 4 -> 16][cnt16: n16 -> 16][csym: n -> 16]
+// (every part starts on a 16-byte boundary: dec_gather_kernel writes csym with 16-byte stores for any C / n_groups)
 struct DecWs {
     int64_t n16, n, off_off16, off_cnt16, off_csym, bytes;
     int nblk;
@@ -1082,7 +1083,7 @@ DecWs dec_ws(int H, int W, int C, int n_groups)
     w.n16 = (int64_t)(C / n_groups) * w.nblk;
     w.n = (int64_t)(C / n_groups) * HW;
     w.off_off16 = 16;
-    w.off_cnt16 = w.off_off16 + w.n16 * 4;
+    w.off_cnt16 = w.off_off16 + (w.n16 * 4 + 15) / 16 * 16;
     w.off_csym = w.off_cnt16 + (w.n16 + 15) / 16 * 16;
     w.bytes = w.off_csym + (w.n + 15) / 16 * 16;
     return w;
@@ -1142,6 +1143,7 @@ int dcvc_prior_dec_restore_compact(int dtype, int n_groups, int step, const int8
     const int cap16 = (int)((w.n + 15) / 16);
     hipLaunchKernelGGL(dec_gather_kernel, dim3((cap16 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint4*)src_dev,
                        (uint4*)(ws + w.off_csym), (const int32_t*)ws, cap16);
+    DCVC_LAUNCH_CHECK();
     const size_t lds = (size_t)(C / n_groups) * 8;
     return typed(dtype, [&](auto tag) {
         using T = decltype(tag);

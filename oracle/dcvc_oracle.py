@@ -639,7 +639,7 @@ class OracleDMC(CodecBase):
         p1 = self.encode_y(w(y_q_1), w(s_hat_1))
         bits = self.coder.flush()
         self.trace = dict(y=y, z_hat=z_hat, params=params, y_hat=y_hat, feature=feature, ctx=ctx,
-                          ctx_t=ctx_t, z8=z8, packed0=p0, packed1=p1)
+                          ctx_t=ctx_t, z8=z8, packed0=p0, packed1=p1, y_hat_0=y_hat_0, sp=[sp])
         self.ref_feature, self.ref_frame = feature, None
         return {"bit_stream": bits}
 
@@ -740,12 +740,13 @@ class OracleDMCI(CodecBase):
         masks = masks_4x(yh, yw, C)
         yq = y * q_enc
         w4 = lambda a: (a[:, :, :C // 4] + a[:, :, C // 4:C // 2]) + (a[:, :, C // 2:3 * C // 4] + a[:, :, 3 * C // 4:])
-        sym, scl = [], []
+        sym, scl, sps = [], [], []
         _, y_q, y_hat_k, s_hat = process_with_mask(yq, scales, means, masks[0], self.thres)
         sym.append(w4(y_q)); scl.append(w4(s_hat))
-        so_far = y_hat_k
+        so_far = y_hat_0 = y_hat_k
         for step in (1, 2, 3):
             sp = self.spatial_prior(np.concatenate([so_far, common], 2), step)
+            sps.append(sp)
             scales, means = sp[:, :, :C], sp[:, :, C:]
             _, y_q, y_hat_k, s_hat = process_with_mask(yq, scales, means, masks[step], self.thres)
             sym.append(w4(y_q)); scl.append(w4(s_hat))
@@ -756,7 +757,8 @@ class OracleDMCI(CodecBase):
         z8 = self.encode_z(z_hat, qp)
         packed = [self.encode_y(a, b) for a, b in zip(sym, scl)]
         bits = self.coder.flush()
-        self.trace = dict(y=y, z_hat=z_hat, params=params, y_hat=y_hat, z8=z8, packed=packed)
+        self.trace = dict(y=y, z_hat=z_hat, params=params, y_hat=y_hat, z8=z8, packed=packed, y_hat_0=y_hat_0,
+                          sp=sps)
         return {"bit_stream": bits, "x_hat": hwc_to_nchw(x_hat)}
 
     def decompress(self, bit_stream, sps, qp):

@@ -192,14 +192,16 @@ def test_compact_symbols_writes_kept_entries_in_order_to_pinned_memory(parts, n)
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
 @pytest.mark.parametrize("groups,H,W,C,thres", [(2, 68, 120, 256, 0.12), (2, 17, 30, 256, 0.12), (4, 9, 13, 64, 0.12), (4, 68, 120, 256, 0.3),
-                                                (2, 136, 240, 256, 0.12), (2, 20, 24, 128, -1.0), (2, 12, 16, 64, 100.0)])
+                                                (2, 136, 240, 256, 0.12), (2, 20, 24, 128, -1.0), (2, 12, 16, 64, 100.0),
+                                                (2, 3, 5, 10, 0.12), (4, 1, 17, 12, 0.05), (2, 8, 6, 2, 0.12), (2, 5, 7, 6, -1.0)])
 def test_decoder_hand_off_compacted_on_the_device(dtype, groups, H, W, C, thres):
     """dcvc_prior_dec_index_compact / dcvc_prior_dec_restore_compact (the decoder's hand-off with the kept entries compacted on
     the device; same stream order as the reference's boolean-mask gather, entropy_models.py:330-341) against the whole-array
     entry points: the pinned buffer holds exactly the non-sentinel indexes of dcvc_prior_dec_index in CHW order and their
     count, nothing behind them is touched, and the restore from compacted symbols equals dcvc_prior_dec_restore from the
     scattered array bit for bit.  Cases: HW a multiple of 16 and not, every step of both group counts, several scan rounds per
-    block (136x240), everything kept (thres < 0), nothing kept."""
+    block (136x240), everything kept (thres < 0), nothing kept, odd C / n_groups with n16 = C / n_groups * ceil(HW / 16) not a
+    multiple of 4 (the workspace's parts must still start on 16-byte boundaries)."""
     import ctypes
     from opendcvc_amd import _lib, entropy, nn
     lib = _lib.lib()
@@ -246,3 +248,77 @@ def test_decoder_hand_off_compacted_on_the_device(dtype, groups, H, W, C, thres)
         torch.cuda.synchronize()
         assert torch.equal(got, want)
         prev = want
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
+def test_flat_ops_contract_bit_exact(dtype):
+    """The operator seam's contract in both storage types: fp32 arithmetic on the loaded inputs, ONE
+    rounding to the storage type at each store.  Random values plus the edges where a symbol or an index changes: y - mean on
+    .5 ties and past +-128, -0.0, scales on 0, 0.11, 16, force_zero_thres and every scale_to_index bin edge, q below / on
+    min_val."""
+    from opendcvc_amd import ops
+    from test_gpu_prior import TIES, scale_edges
+    dt = np.float16 if dtype == torch.float16 else np.float32
+    f = lambda a: np.asarray(a, np.float32)
+    rng = np.random.default_rng(21)
+    C, H, W = 8, 6, 11
+    shape = (1, C, H, W)
+    mask = (rng.random(shape) < 0.5).astype(dt)
+    means = np.where(rng.random(shape) < 0.4, rng.choice([0.0, 0.25, -1.75], shape), rng.normal(0, 3, shape)).astype(dt)
+    y = np.where(rng.random(shape) < 0.5, f(means) + rng.choice(TIES[:10], shape), rng.normal(0, 40, shape))
+    y = np.where(rng.random(shape) < 0.05, -0.0, y).astype(dt)
+    se = scale_edges(dt)
+    scales = np.where(rng.random(shape) < 0.6, se[rng.integers(0, se.size, shape)], np.exp(rng.normal(-1, 2, shape))).astype(dt)
+    st = lambda a: np.asarray(a, np.float32).astype(dt)
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint16 if dt == np.float16 else np.uint32)
+    for thres in (-1.0, 0.05, 0.12):
+        outs = ops.process_with_mask_cuda(cu(y), cu(scales), cu(means), cu(mask), thres)
+        want = O.process_with_mask(f(y), f(scales), f(means), f(mask), None if thres < 0 else thres)
+        for got, w, name in zip(outs, want, ("y_res", "y_q", "y_hat", "s_hat")):
+            assert np.array_equal(bits(got.cpu().numpy()), bits(st(w))), (thres, name)
+    out = torch.empty((1, C // 2, H, W), dtype=dtype, device="cuda")
+    ops.combine_for_reading_2x_cuda(out, cu(y), cu(mask))
+    ym = f(y) * f(mask)
+    assert np.array_equal(bits(out.cpu().numpy()), bits(st(ym[:, :C // 2] + ym[:, C // 2:])))
+    for groups, fn in ((2, ops.restore_y_2x_cuda), (4, ops.restore_y_4x_cuda)):
+        sym = rng.integers(-128, 128, (1, C // groups, H, W)).astype(dt)
+        out = torch.empty(shape, dtype=dtype, device="cuda")
+        fn(out, cu(sym), cu(means), cu(mask))
+        want = (np.concatenate([f(sym)] * groups, 1) + f(means)) * f(mask)
+        assert np.array_equal(bits(out.cpu().numpy()), bits(st(want))), groups
+    args = (0.11, 16.0, O.LOG_SCALE_MIN, O.LOG_STEP_RECIP)
+    s = np.clip(f(scales), np.float32(0.11), np.float32(16.0))
+    want_idx = O.scale_to_index(s, *args)
+    sym = rng.integers(-128, 128, shape).astype(dt)
+    for thres in (0.05, 0.12):
+        idx = torch.empty(shape, dtype=torch.uint8, device="cuda")
+        cond = torch.empty(shape, dtype=torch.bool, device="cuda")
+        ops.build_index_dec_cuda(idx, cond, cu(scales), *args, thres)
+        assert np.array_equal(idx.cpu().numpy(), want_idx)
+        assert np.array_equal(cond.cpu().numpy(), s > np.float32(thres))
+        pk = torch.empty(shape, dtype=torch.int16, device="cuda")
+        cond = torch.empty(shape, dtype=torch.bool, device="cuda")
+        ops.build_index_enc_cuda(pk, cond, cu(sym), cu(scales), *args, thres)
+        assert np.array_equal(pk.cpu().numpy(), (f(sym).astype(np.int32) * 256 + want_idx).astype(np.int16))
+        assert np.array_equal(cond.cpu().numpy(), s > np.float32(thres))
+    z = np.where(rng.random(shape) < 0.5, rng.choice(TIES[:10] + [126.5, -129.0, 1e4, -0.0], shape),
+                 rng.normal(0, 60, shape)).astype(dt)
+    zt = cu(z)
+    z8 = ops.round_and_to_int8_cuda(zt)
+    zw = np.clip(np.round(f(z)), np.float32(-128), np.float32(127))
+    assert np.array_equal(bits(zt.cpu().numpy()), bits(st(zw))) and np.array_equal(z8.cpu().numpy(), zw.astype(np.int8))
+    q = np.where(rng.random(shape) < 0.4, rng.choice([0.25, 0.5, 1.0, 64.0], shape), rng.uniform(0.1, 3, shape)).astype(dt)
+    yt = cu(y)
+    q_out = ops.clamp_reciprocal_with_quant_cuda(cu(q), yt, 0.5)
+    qv = np.maximum(f(q), np.float32(0.5))
+    assert np.array_equal(bits(q_out.cpu().numpy()), bits(st(qv)))
+    assert np.array_equal(bits(yt.cpu().numpy()), bits(st(f(y) * (np.float32(1.0) / qv))))
+    x0, x1 = rng.normal(0, 4, shape).astype(dt), rng.normal(0, 4, shape).astype(dt)
+    a = cu(x0)
+    ops.add_and_multiply_cuda(a, cu(x1), cu(q))
+    assert np.array_equal(bits(a.cpu().numpy()), bits(st((f(x0) + f(x1)) * f(q))))
+    bias = rng.normal(0, 1, C).astype(dt)
+    qs = rng.uniform(0.5, 2, (1, C, 1, 1)).astype(dt)
+    t = cu(x0)
+    ops.bias_quant_cuda(t, cu(bias), cu(qs))
+    assert np.array_equal(bits(t.cpu().numpy()), bits(st((f(x0) + f(bias)[None, :, None, None]) * f(qs))))
