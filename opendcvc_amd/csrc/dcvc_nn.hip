@@ -232,6 +232,7 @@ struct TailParams {
     const void* hwt;     // dcb_tail128_kernel<..., HEADIN>: W1 as the per-quarter fragment stream (the one a fused-head tail reads)
     const void* wt;      // dcb_tail128_kernel: the tail's weights as per-quarter fragment streams (dcb_t128.hpp)
     const void* nwt;     // ... and the fused next-block head's / 1x1 conv's (the same matrix as nw1, 32x32x16 fragments)
+    void* ostage;        // dcb_tail128_kernel<..., OSTORE> (stage A of the staged small-map tail): o, P x C fp16
     int ablate;          // debug: bit0 skip dw, bit1 skip GEMM2, bit2 skip FFN GEMM3, bit3 skip FFN GEMM4
     unsigned long long* stamps;   // diagnostic build only (DCVC_STAMPS): 8 cycle counters per workgroup
 };
@@ -946,6 +947,7 @@ struct dcvc_dcb {
     DevBuf wa_t128; // fp16, widths 256 / 320 / 384: the adaptor as a fragment stream (dcb_head128_kernel)
     DevBuf w1_t128; // fp16, widths 256 / 320 / 384: W1 as a fragment stream (the previous block's tail computes this block's head)
     DevBuf wt128;   // fp16, widths 256 / 320 / 384: W2 | W3 | W4 once more as the fragment streams of dcb_tail128_kernel
+    DevBuf w3s, w4s;    // fp16, widths 256 / 384 / 512: W3 and W4 as the streams of the staged small-map tail (ffn_up / ffn_down_t128_kernel)
 };
 
 struct dcvc_conv {
@@ -1042,6 +1044,26 @@ int pack_t128(DevBuf& dst, const std::function<float(int, int)>& W2, const std::
     return dst.upload(buf.data(), buf.size() * sizeof(half_t));
 }
 
+// W3 for ffn_up_t128_kernel: per quarter, chunk by chunk, the KS fragments of the fused stream's g3(j)
+template <int C>
+int pack_t128_w3(DevBuf& dst, const std::function<float(int, int)>& W3)
+{
+    using FC = t128::FfnCfg<C>;
+    std::vector<half_t> buf((size_t)4 * FC::STREAM3 * 512, (half_t)0.f);
+    for (int cq = 0; cq < 4; ++cq) {
+        size_t f = 0;
+        for (int j = 0; j < FC::NCH; ++j)
+            for (int s = 0; s < FC::KS; ++s, ++f) {
+                half_t* o = &buf[((size_t)cq * FC::STREAM3 + f) * 512];
+                for (int l = 0; l < 64; ++l) {
+                    const int r = l & 31, row = (r < 16 ? 0 : 2 * C - 16) + 64 * j + 16 * cq + r;
+                    for (int jj = 0; jj < 8; ++jj) o[l * 8 + jj] = (half_t)W3(row, 16 * s + 8 * (l >> 5) + jj);
+                }
+            }
+    }
+    return dst.upload(buf.data(), buf.size() * sizeof(half_t));
+}
+
 inline bool t128_width_ok(int c_p) { return c_p == 128 || c_p == 256 || c_p == 320 || c_p == 384 || c_p == 512; }   // (128, 512: 32-pixel tiles only)
 
 // a C x C matrix (next block's first conv, a fused 1x1 conv) as the per-quarter fragment stream gemm_c reads
@@ -1123,6 +1145,14 @@ static bool t32_enabled()    // DCVC_T32=0: small-map tails (widths 256 / 384) b
     return on;
 }
 
+// DCVC_T32S=1: the staged small-map tail (three launches, dcb_t128.hpp) instead of the fused 32-pixel one.  Off by default:
+// bit-identical, but not faster alone (docs/experiments.md, round 5)
+static bool t32s_enabled()
+{
+    static const bool on = getenv("DCVC_T32S") && atoi(getenv("DCVC_T32S")) != 0;
+    return on;
+}
+
 static bool t32_128_enabled()    // DCVC_T32_128=0: width-128 blocks by dcb_tail_kernel<..., HEADIN> (A/B measurements, bit-identity checks)
 {
     static const bool on = !(getenv("DCVC_T32_128") && atoi(getenv("DCVC_T32_128")) == 0);
@@ -1141,12 +1171,12 @@ static bool h128_enabled()   // DCVC_H128=0: large-map heads by dcb_head_kernel 
     return on;
 }
 
-template <int C, class G = t128::G128, bool HEADIN = false>
+template <int C, class G = t128::G128, bool HEADIN = false, bool OSTORE = false>
 int launch_tail128(const TailParams& tp, int H, int W, hipStream_t st)
 {
     const int grid = ((H + G::TH - 1) / G::TH) * ((W + G::TW - 1) / G::TW);
     const size_t lds = t128::Cfg<C, G, HEADIN>::LDS;
-    int rc = set_lds(t128::dcb_tail128_kernel<C, G, HEADIN>, lds);
+    int rc = set_lds(t128::dcb_tail128_kernel<C, G, HEADIN, OSTORE>, lds);
     if (rc) return rc;
 #ifdef DCVC_DIAG      // developer build only (make diag): in-kernel phase stamps, median over the workgroups
     static const bool want_stamps = getenv("DCVC_STAMPS") != nullptr;
@@ -1154,7 +1184,7 @@ int launch_tail128(const TailParams& tp, int H, int W, hipStream_t st)
         TailParams q = tp;
         q.ablate = getenv("DCVC_ABLATE") ? atoi(getenv("DCVC_ABLATE")) : 0;     // timing experiments (wrong results)
         DCVC_HIP(hipMalloc(&q.stamps, (size_t)grid * 16 * sizeof(unsigned long long)));
-        hipLaunchKernelGGL((t128::dcb_tail128_kernel<C, G, HEADIN>), dim3(grid), dim3(t128::Geo<G>::NTHR), lds, st, q);
+        hipLaunchKernelGGL((t128::dcb_tail128_kernel<C, G, HEADIN, OSTORE>), dim3(grid), dim3(t128::Geo<G>::NTHR), lds, st, q);
         DCVC_HIP(hipStreamSynchronize(st));
         std::vector<unsigned long long> hs((size_t)grid * 16);
         DCVC_HIP(hipMemcpy(hs.data(), q.stamps, hs.size() * 8, hipMemcpyDeviceToHost));
@@ -1179,7 +1209,28 @@ int launch_tail128(const TailParams& tp, int H, int W, hipStream_t st)
         return 0;
     }
 #endif
-    hipLaunchKernelGGL((t128::dcb_tail128_kernel<C, G, HEADIN>), dim3(grid), dim3(t128::Geo<G>::NTHR), lds, st, tp);
+    hipLaunchKernelGGL((t128::dcb_tail128_kernel<C, G, HEADIN, OSTORE>), dim3(grid), dim3(t128::Geo<G>::NTHR), lds, st, tp);
+    return 0;
+}
+
+// Stages B and C of the staged small-map tail (dcb_t128.hpp): o (P x C) -> v (P x 2C) -> out.  Stage B's slices take the
+// fewest FFN chunks that keep its grid within one workgroup per CU and round (64 tiles of a 68x120 map: 4 slices).
+template <int C>
+int launch_ffn_staged(t128::FfnParams fp, hipStream_t st)
+{
+    using FC = t128::FfnCfg<C>;
+    const int tiles = (fp.P + t128::M - 1) / t128::M;
+    int nch = 1;
+    while (nch < FC::NCH && (FC::NCH % nch != 0 || tiles * (FC::NCH / nch) > 256)) ++nch;
+    fp.nch = nch;
+    int rc = set_lds(t128::ffn_up_t128_kernel<C>, FC::LDS_UP);
+    if (rc) return rc;
+    hipLaunchKernelGGL(t128::ffn_up_t128_kernel<C>, dim3(tiles, FC::NCH / nch), dim3(t128::NTHR), FC::LDS_UP, st, fp);
+    DCVC_LAUNCH_CHECK();
+    rc = set_lds(t128::ffn_down_t128_kernel<C>, FC::LDS_DOWN);
+    if (rc) return rc;
+    hipLaunchKernelGGL(t128::ffn_down_t128_kernel<C>, dim3(tiles, C / FC::SL), dim3(t128::NTHR), FC::LDS_DOWN, st, fp);
+    DCVC_LAUNCH_CHECK();
     return 0;
 }
 
@@ -1195,6 +1246,8 @@ struct ChainArgs {
     void* conv_out = nullptr;
     int64_t ldco = 0;
 };
+
+static int run_conv(const dcvc_conv* h, const ConvParams& cp, hipStream_t st);
 
 template <typename T, int MT, int NTW>
 int launch_dcb(const dcvc_dcb* h, const SrcPair& src, int H, int W, const float* quant, void* out, int64_t ldo,
@@ -1370,6 +1423,79 @@ int launch_dcb(const dcvc_dcb* h, const SrcPair& src, int H, int W, const float*
         }
     }
     if constexpr (sizeof(T) == 2 && MT == 2 && (NTW == 4 || NTW == 6 || NTW == 8)) {
+        if (t32 && t32s_enabled() && h->w3s.p != nullptr && h->w4s.p != nullptr && P < 12000) {   // (the scratch holds o and v below 12 000 pixels)
+            // staged (dcb_t128.hpp): A -> o, B -> v, C -> out; a fused successor becomes a launch of its own on the block's
+            // output (the head of the 32-pixel form, or the 1x1 conv: the same values as the fused GEMM, see gemm_c)
+            T* o_buf = slots + 3 * P * C;
+            T* v_buf = o_buf + P * C;
+            T* r_buf = out != nullptr ? reinterpret_cast<T*>(out) : a_buf;     // (a_buf: this block's `a`, dead after stage A)
+            const long ldr = out != nullptr ? (long)ldo : C;
+            TailParams ta = tp;
+            ta.wt = h->wt128.p;
+            ta.out = nullptr;
+            ta.nw1 = nullptr;
+            ta.nwt = nullptr;
+            ta.na_out = nullptr;
+            ta.ostage = o_buf;
+            int rc = launch_tail128<NTW * 64, t128::G32, false, true>(ta, H, W, st);
+            if (rc) return rc;
+            DCVC_LAUNCH_CHECK();
+            t128::FfnParams fp{};
+            fp.o = o_buf;
+            fp.v = v_buf;
+            fp.vout = v_buf;
+            fp.P = (int)P;
+            fp.w3 = h->w3s.p;
+            fp.b3 = tp.b3;
+            fp.w4 = h->w4s.p;
+            fp.b4 = tp.b4;
+            fp.ident = tp.ident;
+            fp.ldi = tp.ldi;
+            fp.shortcut = tp.shortcut;
+            fp.q = tp.q;
+            fp.c_log = tp.c_log;
+            fp.out = r_buf;
+            fp.ldo = ldr;
+            rc = launch_ffn_staged<NTW * 64>(fp, st);
+            if (rc) return rc;
+            if (ch.next) {
+                HeadParams nh{};
+                nh.src = SrcPair{r_buf, ldr, C, nullptr, 0, 0};
+                nh.H = H;
+                nh.W = W;
+                nh.C = C;
+                nh.w1128 = ch.next->w1_t128.p;
+                nh.b1 = (const float*)ch.next->b1.p;
+                nh.a_out = a_next;
+                nh.lda = C;
+                const int g32 = ((H + t128::G32::TH - 1) / t128::G32::TH) * ((W + t128::G32::TW - 1) / t128::G32::TW);
+                const size_t lds = t128::HeadCfg<NTW * 64, t128::G32>::LDS;
+                rc = set_lds(t128::dcb_head128_kernel<NTW * 64, false, t128::G32>, lds);
+                if (rc) return rc;
+                hipLaunchKernelGGL((t128::dcb_head128_kernel<NTW * 64, false, t128::G32>), dim3(g32), dim3(t128::Geo<t128::G32>::NTHR), lds, st, nh);
+                DCVC_LAUNCH_CHECK();
+            } else if (ch.conv) {
+                ConvParams cp{};
+                cp.src = SrcPair{r_buf, ldr, C, nullptr, 0, 0};
+                cp.H = cp.Ho = H;
+                cp.W = cp.Wo = W;
+                cp.KH = cp.KW = cp.stride = 1;
+                cp.pad = 0;
+                cp.N = ch.conv->n_p;
+                cp.n_log = ch.conv->cout;
+                cp.cs_p = ch.conv->cs_p;
+                cp.w = ch.conv->w.p;
+                cp.b = (const float*)ch.conv->b.p;
+                cp.q = ch.conv_q;
+                cp.epi = ch.conv->epi;
+                cp.out = ch.conv_out;
+                cp.ldo = ch.ldco;
+                rc = run_conv(ch.conv, cp, st);
+                if (rc) return rc;
+            }
+            if (ev) DCVC_HIP(hipEventRecord(ev[2], st));
+            return 0;
+        }
         if (t32) {
             tp.wt = h->wt128.p;
             tp.nwt = ch.next ? ch.next->w1_t128.p : ch.conv ? ch.conv->w_t128.p : nullptr;
@@ -1678,6 +1804,10 @@ int dcvc_dcb_create(int dtype, int cin, int c, int shortcut, const float* adapto
         rc |= pack_t128_square_any(Cp, h->w1_t128, [&](int n, int k) { return (n < C && k < C) ? ka * w1[(size_t)n * C + k] : 0.f; });
         rc |= Cp == 128 ? pack_t128<128>(h->wt128, W2, W3, W4) : Cp == 256 ? pack_t128<256>(h->wt128, W2, W3, W4) : Cp == 320 ? pack_t128<320>(h->wt128, W2, W3, W4)
                         : Cp == 384 ? pack_t128<384>(h->wt128, W2, W3, W4) : pack_t128<512>(h->wt128, W2, W3, W4);
+        if (Cp == 256 || Cp == 384 || Cp == 512) {   // the staged small-map tail
+            rc |= Cp == 256 ? pack_t128_w3<256>(h->w3s, W3) : Cp == 384 ? pack_t128_w3<384>(h->w3s, W3) : pack_t128_w3<512>(h->w3s, W3);
+            rc |= pack_t128_conv(h->w4s, 1, 1, t128::PADF, Cp, 2 * Cp, [&](int n, int, int k) { return W4(n, k); });
+        }
     }
     if (rc) return rc < 0 ? rc : dcvc::E_MEM;
     *out = h.release();
@@ -1689,7 +1819,9 @@ void dcvc_dcb_destroy(dcvc_dcb* h) { delete h; }
 size_t dcvc_dcb_scratch_bytes(const dcvc_dcb* h, int H, int W)
 {
     if (!h) return 0;
-    return (size_t)H * W * h->c_p * dcvc::elem_size(h->dtype) * 3;   // two `a` slots (chained blocks alternate) + x'
+    // two `a` slots (chained blocks alternate) + x'; small fp16 maps also o and v (2C wide) of the staged tail
+    const bool staged = h->w3s.p != nullptr && (long)H * W < 12000;
+    return (size_t)H * W * h->c_p * dcvc::elem_size(h->dtype) * (staged ? 6 : 3);
 }
 
 int dcvc_dcb_forward(const dcvc_dcb* h, const void* x0, int64_t ld0, int c0, const void* x1, int64_t ld1, int c1,
