@@ -137,12 +137,9 @@ __device__ __forceinline__ floatx16 mfma32(const half8& a, const half8& b, const
 // on the tile and its 1-pixel halo - 60 of 64 GEMM columns - from the block's input x (p.hx) and the W1 fragment stream the
 // fused-head tails use (p.hwt), instead of by a head launch; pixels outside the picture get a = 0 (the depthwise conv's zero
 // padding).  Same k order, bias, gate and fp16 rounding as the head kernels: the same `a`.
-// OSTORE (stage A of the staged small-map tail, see ffn_up_t128_kernel below): the kernel stops after o = (W2 d + b2) + x',
-// stores o (fp16, row stride C) to p.ostage and reads none of the FFN's weights.
-template <int C, class G = G128, bool HEADIN = false, bool OSTORE = false>
+template <int C, class G = G128, bool HEADIN = false>
 __global__ __launch_bounds__(Geo<G>::NTHR, G::WPS) void dcb_tail128_kernel(TailParams p)
 {
-    static_assert(!(OSTORE && HEADIN), "stage A takes `a` from a head launch");
     using TR = Traits<half_t>;
     using CF = Cfg<C, G, HEADIN>;
     using GE = Geo<G>;
@@ -223,7 +220,7 @@ __global__ __launch_bounds__(Geo<G>::NTHR, G::WPS) void dcb_tail128_kernel(TailP
     // the small tables -> LDS (visible after the first barrier of the depthwise stage); requested behind slab 0, in
     // front of the other slabs: their LDS stores wait for nothing else
     {
-        constexpr int NW16 = 9 * C * 2 / 16, NB16 = C * 4 / 16, N316 = OSTORE ? 0 : 4 * C * 4 / 16;
+        constexpr int NW16 = 9 * C * 2 / 16, NB16 = C * 4 / 16, N316 = 4 * C * 4 / 16;
         for (int i = tid; i < NW16 + NB16 + N316; i += NTHR) {
             const Vec16* src = i < NW16 ? reinterpret_cast<const Vec16*>(wd) + i
                                : i < NW16 + NB16 ? reinterpret_cast<const Vec16*>(p.bd) + (i - NW16)
@@ -367,7 +364,7 @@ __global__ __launch_bounds__(Geo<G>::NTHR, G::WPS) void dcb_tail128_kernel(TailP
         } else {
             acc[i][t] = mfma32(ring[k], g2b[t], acc[i][t]);
         }
-        if (t == PTW - 1 && (!OSTORE || s * NTW + i + D < KS * NTW)) ring[k] = wload();   // (stage A: W2's fragments only)
+        if (t == PTW - 1) ring[k] = wload();
     };
     constexpr int G2Q = NTW * PTW;                      // MFMAs per k-step
     // ---- depthwise 3x3 (zero padding) + bias -> d in bufX.  A slab goes registers -> one of two LDS halo buffers
@@ -504,18 +501,6 @@ __global__ __launch_bounds__(Geo<G>::NTHR, G::WPS) void dcb_tail128_kernel(TailP
         lds_store_vec<half_t>(bufX, LDX, m, icg, __builtin_bit_cast(Vec16, o));
     }
     __syncthreads();
-    if constexpr (OSTORE) {
-        half_t* os = reinterpret_cast<half_t*>(p.ostage);
-#pragma unroll
-        for (int k = 0; k < NID; ++k) {
-            int m, icg;
-            idmap(k, m, icg);
-            const int y = ty0 + m / TW, x = tx0 + m % TW;
-            if (y < p.H && x < p.W)
-                *reinterpret_cast<Vec16*>(os + ((long)y * p.W + x) * C + icg) = lds_load_vec<half_t>(bufX, LDX, m, icg);
-        }
-        return;
-    }
 
     STAMP(ts3);
     // ---- FFN, software-pipelined: step j = [W4 x v(j-1) -> acc] [W3 x o -> u(j+1)] with gate(u(j)) -> v(j) in between
@@ -1292,297 +1277,6 @@ __global__ __launch_bounds__(256, 1) void conv_s2_t32_kernel(ConvS2Params p)
         const int oy = ty0 + m / TW_, ox = tx0 + m % TW_;
         if (oy < p.Ho && ox < p.Wo)
             *reinterpret_cast<Vec16*>(out + ((long)oy * p.Wo + ox) * p.ldo + c) = *reinterpret_cast<const Vec16*>(bufO + m * LDO + c);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Staged DepthConvBlock tail for small maps (fp16, widths 256 / 384 / 512 below 12 000 pixels).  The 32-pixel tail above
-// streams the block's whole W2 / W3 / W4 through every CU for 32 pixels; here it is three launches on one stream:
-//   A  dcb_tail128_kernel<C, G32, false, OSTORE>: depthwise + W2 + residual -> o (fp16, P x C)
-//   B  ffn_up_t128_kernel: 128 consecutive pixels x a slice of FFN chunks: u = W3 o + b3, v = g(u_lo) + g(u_hi) -> v (P x 2C)
-//   C  ffn_down_t128_kernel: 128 consecutive pixels x a slice of 128 output channels: r = (W4 v + b4) + o [+ x'] [* q]
-// (the FFN is pointwise: its pixel tiles are runs of the flattened map, no halo).  o and v are stored as fp16 exactly where
-// the fused kernel rounds them to fp16 in LDS, and the split slices output channels only: every output sees the same MFMAs,
-// bias seeding, ascending k order and gate operations, so the values are the fused kernel's bit for bit.
-// Waves as in the 128-pixel tail: w = (channel quarter cq = w & 3, pixel half ph = w >> 2), 2 pixel tiles of 32 each.
-struct FfnParams {
-    const void* o;        // [P][C] fp16
-    const void* v;        // C: [P][2C] fp16
-    void* vout;           // B: [P][2C] fp16
-    int P;
-    const void* w3;       // B: W3 as [quarter][NCH KS + PADF] fragments
-    const float* b3;      // B: [4C] (u_lo | u_hi)
-    const void* w4;       // C: W4 as [slice][quarter][2C / 16 + PADF] fragments
-    const float* b4;      // C: [C]
-    int nch;              // B: FFN chunks (64 v columns) per slice
-    const void* ident;    // C: x' (shortcut), row stride ldi
-    long ldi;
-    int shortcut;
-    const float* q;       // C: quant step (c_log entries) or NULL
-    int c_log;
-    void* out;            // C: block output, row stride ldo
-    long ldo;
-};
-
-// W3 of chunk j for quarter cq = 32 rows: the 16 u_lo rows 64 j + 16 cq + [0, 16) | the u_hi rows they pair with (the
-// fused kernel's g3 fragments, without the W4 fragments between them)
-template <int C>
-struct FfnCfg {
-    using WC = Wcfg<C>;
-    static constexpr int KS = WC::KS, NCH = WC::NCH, LDX = WC::LDX;
-    static constexpr int DU = 8;                                  // ring depth of stage B (divides KS; 24 at C = 384 measured slower)
-    static constexpr int STREAM3 = NCH * KS + PADF;               // fragments per quarter of the W3 stream
-    static constexpr size_t LDS_UP = ((size_t)M * LDX + (size_t)M * LDV) * sizeof(half_t);
-    static constexpr int KCH = 128, LDK = KCH + PAD;              // stage C: v columns staged per chunk
-    static constexpr int DD = 8;                                  // ring depth of stage C (one staged chunk = 8 k-steps)
-    static constexpr int STREAM4 = 2 * C / 16 + PADF;             // fragments per (slice, quarter) of the W4 stream
-    static constexpr int SL = 128, LDR = SL + PAD;                // output channels per stage-C slice
-    static constexpr size_t LDS_DOWN = (size_t)2 * M * LDK * sizeof(half_t);
-    static_assert(KS % DU == 0 && (2 * C) % KCH == 0 && C % SL == 0 && LDR <= 2 * LDK, "staged tail geometry");
-    static_assert(LDS_UP <= 160 * 1024 && 2 * LDS_DOWN <= 160 * 1024, "LDS budget");
-};
-
-template <int C>
-__global__ __launch_bounds__(NTHR, 2) void ffn_up_t128_kernel(FfnParams p)
-{
-    using TR = Traits<half_t>;
-    using FC = FfnCfg<C>;
-    constexpr int KS = FC::KS, LDX = FC::LDX, D = FC::DU, V = 8, G8 = C / 64, RPP = NTHR / 8;
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    half_t* bufO = reinterpret_cast<half_t*>(smem);         // the o tile [M][LDX]
-    half_t* bufV = bufO + M * LDX;                           // one v chunk [M][LDV]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int cqw = wave & 3, ph = wave >> 2;
-    const int pl = lane & 31, hh = lane >> 5;
-    const int p0 = blockIdx.x * M, j0 = blockIdx.y * p.nch;
-    const int prow = (ph * PTW) * 32 + pl;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    constexpr int OOB = 0x7FFFFFF0;
-
-    // this quarter's W3 stream from the slice's first chunk (reads past its end: the stream's padding / zeros)
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(p.w3)) + (size_t)cqw * FC::STREAM3 * 1024, 0, FC::STREAM3 * 1024, 0x00020000);
-    int woff = lane * 16 + j0 * KS * 1024;
-    auto wnext = [&]() __attribute__((always_inline)) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrs, woff, 0, 0);
-        woff += 1024;
-        return __builtin_bit_cast(half8, v);
-    };
-    // o tile -> LDS (pixels beyond the map read zeros); the ring's first fragments are requested behind it
-    half8 ring[D];
-    {
-        const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<void*>(p.o), 0, (int)((long)p.P * C * 2), 0x00020000);
-        u32x4 ov[2 * G8];
-#pragma unroll
-        for (int k = 0; k < 2 * G8; ++k) {
-            const int m = (tid >> 3) + RPP * (k / G8), c = ((tid & 7) + 8 * (k % G8)) * V;
-            ov[k] = __builtin_amdgcn_raw_buffer_load_b128(ors, p0 + m < p.P ? ((p0 + m) * C + c) * 2 : OOB, 0, 0);
-        }
-#pragma unroll
-        for (int k = 0; k < D; ++k) ring[k] = wnext();
-#pragma unroll
-        for (int k = 0; k < 2 * G8; ++k)
-            *reinterpret_cast<u32x4*>(bufO + ((tid >> 3) + RPP * (k / G8)) * LDX + ((tid & 7) + 8 * (k % G8)) * V) = ov[k];
-        __syncthreads();
-    }
-    {
-        const half_t* xb = bufO + prow * LDX + 8 * hh;
-        const float* b3w = p.b3 + 16 * cqw + 4 * hh;
-        half_t* vout = reinterpret_cast<half_t*>(p.vout);
-        for (int jj = 0; jj < p.nch; ++jj) {
-            const int j = j0 + jj;
-            // u starts at the bias (lane's rows: quads 8 g + 4 hh of u_lo, then of u_hi), as in the fused kernel
-            floatx16 biasv;
-            {
-                const floatx4 l0 = load_f4(b3w + 64 * j), l1 = load_f4(b3w + 64 * j + 8);
-                const floatx4 h0 = load_f4(b3w + 64 * j + 2 * C), h1 = load_f4(b3w + 64 * j + 2 * C + 8);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    biasv[r] = l0[r];
-                    biasv[4 + r] = l1[r];
-                    biasv[8 + r] = h0[r];
-                    biasv[12 + r] = h1[r];
-                }
-            }
-            floatx16 u[PTW];
-            half8 bc[PTW], bn[PTW];
-#pragma unroll
-            for (int t = 0; t < PTW; ++t) bc[t] = *reinterpret_cast<const half8*>(xb + t * 32 * LDX);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-#pragma unroll
-                for (int t = 0; t < PTW; ++t) {
-                    if (s + 1 < KS) bn[t] = *reinterpret_cast<const half8*>(xb + t * 32 * LDX + (s + 1) * 16);
-                    u[t] = mfma32(ring[s % D], bc[t], s == 0 ? biasv : u[t]);
-                    if (t == PTW - 1) ring[s % D] = wnext();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#pragma unroll
-                for (int t = 0; t < PTW; ++t) bc[t] = bn[t];
-            }
-            __syncthreads();     // every thread has finished storing the previous chunk's v
-            // v = g(u_lo) + g(u_hi) -> fp16 -> bufV columns 16 cq + 8 g + 4 hh + [0, 4) (Traits<half_t>::gate2: the operations of
-            // the fused kernel's gate_piece)
-#pragma unroll
-            for (int t = 0; t < PTW; ++t)
-#pragma unroll
-                for (int g = 0; g < 2; ++g) {
-                    floatx4 vq;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) vq[e] = TR::gate2(u[t][4 * g + e], u[t][8 + 4 * g + e]);
-                    lds_store_quad<half_t>(bufV, LDV, prow + 32 * t, 16 * cqw + 8 * g + 4 * hh, vq);
-                }
-            __syncthreads();
-            // the chunk's 64 columns of v: 128 bytes per pixel, eight threads per pixel
-#pragma unroll
-            for (int k = 0; k < M / RPP; ++k) {
-                const int m = (tid >> 3) + RPP * k, c = (tid & 7) * V;
-                if (p0 + m < p.P)
-                    *reinterpret_cast<Vec16*>(vout + (long)(p0 + m) * (2 * C) + 64 * j + c) = *reinterpret_cast<const Vec16*>(bufV + m * LDV + c);
-            }
-        }
-    }
-}
-
-template <int C>
-__global__ __launch_bounds__(NTHR, 4) void ffn_down_t128_kernel(FfnParams p)
-{
-    using FC = FfnCfg<C>;
-    constexpr int KCH = FC::KCH, LDK = FC::LDK, D = FC::DD, SL = FC::SL, LDR = FC::LDR, V = 8, K2 = 2 * C;
-    constexpr int TPR = KCH / V, RPK = NTHR / TPR, NLK = M / RPK;   // staging: threads per row, rows per pass, passes
-    constexpr int NO = M * SL / V / NTHR;                           // o / output vectors per thread
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    half_t* bufK = reinterpret_cast<half_t*>(smem);          // two staged v chunks [M][LDK], then the r tile [M][LDR]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int cqw = wave & 3, ph = wave >> 2;
-    const int pl = lane & 31, hh = lane >> 5;
-    const int p0 = blockIdx.x * M, slice = blockIdx.y, n0 = slice * SL;
-    const int prow = (ph * PTW) * 32 + pl;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    constexpr int OOB = 0x7FFFFFF0;
-
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(p.w4)) + ((size_t)slice * 4 + cqw) * FC::STREAM4 * 1024, 0,
-        FC::STREAM4 * 1024, 0x00020000);
-    int woff = lane * 16;
-    auto wnext = [&]() __attribute__((always_inline)) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrs, woff, 0, 0);
-        woff += 1024;
-        return __builtin_bit_cast(half8, v);
-    };
-    const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void*>(p.v), 0, (int)((long)p.P * K2 * 2), 0x00020000);
-    u32x4 pre[NLK];
-    auto fetch = [&](int kc) __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < NLK; ++k) {
-            const int m = tid / TPR + RPK * k, c = (tid % TPR) * V;
-            pre[k] = __builtin_amdgcn_raw_buffer_load_b128(vrs, p0 + m < p.P ? ((p0 + m) * K2 + kc * KCH + c) * 2 : OOB, 0, 0);
-        }
-    };
-    auto stage = [&](half_t* buf) __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < NLK; ++k) *reinterpret_cast<u32x4*>(buf + (tid / TPR + RPK * k) * LDK + (tid % TPR) * V) = pre[k];
-    };
-    fetch(0);
-    half8 ring[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) ring[k] = wnext();
-    // the o slice of the tile (for the epilogue), requested now
-    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.o), 0, (int)((long)p.P * C * 2), 0x00020000);
-    auto omap = [&](int k, int& m, int& c) __attribute__((always_inline)) {
-        m = (tid >> 4) + (NTHR / 16) * k;
-        c = (tid & 15) * V;
-    };
-    u32x4 ov[NO];
-#pragma unroll
-    for (int k = 0; k < NO; ++k) {
-        int m, c;
-        omap(k, m, c);
-        ov[k] = __builtin_amdgcn_raw_buffer_load_b128(ors, p0 + m < p.P ? ((p0 + m) * C + n0 + c) * 2 : OOB, 0, 0);
-    }
-    floatx16 acc[PTW];
-#pragma unroll
-    for (int t = 0; t < PTW; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    // acc = W4 v, k ascending over the 2C hidden columns (from 0: the fused kernel's order), KCH columns per staged chunk
-    constexpr int NKC = K2 / KCH;
-    for (int kc = 0; kc < NKC; ++kc) {
-        half_t* buf = bufK + (kc & 1) * M * LDK;
-        stage(buf);
-        __syncthreads();
-        if (kc + 1 < NKC) fetch(kc + 1);
-        const half_t* xb = buf + prow * LDK + 8 * hh;
-        half8 bc[PTW], bn[PTW];
-#pragma unroll
-        for (int t = 0; t < PTW; ++t) bc[t] = *reinterpret_cast<const half8*>(xb + t * 32 * LDK);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < KCH / 16; ++s) {
-#pragma unroll
-            for (int t = 0; t < PTW; ++t) {
-                if (s + 1 < KCH / 16) bn[t] = *reinterpret_cast<const half8*>(xb + t * 32 * LDK + (s + 1) * 16);
-                acc[t] = mfma32(ring[s % D], bc[t], acc[t]);
-                if (t == PTW - 1) ring[s % D] = wnext();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int t = 0; t < PTW; ++t) bc[t] = bn[t];
-        }
-    }
-    __syncthreads();       // every wave has finished reading the staged chunks: the r tile replaces them
-    half_t* bufR = bufK;
-#pragma unroll
-    for (int k = 0; k < NO; ++k) {
-        int m, c;
-        omap(k, m, c);
-        *reinterpret_cast<u32x4*>(bufR + m * LDR + c) = ov[k];
-    }
-    __syncthreads();
-    // r = (W4 v + b4) + o, in place (each element is owned by one lane), as in the fused kernel
-    {
-        const int chb = 32 * cqw + 4 * hh;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const floatx4 bias = load_f4(p.b4 + n0 + chb + 8 * g);
-#pragma unroll
-            for (int t = 0; t < PTW; ++t) {
-                const floatx4 o = lds_load_quad<half_t>(bufR, LDR, prow + 32 * t, chb + 8 * g);
-                floatx4 v = {acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
-                lds_store_quad<half_t>(bufR, LDR, prow + 32 * t, chb + 8 * g, (v + bias) + o);
-            }
-        }
-    }
-    __syncthreads();
-    // out = r [+ x'] [* q]
-    const half_t* ident = reinterpret_cast<const half_t*>(p.ident);
-    half_t* out = reinterpret_cast<half_t*>(p.out);
-#pragma unroll
-    for (int k = 0; k < NO; ++k) {
-        int m, c;
-        omap(k, m, c);
-        if (p0 + m < p.P) {
-            const long pix = p0 + m;
-            const int icg = n0 + c;
-            float r[V];
-            unpack16<half_t>(*reinterpret_cast<const Vec16*>(bufR + m * LDR + c), r);
-            if (p.shortcut) {
-                float id[V];
-                unpack16<half_t>(*reinterpret_cast<const Vec16*>(ident + pix * p.ldi + icg), id);
-#pragma unroll
-                for (int j = 0; j < V; ++j) r[j] = r[j] + id[j];
-            }
-            if (p.q != nullptr) {
-#pragma unroll
-                for (int j = 0; j < V; ++j) r[j] = r[j] * ((icg + j) < p.c_log ? p.q[icg + j] : 1.0f);
-            }
-            *reinterpret_cast<Vec16*>(out + pix * p.ldo + icg) = pack16<half_t>(r);
-        }
     }
 }
 

@@ -8,6 +8,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -232,7 +233,6 @@ struct TailParams {
     const void* hwt;     // dcb_tail128_kernel<..., HEADIN>: W1 as the per-quarter fragment stream (the one a fused-head tail reads)
     const void* wt;      // dcb_tail128_kernel: the tail's weights as per-quarter fragment streams (dcb_t128.hpp)
     const void* nwt;     // ... and the fused next-block head's / 1x1 conv's (the same matrix as nw1, 32x32x16 fragments)
-    void* ostage;        // dcb_tail128_kernel<..., OSTORE> (stage A of the staged small-map tail): o, P x C fp16
     int ablate;          // debug: bit0 skip dw, bit1 skip GEMM2, bit2 skip FFN GEMM3, bit3 skip FFN GEMM4
     unsigned long long* stamps;   // diagnostic build only (DCVC_STAMPS): 8 cycle counters per workgroup
 };
@@ -947,7 +947,6 @@ struct dcvc_dcb {
     DevBuf wa_t128; // fp16, widths 256 / 320 / 384: the adaptor as a fragment stream (dcb_head128_kernel)
     DevBuf w1_t128; // fp16, widths 256 / 320 / 384: W1 as a fragment stream (the previous block's tail computes this block's head)
     DevBuf wt128;   // fp16, widths 256 / 320 / 384: W2 | W3 | W4 once more as the fragment streams of dcb_tail128_kernel
-    DevBuf w3s, w4s;    // fp16, widths 256 / 384 / 512: W3 and W4 as the streams of the staged small-map tail (ffn_up / ffn_down_t128_kernel)
 };
 
 struct dcvc_conv {
@@ -1044,26 +1043,6 @@ int pack_t128(DevBuf& dst, const std::function<float(int, int)>& W2, const std::
     return dst.upload(buf.data(), buf.size() * sizeof(half_t));
 }
 
-// W3 for ffn_up_t128_kernel: per quarter, chunk by chunk, the KS fragments of the fused stream's g3(j)
-template <int C>
-int pack_t128_w3(DevBuf& dst, const std::function<float(int, int)>& W3)
-{
-    using FC = t128::FfnCfg<C>;
-    std::vector<half_t> buf((size_t)4 * FC::STREAM3 * 512, (half_t)0.f);
-    for (int cq = 0; cq < 4; ++cq) {
-        size_t f = 0;
-        for (int j = 0; j < FC::NCH; ++j)
-            for (int s = 0; s < FC::KS; ++s, ++f) {
-                half_t* o = &buf[((size_t)cq * FC::STREAM3 + f) * 512];
-                for (int l = 0; l < 64; ++l) {
-                    const int r = l & 31, row = (r < 16 ? 0 : 2 * C - 16) + 64 * j + 16 * cq + r;
-                    for (int jj = 0; jj < 8; ++jj) o[l * 8 + jj] = (half_t)W3(row, 16 * s + 8 * (l >> 5) + jj);
-                }
-            }
-    }
-    return dst.upload(buf.data(), buf.size() * sizeof(half_t));
-}
-
 inline bool t128_width_ok(int c_p) { return c_p == 128 || c_p == 256 || c_p == 320 || c_p == 384 || c_p == 512; }   // (128, 512: 32-pixel tiles only)
 
 // a C x C matrix (next block's first conv, a fused 1x1 conv) as the per-quarter fragment stream gemm_c reads
@@ -1126,112 +1105,122 @@ inline int pack_t128_conv(DevBuf& dst, int ntw, int taps, int padf, int Np, int 
     return dst.upload(buf.data(), buf.size() * sizeof(half_t));
 }
 
+// f(std::integral_constant<int, C>()) for the width C = c_p of a 128-pixel / 32-pixel form (t128_width_ok)
+template <typename F>
+int visit_t128_width(int c_p, F&& f)
+{
+    switch (c_p) {
+    case 128: return f(std::integral_constant<int, 128>());
+    case 256: return f(std::integral_constant<int, 256>());
+    case 320: return f(std::integral_constant<int, 320>());
+    case 384: return f(std::integral_constant<int, 384>());
+    case 512: return f(std::integral_constant<int, 512>());
+    default: dcvc::set_error("no fragment-stream form for width %d", c_p); return dcvc::E_ARG;
+    }
+}
+
 inline int pack_t128_square_any(int c_p, DevBuf& dst, const std::function<float(int, int)>& W)
 {
-    return c_p == 128 ? pack_t128_square<128>(dst, W) : c_p == 256 ? pack_t128_square<256>(dst, W) : c_p == 320 ? pack_t128_square<320>(dst, W)
-                      : c_p == 384 ? pack_t128_square<384>(dst, W) : pack_t128_square<512>(dst, W);
+    return visit_t128_width(c_p, [&](auto w) { return pack_t128_square<decltype(w)::value>(dst, W); });
 }
 
-// DCVC_T128=0 keeps the 64-pixel tails on large maps (A/B measurements; both forms pass the same layer tests)
-static bool t128_enabled()
+// Developer switches, read once per process.  DCVC_T128=0, DCVC_T32=0, DCVC_H128=0 and DCVC_C128=0 select the reference
+// kernels of the bit-identity tests (and A/B measurements): dcb_tail_kernel for the 128-pixel tails on large maps (T128, which
+// also turns off every other fragment-stream form of the block) and for the 32-pixel tails on small maps (T32),
+// dcb_head_kernel for the 128-pixel heads (H128), conv_kernel for the 3x3 and stride-2 convs (C128).
+struct Switches {
+    bool t128, t32, h128, c128;
+#ifdef DCVC_DIAG   // developer build only (make diag): forced pixel tiles, in-kernel phase stamps, phase ablation (wrong results)
+    int mt, conv_mt, ablate;
+    bool stamps;
+#endif
+};
+
+static const Switches& switches()
 {
-    static const bool on = !(getenv("DCVC_T128") && atoi(getenv("DCVC_T128")) == 0);
-    return on;
+    static const Switches sw = [] {
+        auto on = [](const char* name) { const char* v = getenv(name); return !(v && atoi(v) == 0); };
+        auto num = [](const char* name) { const char* v = getenv(name); return v ? atoi(v) : 0; };
+        Switches s{};
+        s.t128 = on("DCVC_T128");
+        s.t32 = on("DCVC_T32");
+        s.h128 = on("DCVC_H128");
+        s.c128 = on("DCVC_C128");
+#ifdef DCVC_DIAG
+        s.mt = num("DCVC_MT");
+        s.conv_mt = num("DCVC_CONV_MT");
+        s.ablate = num("DCVC_ABLATE");
+        s.stamps = getenv("DCVC_STAMPS") != nullptr;
+#endif
+        (void)num;
+        return s;
+    }();
+    return sw;
 }
 
-static bool t32_enabled()    // DCVC_T32=0: small-map tails (widths 256 / 384) by dcb_tail_kernel (A/B measurements, bit-identity checks)
+template <typename K, typename P>
+int launch_kernel(K kernel, dim3 grid, int threads, size_t lds, hipStream_t st, const P& p)
 {
-    static const bool on = !(getenv("DCVC_T32") && atoi(getenv("DCVC_T32")) == 0);
-    return on;
+    int rc = set_lds(kernel, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, p);
+    return 0;
 }
 
-// DCVC_T32S=1: the staged small-map tail (three launches, dcb_t128.hpp) instead of the fused 32-pixel one.  Off by default:
-// bit-identical, but not faster alone (docs/experiments.md, round 5)
-static bool t32s_enabled()
+#ifdef DCVC_DIAG
+// Developer build only: waits for a stamped launch, copies its `per` cycle stamps per workgroup to `hs` and frees them.  Every
+// 16th call (`calls`: the launcher's own count) prints "[<tag>] <name>=<median over the workgroups> ..." for each named stamp
+// (nullptr: not printed) and sets `printed`; the caller then ends the line.
+static int stamp_medians(unsigned long long* d, int grid, int per, const char* const* names, const char* tag, int& calls,
+                         hipStream_t st, std::vector<unsigned long long>& hs, bool& printed)
 {
-    static const bool on = getenv("DCVC_T32S") && atoi(getenv("DCVC_T32S")) != 0;
-    return on;
+    DCVC_HIP(hipStreamSynchronize(st));
+    hs.resize((size_t)grid * per);
+    DCVC_HIP(hipMemcpy(hs.data(), d, hs.size() * 8, hipMemcpyDeviceToHost));
+    (void)hipFree(d);
+    printed = calls++ % 16 == 15;
+    if (!printed) return 0;
+    fprintf(stderr, "[%s]", tag);
+    for (int k = 0; k < per; ++k) {
+        if (!names[k]) continue;
+        std::vector<unsigned long long> v(grid);
+        for (int b = 0; b < grid; ++b) v[b] = hs[(size_t)b * per + k];
+        std::sort(v.begin(), v.end());
+        fprintf(stderr, " %s=%llu", names[k], v[grid / 2]);
+    }
+    return 0;
 }
+#endif
 
-static bool t32_128_enabled()    // DCVC_T32_128=0: width-128 blocks by dcb_tail_kernel<..., HEADIN> (A/B measurements, bit-identity checks)
-{
-    static const bool on = !(getenv("DCVC_T32_128") && atoi(getenv("DCVC_T32_128")) == 0);
-    return on;
-}
-
-static bool t32h_enabled()      // DCVC_T32H=0: width 256 keeps its separate head launch in front of the 32-pixel tail (A/B)
-{
-    static const bool on = !(getenv("DCVC_T32H") && atoi(getenv("DCVC_T32H")) == 0);
-    return on;
-}
-
-static bool h128_enabled()   // DCVC_H128=0: large-map heads by dcb_head_kernel (A/B measurements, bit-identity checks)
-{
-    static const bool on = !(getenv("DCVC_H128") && atoi(getenv("DCVC_H128")) == 0);
-    return on;
-}
-
-template <int C, class G = t128::G128, bool HEADIN = false, bool OSTORE = false>
+template <int C, class G = t128::G128, bool HEADIN = false>
 int launch_tail128(const TailParams& tp, int H, int W, hipStream_t st)
 {
     const int grid = ((H + G::TH - 1) / G::TH) * ((W + G::TW - 1) / G::TW);
     const size_t lds = t128::Cfg<C, G, HEADIN>::LDS;
-    int rc = set_lds(t128::dcb_tail128_kernel<C, G, HEADIN, OSTORE>, lds);
-    if (rc) return rc;
 #ifdef DCVC_DIAG      // developer build only (make diag): in-kernel phase stamps, median over the workgroups
-    static const bool want_stamps = getenv("DCVC_STAMPS") != nullptr;
-    if (want_stamps) {
+    if (switches().stamps) {
         TailParams q = tp;
-        q.ablate = getenv("DCVC_ABLATE") ? atoi(getenv("DCVC_ABLATE")) : 0;     // timing experiments (wrong results)
         DCVC_HIP(hipMalloc(&q.stamps, (size_t)grid * 16 * sizeof(unsigned long long)));
-        hipLaunchKernelGGL((t128::dcb_tail128_kernel<C, G, HEADIN, OSTORE>), dim3(grid), dim3(t128::Geo<G>::NTHR), lds, st, q);
-        DCVC_HIP(hipStreamSynchronize(st));
-        std::vector<unsigned long long> hs((size_t)grid * 16);
-        DCVC_HIP(hipMemcpy(hs.data(), q.stamps, hs.size() * 8, hipMemcpyDeviceToHost));
-        (void)hipFree(q.stamps);
-        static int printed = 0;
-        if (printed++ % 16 == 15) {
-            const char* names[15] = {"loads+dw", "gemm2", "o_pass", "u0", "ffn", "r+store", "", "", "dw:issue+stage0", "barrier0", "slab0", "slab1", "slab2", "slab3", "fused"};
-            fprintf(stderr, "[t128 stamps C=%d tile=%d grid=%d]", C, t128::Geo<G>::M, grid);
-            constexpr int nslab = C / G::DW_SLAB;      // the kernel stamps min(nslab, 4) slabs: print only those
-            for (int k = 0; k < 15; ++k) {
-                if (k == 6 || k == 7 || (k >= 10 && k <= 13 && k - 10 >= nslab)) continue;
-                std::vector<unsigned long long> v(grid);
-                for (int b = 0; b < grid; ++b) v[b] = hs[(size_t)b * 16 + k];
-                std::sort(v.begin(), v.end());
-                fprintf(stderr, " %s=%llu", names[k], v[grid / 2]);
-            }
-            std::vector<unsigned long long> du(grid);
-            for (int b = 0; b < grid; ++b) du[b] = hs[(size_t)b * 16 + 7] - hs[(size_t)b * 16 + 6];
-            std::sort(du.begin(), du.end());
-            fprintf(stderr, " | wg total min/med/max %llu %llu %llu\n", du[0], du[grid / 2], du[grid - 1]);
-        }
+        int rc = launch_kernel(t128::dcb_tail128_kernel<C, G, HEADIN>, dim3(grid), t128::Geo<G>::NTHR, lds, st, q);
+        if (rc) return rc;
+        const char* names[16] = {"loads+dw", "gemm2", "o_pass", "u0", "ffn", "r+store", nullptr, nullptr, "dw:issue+stage0",
+                                 "barrier0", "slab0", "slab1", "slab2", "slab3", "fused", nullptr};
+        for (int k = C / G::DW_SLAB; k < 4; ++k) names[10 + k] = nullptr;    // the kernel stamps min(slabs, 4) slabs
+        char tag[64];
+        snprintf(tag, sizeof tag, "t128 stamps C=%d tile=%d grid=%d", C, t128::Geo<G>::M, grid);
+        static int calls = 0;
+        std::vector<unsigned long long> hs;
+        bool printed = false;
+        rc = stamp_medians(q.stamps, grid, 16, names, tag, calls, st, hs, printed);
+        if (rc || !printed) return rc;
+        std::vector<unsigned long long> du(grid);
+        for (int b = 0; b < grid; ++b) du[b] = hs[(size_t)b * 16 + 7] - hs[(size_t)b * 16 + 6];
+        std::sort(du.begin(), du.end());
+        fprintf(stderr, " | wg total min/med/max %llu %llu %llu\n", du[0], du[grid / 2], du[grid - 1]);
         return 0;
     }
 #endif
-    hipLaunchKernelGGL((t128::dcb_tail128_kernel<C, G, HEADIN, OSTORE>), dim3(grid), dim3(t128::Geo<G>::NTHR), lds, st, tp);
-    return 0;
-}
-
-// Stages B and C of the staged small-map tail (dcb_t128.hpp): o (P x C) -> v (P x 2C) -> out.  Stage B's slices take the
-// fewest FFN chunks that keep its grid within one workgroup per CU and round (64 tiles of a 68x120 map: 4 slices).
-template <int C>
-int launch_ffn_staged(t128::FfnParams fp, hipStream_t st)
-{
-    using FC = t128::FfnCfg<C>;
-    const int tiles = (fp.P + t128::M - 1) / t128::M;
-    int nch = 1;
-    while (nch < FC::NCH && (FC::NCH % nch != 0 || tiles * (FC::NCH / nch) > 256)) ++nch;
-    fp.nch = nch;
-    int rc = set_lds(t128::ffn_up_t128_kernel<C>, FC::LDS_UP);
-    if (rc) return rc;
-    hipLaunchKernelGGL(t128::ffn_up_t128_kernel<C>, dim3(tiles, FC::NCH / nch), dim3(t128::NTHR), FC::LDS_UP, st, fp);
-    DCVC_LAUNCH_CHECK();
-    rc = set_lds(t128::ffn_down_t128_kernel<C>, FC::LDS_DOWN);
-    if (rc) return rc;
-    hipLaunchKernelGGL(t128::ffn_down_t128_kernel<C>, dim3(tiles, C / FC::SL), dim3(t128::NTHR), FC::LDS_DOWN, st, fp);
-    DCVC_LAUNCH_CHECK();
-    return 0;
+    return launch_kernel(t128::dcb_tail128_kernel<C, G, HEADIN>, dim3(grid), t128::Geo<G>::NTHR, lds, st, tp);
 }
 
 // chained launches: this block's `a` lives in scratch slot a_slot (already there if head_done: the previous
@@ -1247,12 +1236,135 @@ struct ChainArgs {
     int64_t ldco = 0;
 };
 
-static int run_conv(const dcvc_conv* h, const ConvParams& cp, hipStream_t st);
+// Pixel-tile selection (f16): 16*MT pixels per workgroup.  Small feature maps take 32-pixel tiles so
+// that the grid still covers the 256 CUs (measured: 68x120 maps 15-25 % faster); 128-pixel tiles
+// (MT = 8, one workgroup per CU) were measured slower than 64-pixel tiles at two workgroups per CU
+// (80 vs 63 us at C = 256, 136x240) and are not instantiated.  (Developer build: DCVC_MT overrides.)
+static int pick_mt_f16(int H, int W)
+{
+#ifdef DCVC_DIAG
+    if (switches().mt == 2 || switches().mt == 4) return switches().mt;
+#endif
+    return (long)H * W >= 12000 ? 4 : 2;
+}
+
+// The block kernels each (dtype, pixel tile 16 mt, channel tiles per wave ntw = c_p / 64) is built with; plan_dcb names only
+// these and launch_dcb instantiates only these.
+// dcb_tail128_kernel<64 ntw, G, headin>: G128 on 64-pixel maps (mt 4), G32 on 32-pixel maps (mt 2)
+constexpr bool has_tail128(bool f16, int mt, int ntw, bool headin)
+{
+    return f16 && (mt == 4 ? !headin && (ntw == 4 || ntw == 5 || ntw == 6)
+                           : headin ? (ntw == 2 || ntw == 4) : (ntw == 4 || ntw == 6 || ntw == 8));
+}
+// dcb_head128_kernel<64 ntw, adapt, G>
+constexpr bool has_head128(bool f16, int mt, int ntw)
+{
+    return f16 && (mt == 4 ? (ntw == 4 || ntw == 5 || ntw == 6) : (ntw == 4 || ntw == 6 || ntw == 8));
+}
+// dcb_tail_kernel<..., HEADIN>
+constexpr bool has_tail_headin(bool f16, int mt, int ntw) { return f16 && mt == 2 && (ntw <= 4 || ntw == 6); }
+
+// dcb_tail_kernel<T, MT, ntw, nw, rag>: widths of 384 and up (6+ channel tiles per wave) fit one workgroup per CU only.
+// Eight waves (two per SIMD, half the channel tiles each, <= 256 VGPRs) give every SIMD a second wave of the same tile to
+// switch to: 144 -> 117 us at C=384, 136x240.  At C <= 256 two independent 4-wave workgroups per CU do that job better
+// (8 waves there measured 116 us vs 63 us; 128-pixel tiles on 8 waves, MT = 8 x NTW = 2, spill at 256 VGPRs and measured
+// 66 us against 59 us for the same build).  C = 320 (5 tiles) runs 20 tiles on 8 waves: 4 waves x 3 + 4 waves x 2 (RAG).
+struct TailForm {
+    int ntw, nw;
+    bool rag;
+};
+constexpr TailForm tail_form(bool f16, int ntw)
+{
+    return !f16 ? TailForm{ntw, 4, false} : ntw == 5 ? TailForm{3, 8, true}
+                                          : ntw >= 6 && ntw % 2 == 0 ? TailForm{ntw / 2, 8, false} : TailForm{ntw, 4, false};
+}
+
+// What one DepthConvBlock launch runs: an optional head kernel (a = wsilu(conv1(x')), with the adaptor x' first) and a tail
+// kernel.  Fragment-stream kernels (dcb_t128.hpp) use geometry G128 at mt 4 and G32 at mt 2.
+struct DcbPlan {
+    enum class Head { none, head128, head } head = Head::none;   // none: `a` is written by the predecessor's tail or the tail computes it
+    bool head_adapt = false;       // the head's adaptor form
+    bool head_t32 = false;         // dcb_head_kernel (adaptor) on 32-pixel tiles in front of a 64-pixel tail
+    enum class Tail { tail128, tail } tail = Tail::tail;
+    bool headin = false;           // the tail computes the block's head on its tile + halo
+    int mt = 2, ntw = 1;           // the block's pixel tile (16 mt pixels) and channel tiles per wave (c_p / 64)
+    TailForm form{1, 4, false};    // Tail::tail: dcb_tail_kernel<T, mt, form.ntw, form.nw, form.rag, headin>
+    const void* nwt = nullptr;     // Tail::tail128: the fused successor's fragment stream (next block's W1, or the 1x1 conv)
+};
+
+static DcbPlan plan_dcb(const dcvc_dcb* h, const SrcPair& src, int H, int W, const ChainArgs& ch)
+{
+    const Switches& sw = switches();
+    const bool f16 = h->dtype == DCVC_F16;
+    DcbPlan pl;
+    pl.mt = f16 ? pick_mt_f16(H, W) : 2;
+    pl.ntw = h->c_p / 64;
+    const int mt = pl.mt, ntw = pl.ntw;
+    pl.nwt = ch.next ? ch.next->w1_t128.p : ch.conv ? ch.conv->w_t128.p : nullptr;
+    // the fragment-stream tails also need a fused successor's weights as a fragment stream
+    const bool t128 = sw.t128 && h->wt128.p != nullptr && (pl.nwt != nullptr || (!ch.next && !ch.conv));
+    // the block's own head could run inside its tail: no adaptor, one source, not computed by the predecessor
+    const bool own_head = !ch.head_done && !ch.separate_head && !h->adapt && src.c1 == 0;
+
+    // ---- tail
+    if (has_tail128(f16, mt, ntw, true) && t128 && sw.t32 && h->w1_t128.p != nullptr && own_head) {
+        // Small maps, widths 128 and 256: the 32-pixel fragment-stream tail with the block's first conv computed inside on the
+        // tile + halo.  Width 128: the hyper path's blocks on 17x30 ... 68x120 maps, where dcb_tail_kernel<..., HEADIN> ran
+        // before.  Width 256: one launch of 21.5 us instead of 6.1 + 17.5 us at 68x120.  (At width 384 the head on the
+        // 60-pixel halo tile costs more than the head launch it saves: 41.9 against 8.0 + 32.1 us - not used.)
+        pl.tail = DcbPlan::Tail::tail128;
+        pl.headin = true;
+    } else if (has_tail128(f16, mt, ntw, false) && t128 && (mt == 4 || sw.t32)) {
+        // Large maps, widths 256 / 320 / 384: 128-pixel tiles, one 4-wave workgroup per CU, gate pipelined into the MFMA
+        // stream.  Small maps, widths 256 / 384 / 512: its 32-pixel form (geometry G32); `a` comes from a head launch or
+        // the predecessor's tail.
+        pl.tail = DcbPlan::Tail::tail128;
+    } else {
+        // Small maps, block without adaptor, one source: no head launch - dcb_tail_kernel<..., HEADIN> computes `a` on its
+        // tile + halo itself
+        pl.tail = DcbPlan::Tail::tail;
+        pl.headin = has_tail_headin(f16, mt, ntw) && own_head;
+        pl.form = tail_form(f16, ntw);
+    }
+
+    // ---- head
+    const int kin = src.c0 + src.c1;
+    if (ch.head_done || pl.headin) {
+        pl.head = DcbPlan::Head::none;
+    } else if (sw.t128 && sw.h128 && has_head128(f16, mt, ntw) && (mt == 4 || pl.tail == DcbPlan::Tail::tail128) &&
+               h->w1_t128.p != nullptr &&
+               (h->adapt ? (h->wa_t128.p != nullptr && src.c0 % 64 == 0 && src.c1 % 64 == 0 && kin == h->cin_p)
+                         : (src.c1 == 0 && src.c0 == ntw * 64))) {
+        // Widths 256 / 320 / 384 on large maps, 256 / 384 / 512 in front of the 32-pixel fragment-stream tails: the head in
+        // the form of dcb_t128.hpp (sources of 64-channel multiples)
+        pl.head = DcbPlan::Head::head128;
+        pl.head_adapt = h->adapt;
+    } else {
+        pl.head = DcbPlan::Head::head;
+        pl.head_adapt = h->adapt;
+        // Two sources go through LDS one at a time (half the staging buffer: a 64-pixel tile of 256 + 256 channels then
+        // leaves room for two workgroups per CU, i.e. half the weight fragments per pixel of the 32-pixel form).  A 64-pixel
+        // tile of a wide two-source input that still needs more than 80 KiB leaves room for one workgroup per CU (two rounds
+        // over a 136x240 map); 32-pixel tiles fit three per CU (97 -> 88 us for head + tail at 256 + 256 -> 256).  Head and
+        // tail tile shapes are independent.
+        const int kstage = src.c1 > 0 ? std::max(src.c0, src.c1) : kin;
+        pl.head_t32 = h->adapt && mt == 4 && head_lds<half_t, 4>(kstage, h->c_p, true) > 80 * 1024;
+    }
+    return pl;
+}
+
+static int not_built(const char* what, const DcbPlan& pl)
+{
+    dcvc::set_error("%s is not instantiated for mt %d, ntw %d", what, pl.mt, pl.ntw);
+    return dcvc::E_ARG;
+}
 
 template <typename T, int MT, int NTW>
-int launch_dcb(const dcvc_dcb* h, const SrcPair& src, int H, int W, const float* quant, void* out, int64_t ldo,
-               void* scratch, hipStream_t st, hipEvent_t* ev = nullptr, ChainArgs ch = ChainArgs())
+int launch_dcb(const DcbPlan& pl, const dcvc_dcb* h, const SrcPair& src, int H, int W, const float* quant, void* out,
+               int64_t ldo, void* scratch, hipStream_t st, hipEvent_t* ev, const ChainArgs& ch)
 {
+    constexpr bool f16 = sizeof(T) == 2;
+    using G = typename std::conditional<MT == 4, t128::G128, t128::G32>::type;
     const int C = h->c_p;
     const int grid = ((H + Tile<MT>::TH - 1) / Tile<MT>::TH) * ((W + Tile<MT>::TW - 1) / Tile<MT>::TW);
     const size_t P = (size_t)H * W;
@@ -1273,90 +1385,9 @@ int launch_dcb(const dcvc_dcb* h, const SrcPair& src, int H, int W, const float*
     hp.b1 = (const float*)h->b1.p;
     hp.a_out = a_buf;
     hp.lda = C;
-    const int kin = src.c0 + src.c1;
-    // Small maps (32-pixel tiles, 4-wave tails), block without adaptor, one source: no head launch - the tail computes
-    // `a` on its tile + halo itself (dcb_tail_kernel<..., HEADIN>)
-    constexpr bool kHeadInKernel = sizeof(T) == 2 && MT == 2 && (NTW <= 4 || NTW == 6);   // (6: the 8-wave tail of C=384)
-    // Small maps, widths 256 / 384 / 512 (fp16): the 32-pixel form of dcb_tail128_kernel (dcb_t128.hpp, geometry G32) - it wants `a`
-    // from a head launch or the previous block's tail, like the large-map form
-    bool t32 = false;
-    if constexpr (sizeof(T) == 2 && MT == 2 && (NTW == 4 || NTW == 6 || NTW == 8)) {
-        const bool fuse_ok = ch.next ? ch.next->w1_t128.p != nullptr : ch.conv ? ch.conv->w_t128.p != nullptr : true;
-        t32 = h->wt128.p != nullptr && t128_enabled() && t32_enabled() && fuse_ok;
-    }
-    // ... with the block's first conv computed inside on the tile + halo (dcb_tail128_kernel<C, G32, HEADIN>) where the block has no
-    // adaptor and its head was not computed by its predecessor: width 128 (the hyper path's blocks on 17x30 ... 68x120 maps, where
-    // dcb_tail_kernel<..., HEADIN> ran before) and width 256 (one launch of 21.5 us instead of 6.1 + 17.5 us at 68x120; at width
-    // 384 the head on the 60-pixel halo tile costs more than the head launch it saves: 41.9 against 8.0 + 32.1 us - not used)
-    bool t32h = false;
-    if constexpr (sizeof(T) == 2 && MT == 2 && (NTW == 2 || NTW == 4)) {
-        const bool fuse_ok = ch.next ? ch.next->w1_t128.p != nullptr : ch.conv ? ch.conv->w_t128.p != nullptr : true;
-        t32h = h->wt128.p != nullptr && h->w1_t128.p != nullptr && t128_enabled() && t32_enabled() && fuse_ok &&
-               (NTW == 2 ? t32_128_enabled() : t32h_enabled()) && !ch.head_done && !ch.separate_head && !h->adapt && src.c1 == 0;
-        if (t32h) t32 = false;
-    }
-    const bool head_in = kHeadInKernel && !ch.head_done && !ch.separate_head && !h->adapt && src.c1 == 0 && !t32 && !t32h;
-    if (ev) DCVC_HIP(hipEventRecord(ev[0], st));
-    // widths 256 / 320 / 384 on large maps, 256 / 384 / 512 in front of the 32-pixel tails: the head in the form of dcb_t128.hpp
-    // (sources of 64-channel multiples)
-    bool head128 = false;
-    {
-        constexpr bool kLarge = sizeof(T) == 2 && MT == 4 && (NTW == 4 || NTW == 5 || NTW == 6);
-        constexpr bool kSmall = sizeof(T) == 2 && MT == 2 && (NTW == 4 || NTW == 6 || NTW == 8);
-        if constexpr (kLarge || kSmall) {
-            using G = typename std::conditional<kLarge, t128::G128, t128::G32>::type;
-            head128 = t128_enabled() && h128_enabled() && (kLarge || t32) && !t32h && !ch.head_done && !head_in && h->w1_t128.p != nullptr &&
-                      (h->adapt ? (h->wa_t128.p != nullptr && src.c0 % 64 == 0 && src.c1 % 64 == 0 && kin == h->cin_p)
-                                : (src.c1 == 0 && src.c0 == NTW * 64));
-            if (head128) {
-                hp.wa128 = h->wa_t128.p;
-                hp.w1128 = h->w1_t128.p;
-                const int g128 = ((H + G::TH - 1) / G::TH) * ((W + G::TW - 1) / G::TW);
-                const size_t lds = t128::HeadCfg<NTW * 64, G>::LDS;
-                constexpr int NTHR_ = t128::Geo<G>::NTHR;
-                int rc;
-                if (h->adapt) {
-                    rc = set_lds(t128::dcb_head128_kernel<NTW * 64, true, G>, lds);
-                    if (rc) return rc;
-                    hipLaunchKernelGGL((t128::dcb_head128_kernel<NTW * 64, true, G>), dim3(g128), dim3(NTHR_), lds, st, hp);
-                } else {
-                    rc = set_lds(t128::dcb_head128_kernel<NTW * 64, false, G>, lds);
-                    if (rc) return rc;
-                    hipLaunchKernelGGL((t128::dcb_head128_kernel<NTW * 64, false, G>), dim3(g128), dim3(NTHR_), lds, st, hp);
-                }
-            }
-        }
-    }
-    if (ch.head_done || head_in || head128 || t32h) {
-        // `a` was written by the previous block's tail / is computed by this block's tail / by the 128-pixel head
-    } else if (h->adapt) {
-        // two sources: one at a time through LDS (half the staging buffer: a 64-pixel tile of 256 + 256 channels then
-        // leaves room for two workgroups per CU, i.e. half the weight fragments per pixel of the 32-pixel form)
-        hp.split = src.c1 > 0;
-        const int kstage = hp.split ? std::max(src.c0, src.c1) : kin;
-        const size_t lds = head_lds<T, MT>(kstage, C, true);
-        if (MT == 4 && lds > 80 * 1024) {
-            // a 64-pixel tile of a wide two-source input leaves room for one workgroup per CU (two rounds over
-            // a 136x240 map); 32-pixel tiles fit three per CU (97 -> 88 us for head + tail at 256+256 -> 256).
-            // Head and tail tile shapes are independent.
-            const int grid2 = ((H + Tile<2>::TH - 1) / Tile<2>::TH) * ((W + Tile<2>::TW - 1) / Tile<2>::TW);
-            const size_t lds2 = head_lds<T, 2>(kstage, C, true);
-            int rc = set_lds(dcb_head_kernel<T, 2, NTW, true>, lds2);
-            if (rc) return rc;
-            hipLaunchKernelGGL((dcb_head_kernel<T, 2, NTW, true>), dim3(grid2), dim3(NTHREADS), lds2, st, hp);
-        } else {
-            int rc = set_lds(dcb_head_kernel<T, MT, NTW, true>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL((dcb_head_kernel<T, MT, NTW, true>), dim3(grid), dim3(NTHREADS), lds, st, hp);
-        }
-    } else {
-        const size_t lds = head_lds<T, MT>(kin, C, false);
-        int rc = set_lds(dcb_head_kernel<T, MT, NTW, false>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((dcb_head_kernel<T, MT, NTW, false>), dim3(grid), dim3(NTHREADS), lds, st, hp);
-    }
-    DCVC_LAUNCH_CHECK();
-    if (ev) DCVC_HIP(hipEventRecord(ev[1], st));
+    hp.split = src.c1 > 0;
+    hp.wa128 = h->wa_t128.p;
+    hp.w1128 = h->w1_t128.p;
     TailParams tp{};
     tp.a = a_buf;
     tp.lda = C;
@@ -1378,13 +1409,13 @@ int launch_dcb(const dcvc_dcb* h, const SrcPair& src, int H, int W, const float*
     tp.q = quant;
     tp.out = out;
     tp.ldo = ldo;
-    if (head_in || t32h) {
-        tp.hx = src.x0;
-        tp.ldhx = src.ld0;
-        tp.hw1 = h->w1.p;
-        tp.hb1 = (const float*)h->b1.p;
-        tp.hwt = h->w1_t128.p;
-    }
+    tp.hx = src.x0;
+    tp.ldhx = src.ld0;
+    tp.hw1 = h->w1.p;
+    tp.hb1 = (const float*)h->b1.p;
+    tp.hwt = h->w1_t128.p;
+    tp.wt = h->wt128.p;
+    tp.nwt = pl.nwt;
     if (ch.next) {
         tp.nw1 = ch.next->w1.p;
         tp.nb1 = (const float*)ch.next->b1.p;
@@ -1399,207 +1430,124 @@ int launch_dcb(const dcvc_dcb* h, const SrcPair& src, int H, int W, const float*
         tp.nq = ch.conv_q;
         tp.n_log = ch.conv->cout;
     }
-#ifdef DCVC_DIAG      // developer build only (make diag): phase ablation / in-kernel stamps
-    {
-        static const int abl = getenv("DCVC_ABLATE") ? atoi(getenv("DCVC_ABLATE")) : 0;
-        tp.ablate = abl;
-    }
-    static const bool want_stamps = getenv("DCVC_STAMPS") != nullptr;
-    unsigned long long* d_stamps = nullptr;
-    if (want_stamps) {
-        DCVC_HIP(hipMalloc(&d_stamps, (size_t)grid * 8 * sizeof(unsigned long long)));
-        tp.stamps = d_stamps;
-    }
-#endif
-    if constexpr (sizeof(T) == 2 && MT == 2 && (NTW == 2 || NTW == 4)) {
-        if (t32h) {
-            tp.wt = h->wt128.p;
-            tp.nwt = ch.next ? ch.next->w1_t128.p : ch.conv ? ch.conv->w_t128.p : nullptr;
-            int rc = launch_tail128<NTW * 64, t128::G32, true>(tp, H, W, st);
-            if (rc) return rc;
-            DCVC_LAUNCH_CHECK();
-            if (ev) DCVC_HIP(hipEventRecord(ev[2], st));
-            return 0;
-        }
-    }
-    if constexpr (sizeof(T) == 2 && MT == 2 && (NTW == 4 || NTW == 6 || NTW == 8)) {
-        if (t32 && t32s_enabled() && h->w3s.p != nullptr && h->w4s.p != nullptr && P < 12000) {   // (the scratch holds o and v below 12 000 pixels)
-            // staged (dcb_t128.hpp): A -> o, B -> v, C -> out; a fused successor becomes a launch of its own on the block's
-            // output (the head of the 32-pixel form, or the 1x1 conv: the same values as the fused GEMM, see gemm_c)
-            T* o_buf = slots + 3 * P * C;
-            T* v_buf = o_buf + P * C;
-            T* r_buf = out != nullptr ? reinterpret_cast<T*>(out) : a_buf;     // (a_buf: this block's `a`, dead after stage A)
-            const long ldr = out != nullptr ? (long)ldo : C;
-            TailParams ta = tp;
-            ta.wt = h->wt128.p;
-            ta.out = nullptr;
-            ta.nw1 = nullptr;
-            ta.nwt = nullptr;
-            ta.na_out = nullptr;
-            ta.ostage = o_buf;
-            int rc = launch_tail128<NTW * 64, t128::G32, false, true>(ta, H, W, st);
-            if (rc) return rc;
-            DCVC_LAUNCH_CHECK();
-            t128::FfnParams fp{};
-            fp.o = o_buf;
-            fp.v = v_buf;
-            fp.vout = v_buf;
-            fp.P = (int)P;
-            fp.w3 = h->w3s.p;
-            fp.b3 = tp.b3;
-            fp.w4 = h->w4s.p;
-            fp.b4 = tp.b4;
-            fp.ident = tp.ident;
-            fp.ldi = tp.ldi;
-            fp.shortcut = tp.shortcut;
-            fp.q = tp.q;
-            fp.c_log = tp.c_log;
-            fp.out = r_buf;
-            fp.ldo = ldr;
-            rc = launch_ffn_staged<NTW * 64>(fp, st);
-            if (rc) return rc;
-            if (ch.next) {
-                HeadParams nh{};
-                nh.src = SrcPair{r_buf, ldr, C, nullptr, 0, 0};
-                nh.H = H;
-                nh.W = W;
-                nh.C = C;
-                nh.w1128 = ch.next->w1_t128.p;
-                nh.b1 = (const float*)ch.next->b1.p;
-                nh.a_out = a_next;
-                nh.lda = C;
-                const int g32 = ((H + t128::G32::TH - 1) / t128::G32::TH) * ((W + t128::G32::TW - 1) / t128::G32::TW);
-                const size_t lds = t128::HeadCfg<NTW * 64, t128::G32>::LDS;
-                rc = set_lds(t128::dcb_head128_kernel<NTW * 64, false, t128::G32>, lds);
-                if (rc) return rc;
-                hipLaunchKernelGGL((t128::dcb_head128_kernel<NTW * 64, false, t128::G32>), dim3(g32), dim3(t128::Geo<t128::G32>::NTHR), lds, st, nh);
-                DCVC_LAUNCH_CHECK();
-            } else if (ch.conv) {
-                ConvParams cp{};
-                cp.src = SrcPair{r_buf, ldr, C, nullptr, 0, 0};
-                cp.H = cp.Ho = H;
-                cp.W = cp.Wo = W;
-                cp.KH = cp.KW = cp.stride = 1;
-                cp.pad = 0;
-                cp.N = ch.conv->n_p;
-                cp.n_log = ch.conv->cout;
-                cp.cs_p = ch.conv->cs_p;
-                cp.w = ch.conv->w.p;
-                cp.b = (const float*)ch.conv->b.p;
-                cp.q = ch.conv_q;
-                cp.epi = ch.conv->epi;
-                cp.out = ch.conv_out;
-                cp.ldo = ch.ldco;
-                rc = run_conv(ch.conv, cp, st);
-                if (rc) return rc;
-            }
-            if (ev) DCVC_HIP(hipEventRecord(ev[2], st));
-            return 0;
-        }
-        if (t32) {
-            tp.wt = h->wt128.p;
-            tp.nwt = ch.next ? ch.next->w1_t128.p : ch.conv ? ch.conv->w_t128.p : nullptr;
-            int rc = launch_tail128<NTW * 64, t128::G32>(tp, H, W, st);
-            if (rc) return rc;
-            DCVC_LAUNCH_CHECK();
-            if (ev) DCVC_HIP(hipEventRecord(ev[2], st));
-            return 0;
-        }
-    }
-    if constexpr (sizeof(T) == 2 && MT == 4 && (NTW == 4 || NTW == 5 || NTW == 6)) {
-        // large maps, widths 256 / 384: 128-pixel tiles, one 4-wave workgroup per CU, gate pipelined into the MFMA stream
-        const void* nwt = ch.next ? ch.next->w1_t128.p : ch.conv ? ch.conv->w_t128.p : nullptr;
-        if (h->wt128.p != nullptr && t128_enabled() && !head_in && (tp.nw1 == nullptr || nwt != nullptr)) {
-            tp.wt = h->wt128.p;
-            tp.nwt = nwt;
-            int rc = launch_tail128<NTW * 64>(tp, H, W, st);
-            if (rc) return rc;
-            DCVC_LAUNCH_CHECK();
-            if (ev) DCVC_HIP(hipEventRecord(ev[2], st));
-            return 0;
-        }
-    }
-    {
-        // Widths of 384 and up (6+ channel tiles per wave) fit one workgroup per CU only.  Eight waves
-        // (two per SIMD, half the channel tiles each, <= 256 VGPRs) give every SIMD a second wave of the
-        // same tile to switch to: 144 -> 117 us at C=384, 136x240.  At C <= 256 two independent 4-wave
-        // workgroups per CU do that job better (8 waves there measured 116 us vs 63 us; 128-pixel tiles on 8 waves,
-        // MT = 8 x NTW = 2, spill at 256 VGPRs and measured 66 us against 59 us for the same build).
-        int rc;
-        if constexpr (NTW == 6 && kHeadInKernel)
-            rc = head_in ? launch_tail<T, MT, 3, 8, false, true>(tp, grid, C, st) : launch_tail<T, MT, 3, 8>(tp, grid, C, st);
-        else if constexpr (NTW >= 6 && NTW % 2 == 0 && sizeof(T) == 2)
-            rc = launch_tail<T, MT, NTW / 2, 8>(tp, grid, C, st);
-        else if constexpr (NTW == 5 && sizeof(T) == 2)
-            rc = launch_tail<T, MT, 3, 8, true>(tp, grid, C, st);   // 20 tiles on 8 waves: 4 waves x 3 + 4 waves x 2
-        else if constexpr (kHeadInKernel && NTW <= 4) {
-            rc = head_in ? launch_tail<T, MT, NTW, 4, false, true>(tp, grid, C, st) : launch_tail<T, MT, NTW, 4>(tp, grid, C, st);
-        } else
-            rc = launch_tail<T, MT, NTW, 4>(tp, grid, C, st);
-        if (rc) return rc;
-    }
-    DCVC_LAUNCH_CHECK();
-    if (ev) DCVC_HIP(hipEventRecord(ev[2], st));
 #ifdef DCVC_DIAG
-    if (want_stamps) {   // diagnostic only: median cycles per phase over the workgroups
-        DCVC_HIP(hipStreamSynchronize(st));
-        std::vector<unsigned long long> hs((size_t)grid * 8);
-        DCVC_HIP(hipMemcpy(hs.data(), d_stamps, hs.size() * 8, hipMemcpyDeviceToHost));
-        (void)hipFree(d_stamps);
-        static int printed = 0;
-        if (printed++ % 16 == 15) {
+    tp.ablate = switches().ablate;
+#endif
+
+    if (ev) DCVC_HIP(hipEventRecord(ev[0], st));
+    int rc = 0;
+    if (pl.head == DcbPlan::Head::head128) {
+        if constexpr (has_head128(f16, MT, NTW)) {
+            const dim3 g128(((H + G::TH - 1) / G::TH) * ((W + G::TW - 1) / G::TW));
+            const size_t lds = t128::HeadCfg<NTW * 64, G>::LDS;
+            rc = pl.head_adapt ? launch_kernel(t128::dcb_head128_kernel<NTW * 64, true, G>, g128, t128::Geo<G>::NTHR, lds, st, hp)
+                               : launch_kernel(t128::dcb_head128_kernel<NTW * 64, false, G>, g128, t128::Geo<G>::NTHR, lds, st, hp);
+        } else {
+            rc = not_built("dcb_head128_kernel", pl);
+        }
+    } else if (pl.head == DcbPlan::Head::head) {
+        const int kstage = pl.head_adapt && hp.split ? std::max(src.c0, src.c1) : src.c0 + src.c1;
+        if (!pl.head_adapt) {
+            rc = launch_kernel(dcb_head_kernel<T, MT, NTW, false>, dim3(grid), NTHREADS, head_lds<T, MT>(kstage, C, false), st, hp);
+        } else if (pl.head_t32) {
+            const int grid2 = ((H + Tile<2>::TH - 1) / Tile<2>::TH) * ((W + Tile<2>::TW - 1) / Tile<2>::TW);
+            rc = launch_kernel(dcb_head_kernel<T, 2, NTW, true>, dim3(grid2), NTHREADS, head_lds<T, 2>(kstage, C, true), st, hp);
+        } else {
+            rc = launch_kernel(dcb_head_kernel<T, MT, NTW, true>, dim3(grid), NTHREADS, head_lds<T, MT>(kstage, C, true), st, hp);
+        }
+    }
+    if (rc) return rc;
+    DCVC_LAUNCH_CHECK();
+    if (ev) DCVC_HIP(hipEventRecord(ev[1], st));
+
+    if (pl.tail == DcbPlan::Tail::tail128) {
+        if (pl.headin) {
+            if constexpr (has_tail128(f16, MT, NTW, true)) rc = launch_tail128<NTW * 64, G, true>(tp, H, W, st);
+            else rc = not_built("dcb_tail128_kernel<..., HEADIN>", pl);
+        } else {
+            if constexpr (has_tail128(f16, MT, NTW, false)) rc = launch_tail128<NTW * 64, G>(tp, H, W, st);
+            else rc = not_built("dcb_tail128_kernel", pl);
+        }
+        if (rc) return rc;
+        DCVC_LAUNCH_CHECK();
+    } else {
+        constexpr TailForm F = tail_form(f16, NTW);
+#ifdef DCVC_DIAG      // developer build only (make diag): in-kernel phase stamps, median over the workgroups
+        if (switches().stamps) DCVC_HIP(hipMalloc(&tp.stamps, (size_t)grid * 8 * sizeof(unsigned long long)));
+#endif
+        if (pl.headin) {
+            if constexpr (has_tail_headin(f16, MT, NTW)) rc = launch_tail<T, MT, F.ntw, F.nw, F.rag, true>(tp, grid, C, st);
+            else rc = not_built("dcb_tail_kernel<..., HEADIN>", pl);
+        } else {
+            rc = launch_tail<T, MT, F.ntw, F.nw, F.rag>(tp, grid, C, st);
+        }
+        if (rc) return rc;
+        DCVC_LAUNCH_CHECK();
+#ifdef DCVC_DIAG
+        if (tp.stamps) {
             const char* names[8] = {"dw", "gemm2", "o_pass", "gemm3", "ffn_epi", "gemm4", "final", "total"};
-            fprintf(stderr, "[stamps C=%d MT=%d grid=%d]", C, MT, grid);
-            for (int k = 0; k < 8; ++k) {
-                std::vector<unsigned long long> v(grid);
-                for (int b = 0; b < grid; ++b) v[b] = hs[(size_t)b * 8 + k];
-                std::sort(v.begin(), v.end());
-                fprintf(stderr, " %s=%llu", names[k], v[grid / 2]);
-            }
-            fprintf(stderr, "\n");
-            if (tp.ablate & 16) {
+            char tag[64];
+            snprintf(tag, sizeof tag, "stamps C=%d MT=%d grid=%d", C, MT, grid);
+            static int calls = 0;
+            std::vector<unsigned long long> hs;
+            bool printed = false;
+            rc = stamp_medians(tp.stamps, grid, 8, names, tag, calls, st, hs, printed);
+            if (rc) return rc;
+            if (printed) fprintf(stderr, "\n");
+            if (printed && (tp.ablate & 16)) {   // the kernel stored absolute start / end stamps instead of two phase counters
                 unsigned long long t0 = ~0ull, t1 = 0;
                 for (int b = 0; b < grid; ++b) {
                     t0 = std::min(t0, hs[(size_t)b * 8]);
                     t1 = std::max(t1, hs[(size_t)b * 8 + 1]);
                 }
-                std::vector<unsigned long long> st(grid), en(grid), du(grid);
+                std::vector<unsigned long long> s(grid), e(grid), du(grid);
                 for (int b = 0; b < grid; ++b) {
-                    st[b] = hs[(size_t)b * 8] - t0;
-                    en[b] = hs[(size_t)b * 8 + 1] - t0;
+                    s[b] = hs[(size_t)b * 8] - t0;
+                    e[b] = hs[(size_t)b * 8 + 1] - t0;
                     du[b] = hs[(size_t)b * 8 + 7];
                 }
-                std::sort(st.begin(), st.end());
-                std::sort(en.begin(), en.end());
+                std::sort(s.begin(), s.end());
+                std::sort(e.begin(), e.end());
                 std::sort(du.begin(), du.end());
                 fprintf(stderr, "[span %llu] start min/med/p90/max %llu %llu %llu %llu | end med/p90/max %llu %llu %llu | dur min/med/p90/max %llu %llu %llu %llu\n",
-                        t1 - t0, st[0], st[grid / 2], st[grid * 9 / 10], st[grid - 1], en[grid / 2], en[grid * 9 / 10],
-                        en[grid - 1], du[0], du[grid / 2], du[grid * 9 / 10], du[grid - 1]);
+                        t1 - t0, s[0], s[grid / 2], s[grid * 9 / 10], s[grid - 1], e[grid / 2], e[grid * 9 / 10],
+                        e[grid - 1], du[0], du[grid / 2], du[grid * 9 / 10], du[grid - 1]);
             }
         }
-    }
 #endif
+    }
+    if (ev) DCVC_HIP(hipEventRecord(ev[2], st));
     return 0;
 }
 
 template <typename T, int MT>
-int dispatch_dcb(const dcvc_dcb* h, const SrcPair& src, int H, int W, const float* quant, void* out, int64_t ldo,
-                 void* scratch, hipStream_t st, hipEvent_t* ev = nullptr, ChainArgs ch = ChainArgs())
+int dispatch_dcb(const DcbPlan& pl, const dcvc_dcb* h, const SrcPair& src, int H, int W, const float* quant, void* out,
+                 int64_t ldo, void* scratch, hipStream_t st, hipEvent_t* ev, const ChainArgs& ch)
 {
-    switch (h->c_p / 64) {
-    case 1: return launch_dcb<T, MT, 1>(h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
-    case 2: return launch_dcb<T, MT, 2>(h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
-    case 3: return launch_dcb<T, MT, 3>(h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
-    case 4: return launch_dcb<T, MT, 4>(h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
-    case 5: return launch_dcb<T, MT, 5>(h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
-    case 6: return launch_dcb<T, MT, 6>(h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
-    case 8: return launch_dcb<T, MT, 8>(h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
+    switch (pl.ntw) {
+    case 1: return launch_dcb<T, MT, 1>(pl, h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
+    case 2: return launch_dcb<T, MT, 2>(pl, h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
+    case 3: return launch_dcb<T, MT, 3>(pl, h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
+    case 4: return launch_dcb<T, MT, 4>(pl, h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
+    case 5: return launch_dcb<T, MT, 5>(pl, h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
+    case 6: return launch_dcb<T, MT, 6>(pl, h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
+    case 8: return launch_dcb<T, MT, 8>(pl, h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
     default: dcvc::set_error("DepthConvBlock width %d not instantiated", h->c_p); return dcvc::E_ARG;
     }
 }
 
+static int run_dcb(const dcvc_dcb* h, const SrcPair& src, int H, int W, const float* quant, void* out, int64_t ldo,
+                   void* scratch, hipStream_t st, hipEvent_t* ev, ChainArgs ch = ChainArgs())
+{
+    const DcbPlan pl = plan_dcb(h, src, H, W, ch);
+    if (h->dtype != DCVC_F16) return dispatch_dcb<float, 2>(pl, h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
+    if (pl.mt == 2) return dispatch_dcb<half_t, 2>(pl, h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
+    return dispatch_dcb<half_t, 4>(pl, h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
+}
+
+// ---- dense convolutions
 template <typename T, int MT, int NTW>
-int launch_conv(const dcvc_conv* h, const ConvParams& cp, hipStream_t st)
+int launch_conv(const ConvParams& cp, hipStream_t st)
 {
     const int grid = ((cp.Ho + Tile<MT>::TH - 1) / Tile<MT>::TH) * ((cp.Wo + Tile<MT>::TW - 1) / Tile<MT>::TW);
     const size_t row = (size_t)(cp.src.c0 + cp.src.c1 + Traits<T>::kPad) * sizeof(T);
@@ -1616,72 +1564,60 @@ int launch_conv(const dcvc_conv* h, const ConvParams& cp, hipStream_t st)
     const int passes = (cp.N / 16 + NWAVE * NTW - 1) / (NWAVE * NTW);
     p.split_n = passes > 1 && grid < 400;
     const dim3 g(grid, p.split_n ? passes : 1);
-    if (p.halo) {
-        int rc = set_lds(conv_kernel<T, MT, NTW, true>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((conv_kernel<T, MT, NTW, true>), g, dim3(NTHREADS), lds, st, p);
-    } else {
-        int rc = set_lds(conv_kernel<T, MT, NTW, false>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((conv_kernel<T, MT, NTW, false>), g, dim3(NTHREADS), lds, st, p);
-    }
+    int rc = p.halo ? launch_kernel(conv_kernel<T, MT, NTW, true>, g, NTHREADS, lds, st, p)
+                    : launch_kernel(conv_kernel<T, MT, NTW, false>, g, NTHREADS, lds, st, p);
+    if (rc) return rc;
     DCVC_LAUNCH_CHECK();
-    (void)h;
     return 0;
 }
 
 template <typename T, int MT>
-int dispatch_conv(const dcvc_conv* h, const ConvParams& cp, hipStream_t st)
+int dispatch_conv(int ntw, const ConvParams& cp, hipStream_t st)
 {
-    const int nt = cp.N / 16;
-    if (nt <= 8) return launch_conv<T, MT, 2>(h, cp, st);
-    if (nt <= 12) return launch_conv<T, MT, 3>(h, cp, st);
-    return launch_conv<T, MT, 4>(h, cp, st);
+    if (ntw == 2) return launch_conv<T, MT, 2>(cp, st);
+    if (ntw == 3) return launch_conv<T, MT, 3>(cp, st);
+    return launch_conv<T, MT, 4>(cp, st);
 }
 
+// What one convolution launch runs
+struct ConvPlan {
+    enum class Kind { s2_t32, c3_t128, conv } kind = Kind::conv;
+    int ntw = 2;   // s2_t32 / c3_t128: 128-channel slices per workgroup (1 or 2); conv: channel tiles per wave (2, 3 or 4)
+    int mt = 2;    // conv: conv_kernel's pixel tile (16 mt pixels)
+};
 
-// Pixel-tile selection (f16): 16*MT pixels per workgroup.  Small feature maps take 32-pixel tiles so
-// that the grid still covers the 256 CUs (measured: 68x120 maps 15-25 % faster); 128-pixel tiles
-// (MT = 8, one workgroup per CU) were measured slower than 64-pixel tiles at two workgroups per CU
-// (80 vs 63 us at C = 256, 136x240) and are not instantiated.  (Developer build: DCVC_MT overrides.)
-static int pick_mt_f16(int H, int W, int c_p)
+static ConvPlan plan_conv(const dcvc_conv* h, const ConvParams& cp)
 {
+    const Switches& sw = switches();
+    ConvPlan pl;
+    if (h->dtype == DCVC_F16 && h->w_s2.p != nullptr && sw.c128 && cp.src.c1 == 0 && (long)cp.Ho * cp.Wo < 12000) {
+        // stride-2 convs with 128 / 256 output channels: conv_s2_t32_kernel (a workgroup streams all the weights for 32
+        // pixels: small maps)
+        pl.kind = ConvPlan::Kind::s2_t32;
+        pl.ntw = cp.N / 128;
+    } else if (h->dtype == DCVC_F16 && h->w_c128[0].p != nullptr && sw.c128 && cp.src.c1 == 0 && cp.in_q == nullptr) {
+        // 3x3 s1 convs: conv3x3_t128_kernel, 256-channel slices at one workgroup per CU if that grid runs in one round,
+        // else 128-channel slices at two per CU
+        const int tiles = ((cp.H + t128::TH - 1) / t128::TH) * ((cp.W + t128::TW - 1) / t128::TW);
+        pl.kind = ConvPlan::Kind::c3_t128;
+        pl.ntw = tiles * (cp.N / 256) <= 256 ? 2 : 1;
+    } else {
+        const int nt = cp.N / 16;
+        pl.ntw = nt <= 8 ? 2 : nt <= 12 ? 3 : 4;
+        pl.mt = h->dtype != DCVC_F16 ? 2 : (long)cp.Ho * cp.Wo >= 12000 ? 4 : 2;
 #ifdef DCVC_DIAG
-    static const int forced = getenv("DCVC_MT") ? atoi(getenv("DCVC_MT")) : 0;
-    if (forced == 2 || forced == 4) return forced;
+        if (h->dtype == DCVC_F16 && (sw.conv_mt == 2 || sw.conv_mt == 4 || sw.conv_mt == 8)) pl.mt = sw.conv_mt;
 #endif
-    const long P = (long)H * W;
-    (void)c_p;
-    return P >= 12000 ? 4 : 2;
-}
-
-template <int MT>
-int dispatch_dcb_f16(const dcvc_dcb* h, const SrcPair& src, int H, int W, const float* quant, void* out, int64_t ldo,
-                     void* scratch, hipStream_t st, hipEvent_t* ev, ChainArgs ch)
-{
-    return dispatch_dcb<half_t, MT>(h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
-}
-
-static int run_dcb(const dcvc_dcb* h, const SrcPair& src, int H, int W, const float* quant, void* out, int64_t ldo,
-                   void* scratch, hipStream_t st, hipEvent_t* ev, ChainArgs ch = ChainArgs())
-{
-    if (h->dtype != DCVC_F16) return dispatch_dcb<float, 2>(h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
-    switch (pick_mt_f16(H, W, h->c_p)) {
-    case 2: return dispatch_dcb_f16<2>(h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
-    default: return dispatch_dcb_f16<4>(h, src, H, W, quant, out, ldo, scratch, st, ev, ch);
     }
-}
-
-static bool c128_enabled()   // DCVC_C128=0: 3x3 convs by conv_kernel (A/B measurements, bit-identity checks)
-{
-    static const bool on = !(getenv("DCVC_C128") && atoi(getenv("DCVC_C128")) == 0);
-    return on;
+    return pl;
 }
 
 static int run_conv(const dcvc_conv* h, const ConvParams& cp, hipStream_t st)
 {
-    if (h->dtype != DCVC_F16) return dispatch_conv<float, 2>(h, cp, st);
-    if (h->w_s2.p != nullptr && c128_enabled() && cp.src.c1 == 0 && (long)cp.Ho * cp.Wo < 12000) {     // (a workgroup streams all the weights for 32 pixels: small maps)
+    const ConvPlan pl = plan_conv(h, cp);
+    int rc = 0;
+    switch (pl.kind) {
+    case ConvPlan::Kind::s2_t32: {
         t128::ConvS2Params p{};
         p.x = cp.src.x0;
         p.ldx = cp.src.ld0;
@@ -1698,54 +1634,41 @@ static int run_conv(const dcvc_conv* h, const ConvParams& cp, hipStream_t st)
         p.in_qn = cp.in_qn;
         p.out = cp.out;
         p.ldo = cp.ldo;
-        const int ntw = cp.N / 128;
-        const size_t lds = t128::conv_s2_lds(p.kin, p.k, ntw);
+        const size_t lds = t128::conv_s2_lds(p.kin, p.k, pl.ntw);
         const dim3 g(((cp.Ho + t128::S2_TH - 1) / t128::S2_TH) * ((cp.Wo + t128::S2_TW - 1) / t128::S2_TW));
-        int rc = ntw == 2 ? set_lds(t128::conv_s2_t32_kernel<2>, lds) : set_lds(t128::conv_s2_t32_kernel<1>, lds);
-        if (rc) return rc;
-        if (ntw == 2)
-            hipLaunchKernelGGL(t128::conv_s2_t32_kernel<2>, g, dim3(256), lds, st, p);
-        else
-            hipLaunchKernelGGL(t128::conv_s2_t32_kernel<1>, g, dim3(256), lds, st, p);
-        DCVC_LAUNCH_CHECK();
-        return 0;
+        rc = pl.ntw == 2 ? launch_kernel(t128::conv_s2_t32_kernel<2>, g, 256, lds, st, p)
+                         : launch_kernel(t128::conv_s2_t32_kernel<1>, g, 256, lds, st, p);
+        break;
     }
-    if (h->w_c128[0].p != nullptr && c128_enabled() && cp.src.c1 == 0 && cp.in_q == nullptr) {
-        const int tiles = ((cp.H + t128::TH - 1) / t128::TH) * ((cp.W + t128::TW - 1) / t128::TW);
-        // 256-channel slices at one workgroup per CU if that grid runs in one round, else 128-channel slices at two per CU
-        const int ntw = tiles * (cp.N / 256) <= 256 ? 2 : 1;
+    case ConvPlan::Kind::c3_t128: {
         t128::Conv128Params p{};
         p.x = cp.src.x0;
         p.ldx = cp.src.ld0;
         p.H = cp.H;
         p.W = cp.W;
         p.kin = cp.src.c0;
-        p.wt = h->w_c128[ntw - 1].p;
+        p.wt = h->w_c128[pl.ntw - 1].p;
         p.b = cp.b;
         p.out = cp.out;
         p.ldo = cp.ldo;
         p.shuffle = cp.epi == DCVC_EPI_SHUFFLE2;
         p.cs_p = cp.cs_p;
-        const size_t lds = t128::conv128_lds(p.kin, ntw);
-        const dim3 g(tiles, cp.N / (128 * ntw));
-        int rc = ntw == 2 ? set_lds(t128::conv3x3_t128_kernel<2>, lds) : set_lds(t128::conv3x3_t128_kernel<1>, lds);
-        if (rc) return rc;
-        if (ntw == 2)
-            hipLaunchKernelGGL(t128::conv3x3_t128_kernel<2>, g, dim3(t128::NTHR), lds, st, p);
-        else
-            hipLaunchKernelGGL(t128::conv3x3_t128_kernel<1>, g, dim3(t128::NTHR), lds, st, p);
-        DCVC_LAUNCH_CHECK();
-        return 0;
+        const size_t lds = t128::conv128_lds(p.kin, pl.ntw);
+        const dim3 g(((cp.H + t128::TH - 1) / t128::TH) * ((cp.W + t128::TW - 1) / t128::TW), cp.N / (128 * pl.ntw));
+        rc = pl.ntw == 2 ? launch_kernel(t128::conv3x3_t128_kernel<2>, g, t128::NTHR, lds, st, p)
+                         : launch_kernel(t128::conv3x3_t128_kernel<1>, g, t128::NTHR, lds, st, p);
+        break;
     }
-    const long P = (long)cp.Ho * cp.Wo;
+    case ConvPlan::Kind::conv:
+        if (h->dtype != DCVC_F16) return dispatch_conv<float, 2>(pl.ntw, cp, st);
 #ifdef DCVC_DIAG
-    static const int forced = getenv("DCVC_CONV_MT") ? atoi(getenv("DCVC_CONV_MT")) : 0;
-    if (forced == 2) return dispatch_conv<half_t, 2>(h, cp, st);
-    if (forced == 4) return dispatch_conv<half_t, 4>(h, cp, st);
-    if (forced == 8) return dispatch_conv<half_t, 8>(h, cp, st);
+        if (pl.mt == 8) return dispatch_conv<half_t, 8>(pl.ntw, cp, st);
 #endif
-    if (P >= 12000) return dispatch_conv<half_t, 4>(h, cp, st);
-    return dispatch_conv<half_t, 2>(h, cp, st);
+        return pl.mt == 4 ? dispatch_conv<half_t, 4>(pl.ntw, cp, st) : dispatch_conv<half_t, 2>(pl.ntw, cp, st);
+    }
+    if (rc) return rc;
+    DCVC_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace
@@ -1798,16 +1721,10 @@ int dcvc_dcb_create(int dtype, int cin, int c, int shortcut, const float* adapto
         auto W4 = [&](int n, int k) { return (n < C && k < 2 * C) ? w4[(size_t)n * 2 * C + k] / ka : 0.f; };
         if (h->adapt && Kp % 64 == 0) {
             auto WA = [&](int n, int k) { return (n < C && k < cin) ? adaptor_w[(size_t)n * cin + k] : 0.f; };
-            rc |= Cp == 128 ? pack_t128_rect<128>(h->wa_t128, Kp, WA) : Cp == 256 ? pack_t128_rect<256>(h->wa_t128, Kp, WA) : Cp == 320 ? pack_t128_rect<320>(h->wa_t128, Kp, WA)
-                            : Cp == 384 ? pack_t128_rect<384>(h->wa_t128, Kp, WA) : pack_t128_rect<512>(h->wa_t128, Kp, WA);
+            rc |= visit_t128_width(Cp, [&](auto w) { return pack_t128_rect<decltype(w)::value>(h->wa_t128, Kp, WA); });
         }
         rc |= pack_t128_square_any(Cp, h->w1_t128, [&](int n, int k) { return (n < C && k < C) ? ka * w1[(size_t)n * C + k] : 0.f; });
-        rc |= Cp == 128 ? pack_t128<128>(h->wt128, W2, W3, W4) : Cp == 256 ? pack_t128<256>(h->wt128, W2, W3, W4) : Cp == 320 ? pack_t128<320>(h->wt128, W2, W3, W4)
-                        : Cp == 384 ? pack_t128<384>(h->wt128, W2, W3, W4) : pack_t128<512>(h->wt128, W2, W3, W4);
-        if (Cp == 256 || Cp == 384 || Cp == 512) {   // the staged small-map tail
-            rc |= Cp == 256 ? pack_t128_w3<256>(h->w3s, W3) : Cp == 384 ? pack_t128_w3<384>(h->w3s, W3) : pack_t128_w3<512>(h->w3s, W3);
-            rc |= pack_t128_conv(h->w4s, 1, 1, t128::PADF, Cp, 2 * Cp, [&](int n, int, int k) { return W4(n, k); });
-        }
+        rc |= visit_t128_width(Cp, [&](auto w) { return pack_t128<decltype(w)::value>(h->wt128, W2, W3, W4); });
     }
     if (rc) return rc < 0 ? rc : dcvc::E_MEM;
     *out = h.release();
@@ -1819,9 +1736,7 @@ void dcvc_dcb_destroy(dcvc_dcb* h) { delete h; }
 size_t dcvc_dcb_scratch_bytes(const dcvc_dcb* h, int H, int W)
 {
     if (!h) return 0;
-    // two `a` slots (chained blocks alternate) + x'; small fp16 maps also o and v (2C wide) of the staged tail
-    const bool staged = h->w3s.p != nullptr && (long)H * W < 12000;
-    return (size_t)H * W * h->c_p * dcvc::elem_size(h->dtype) * (staged ? 6 : 3);
+    return (size_t)H * W * h->c_p * dcvc::elem_size(h->dtype) * 3;   // two `a` slots (chained blocks alternate) + x'
 }
 
 int dcvc_dcb_forward(const dcvc_dcb* h, const void* x0, int64_t ld0, int c0, const void* x1, int64_t ld1, int c1,

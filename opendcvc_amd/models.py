@@ -154,7 +154,6 @@ class _CompactStep:
 
 # DCVC_NO_FORK=1: no second stream inside a run (the temporal prior encoder then runs behind the hyper decoder)
 _FORK = os.environ.get("DCVC_NO_FORK") != "1"
-_PICTURE_RING = os.environ.get("DCVC_PICTURE_RING") == "1"
 
 
 class GraphCache:
@@ -362,14 +361,7 @@ class CompressionModel(tnn.Module):
         """PixelShuffle(8) + clamp of the last conv's output into a FRESH tensor, launched outside the captured run (whose own
         output buffer is overwritten by the next frame).  The reference returns a fresh tensor per frame and callers keep
         them (a sequence's pictures for the PSNR, the DPB): no ring of picture buffers - the kernel writes the new tensor
-        directly, so there is no copy either, and the allocator hands the block back once the caller drops the picture.
-        (DCVC_PICTURE_RING=1, a developer switch for A/B timing only: round 3's two alternating buffers - a picture is
-        then overwritten by the second following frame.)"""
-        if _PICTURE_RING:
-            H, W, _, _ = L._geom(head)
-            self._pic_parity = getattr(self, "_pic_parity", 0) ^ 1
-            buf = self._buffer(f"picture_{self._pic_parity}", (1, 3, H * 8, W * 8), head.dtype, head.device)
-            return self._shuffle8_clamp(head, out=buf)
+        directly, so there is no copy either, and the allocator hands the block back once the caller drops the picture."""
         return self._shuffle8_clamp(head)
 
     def _thres(self):
@@ -568,9 +560,9 @@ class DMC(CompressionModel):
         n["spatial"] = [D(sd, "y_spatial_prior.conv.0", dt), D(sd, "y_spatial_prior.conv.1", dt)]
         # y_spatial_prior's last conv is 384 -> 256: as a SQUARE 384 -> 384 conv (128 all-zero output rows, never read) it qualifies
         # for the fused launch inside the preceding block's tail (Conv2d.fusable_after) - the same dot products for the real
-        # channels, one 12 - 14 us launch less per coded frame on the decoder's critical path (DCVC_SQUARE_SPATIAL_OUT=0: as is)
+        # channels, one 12 - 14 us launch less per coded frame on the decoder's critical path
         w, b = sd["y_spatial_prior.conv.2.weight"], sd["y_spatial_prior.conv.2.bias"]
-        if os.environ.get("DCVC_SQUARE_SPATIAL_OUT") != "0" and w.shape[0] < w.shape[1] and w.shape[2:] == (1, 1):
+        if w.shape[0] < w.shape[1] and w.shape[2:] == (1, 1):
             wp = torch.zeros((w.shape[1], w.shape[1], 1, 1), dtype=w.dtype)
             wp[:w.shape[0]] = w
             bp = torch.zeros(w.shape[1], dtype=b.dtype)

@@ -207,7 +207,8 @@ def _small_map_outputs():
     """fp16 blocks on maps below 12 000 pixels, widths 256 / 368 (-> 384) / 512 / 128: a 4-block chain behind an adaptor block
     (fused heads, quant at the end), a shortcut + quant block, a 2-block chain ending in a fused 1x1 conv with quant.  (Width 128:
     the blocks without adaptor and without a head computed by their predecessor take dcb_tail128_kernel<128, G32, HEADIN> - the
-    head inside - unless DCVC_T32=0 / DCVC_T32_128=0.)"""
+    head inside - unless DCVC_T32=0.)  Then single blocks of widths 256 / 368 / 384 / 512 on a regular and a ragged map: plain
+    and with shortcut, each with and without quant, a two-source adaptor block, a fused 1x1 conv without quant."""
     from opendcvc_amd import _lib, nn
     outs = []
     for c, (H, W) in ((256, (21, 19)), (368, (12, 27)), (512, (14, 20)), (256, (68, 120)), (128, (17, 30)), (128, (35, 61))):
@@ -223,6 +224,23 @@ def _small_map_outputs():
                "o.bias": (rng.standard_normal(c) * 0.1).astype(np.float32)}
         conv = nn.Conv2d(csd, "o", torch.float16, epilogue=_lib.EPI_BIAS_QUANT)
         outs.append(nn.dcb_chain(blocks[1:3], x1, then_conv=conv, conv_quant=q))
+    f16 = torch.float16
+    for c in (256, 368, 384, 512):
+        for (H, W) in ((68, 120), (67, 119)):
+            rng = _rng(7000 + c + H)
+            plain = nn.DepthConvBlock(make_dcb_weights(rng, "m", c, c, False), "m", f16)
+            x = to_dev(rng.standard_normal((H, W, c)).astype(np.float32), plain.cin_p, f16)
+            q = torch.from_numpy(rng.uniform(0.5, 1.5, c).astype(np.float32)).cuda()
+            outs += [plain(x), plain(x, quant=q)]
+            sc = nn.DepthConvBlock(make_dcb_weights(rng, "m", c, c, False), "m", f16, shortcut=True)
+            outs += [sc(x), sc(x, quant=q)]
+            ad = nn.DepthConvBlock(make_dcb_weights(rng, "m", 2 * c, c, True), "m", f16)
+            x2 = to_dev(rng.standard_normal((H, W, 2 * c)).astype(np.float32), ad.cin_p, f16)
+            s0 = ad.cin_p // 2 // 64 * 64
+            outs.append(ad(x2[..., :s0].contiguous(), x2[..., s0:].contiguous()))
+            csd = {"o.weight": (rng.standard_normal((c, c, 1, 1)) / np.sqrt(c)).astype(np.float32),
+                   "o.bias": (rng.standard_normal(c) * 0.1).astype(np.float32)}
+            outs.append(nn.dcb_chain([plain], x, then_conv=nn.Conv2d(csd, "o", f16, epilogue=_lib.EPI_BIAS)))
     torch.cuda.synchronize()
     return np.concatenate([o.float().cpu().numpy().ravel() for o in outs])
 
@@ -241,6 +259,17 @@ def test_tail32_equals_tail_kernel_bitwise(tmp_path):
         subprocess.check_call([sys.executable, "-c", code], env=dict(os.environ, DCVC_T32=v))
         outs[v] = np.load(path)
     assert np.isfinite(outs["1"]).all() and np.array_equal(outs["1"], outs["0"])
+
+
+def test_scratch_bytes_are_three_activation_slots():
+    """dcvc_dcb_scratch_bytes: two `a` slots (chained blocks alternate) + x', on small and large maps, fp16 and fp32."""
+    from opendcvc_amd import _lib, nn
+    L = _lib.lib()
+    for dtype, es in ((torch.float16, 2), (torch.float32, 4)):
+        for c, cp in ((128, 128), (256, 256), (320, 320), (368, 384), (512, 512)):
+            blk = nn.DepthConvBlock(make_dcb_weights(_rng(c), "m", c, c, False), "m", dtype)
+            for (H, W) in ((68, 120), (34, 60), (67, 119), (136, 240), (100, 120)):
+                assert L.dcvc_dcb_scratch_bytes(blk.h, H, W) == 3 * H * W * cp * es
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
