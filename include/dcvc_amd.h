@@ -31,7 +31,11 @@ extern "C" {
 
 #define DCVC_ABI_VERSION 1
 
-enum { DCVC_F16 = 0, DCVC_F32 = 1 };
+enum {
+    DCVC_F16 = 0,
+    DCVC_F32 = 1,
+    DCVC_U8 = 2 /* uint8 planes: an element type of the metric entries (dcvc_sse, dcvc_msssim_stats) ONLY */
+};
 
 enum {              /* epilogue of dcvc_conv_forward */
     DCVC_EPI_BIAS = 0,      /* out = conv + bias                                       */
@@ -333,6 +337,32 @@ void* dcvc_host_device_ptr(void* host);
 #define DCVC_COMPACT_BLOCKS 256
 int dcvc_compact_symbols(const int16_t* packed, int n_per_part, int n_parts, int16_t* out_host, int32_t* counts_host,
                          int32_t* workspace, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Distortion metrics of a decoded frame on the device (the reference computes them on the host from copied planes:
+ * test_video.py:94-127 get_distortion, src/utils/metrics.py).  fp64 arithmetic, fixed reduction order.  Results are
+ * written by a kernel into a dcvc_host_alloc buffer and are valid for the host once the stream has passed that point;
+ * no call waits for the device, so all planes of a frame can be enqueued before ONE synchronisation.
+ *
+ * The planes get_distortion compares for a YUV 4:2:0 source (test_video.py:96-101), NOT rounded, in the storage type:
+ * crop to H x W, Y = clamp(x * 255, 0, 255) [H][W], U / V = clamp(avg_pool2d(x, 2) * 255, 0, 255) [H/2][W/2] - exactly
+ * the values dcvc_frame_to_yuv420 rounds / truncates to uint8.  (RGB sources: dcvc_frame_to_rgb.) */
+int dcvc_frame_to_yuv420_planes(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, void* y, void* u, void* v,
+                                void* stream);
+/* *out_host = sum over i < n of ((double)a[i] - (double)b[i])^2 (calc_psnr, metrics.py:81-96, before the mean and the
+ * logarithm).  a_type / b_type: DCVC_F16, DCVC_F32 or DCVC_U8.  workspace: device, DCVC_SSE_BLOCKS doubles. */
+#define DCVC_SSE_BLOCKS 1024
+int dcvc_sse(int a_type, const void* a, int b_type, const void* b, int64_t n, void* workspace, double* out_host,
+             void* stream);
+/* MS-SSIM statistics of two H x W planes (calc_msssim + calc_ssim, metrics.py:15-68; the 11x11 Gaussian window, sigma
+ * 1.5, is applied directly as a row and a column pass instead of by FFT): levels = 5, or 4 if H < 176 or W < 176;
+ * H < 88 or W < 88 is an argument error.  Per level l: out_host[2 l] = mean of the ssim map, out_host[2 l + 1] = mean
+ * of the cs map over the 'valid' (h - 10) x (w - 10) positions; between levels the 2 x 2 box at even positions
+ * (ndimage.convolve mode='reflect', then [::2, ::2]).  *levels_out (host, may be NULL) is set on return.  The final
+ * prod(cs[:L-1] ** weight[:L-1]) * ssim[L-1] ** weight[L-1] is the caller's (a negative contrast mean gives NaN there, as in
+ * the reference).  workspace: device, 8-byte aligned, dcvc_msssim_ws_bytes(H, W) bytes (< 0: bad size). */
+int64_t dcvc_msssim_ws_bytes(int H, int W);
+int dcvc_msssim_stats(int a_type, const void* a, int b_type, const void* b, int H, int W, double data_range,
+                      void* workspace, double* out_host, int* levels_out, void* stream);
 /* dst[0..n) = src[0..n) on the device by a kernel (the per-frame row of the quantisation tables: src/models/video_model.py:303-305
  * slices them per call; a runtime copy command costs an order of magnitude more than the kernel) */
 int dcvc_copy_f32(float* dst, const float* src, int n, void* stream);

@@ -7,7 +7,7 @@ CPU path.
 import ctypes
 import os
 import subprocess
-from ctypes import (POINTER, c_char_p, c_float, c_int, c_int8, c_int16, c_int32, c_int64, c_size_t,
+from ctypes import (POINTER, c_char_p, c_double, c_float, c_int, c_int8, c_int16, c_int32, c_int64, c_size_t,
                     c_uint8, c_uint32, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -17,6 +17,8 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("DCVC_AMD_LIB") or
                         ("libdcvc_amd_diag.so" if os.environ.get("DCVC_AMD_DIAG") else "libdcvc_amd.so"))
 
 F16, F32 = 0, 1
+U8 = 2                    # uint8 planes: the metric entries only (dcvc_sse, dcvc_msssim_stats)
+SSE_BLOCKS = 1024         # DCVC_SSE_BLOCKS
 EPI_BIAS, EPI_BIAS_QUANT, EPI_SHUFFLE2, EPI_WSILU = 0, 1, 2, 3
 
 
@@ -117,6 +119,10 @@ _SIGS = {
     "dcvc_host_free": (None, [_P]),
     "dcvc_host_device_ptr": (_P, [_P]),
     "dcvc_compact_symbols": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "dcvc_frame_to_yuv420_planes": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dcvc_sse": (_I, [_I, _P, _I, _P, _L, _P, _P, _P]),
+    "dcvc_msssim_ws_bytes": (_L, [_I, _I]),
+    "dcvc_msssim_stats": (_I, [_I, _P, _I, _P, _I, _I, c_double, _P, _P, POINTER(_I), _P]),
     "dcvc_copy_f32": (_I, [_P, _P, _I, _P]),
     "dcvc_memcpy_d2h": (_I, [_P, _P, c_size_t, _P]),
     "dcvc_memcpy_h2d": (_I, [_P, _P, c_size_t, _P]),

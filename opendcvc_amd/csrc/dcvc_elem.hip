@@ -6,38 +6,13 @@
 // _Float16 or float.
 #include "common.hpp"
 #include "gemm_core.hpp"
+#include "plane_math.hpp"   // ld / to_t / st / clampf, yuv420_luma / yuv420_chroma
 
 namespace {
 
 constexpr int EB = 256;   // threads per block for 1-D kernels
 
 inline int nblocks(int64_t n) { return (int)((n + EB - 1) / EB); }
-
-template <typename T>
-__device__ __forceinline__ float ld(const T* p, int64_t i)
-{
-    return (float)p[i];
-}
-// fp32 VALUE -> storage type.  The empty asm hides the value's producer, so the compiler cannot fold the preceding
-// fp32 add / multiply into v_fma_mixlo_f16 (one rounding) in one kernel and leave add + cvt (two roundings) in another:
-// the encoder's and the decoder's y_hat kernels must round alike (see Traits<half_t>::from_f, gemm_core.hpp).
-template <typename T>
-__device__ __forceinline__ T to_t(float v)
-{
-    asm("" : "+v"(v));
-    return (T)v;
-}
-template <typename T>
-__device__ __forceinline__ void st(T* p, int64_t i, float v)
-{
-    p[i] = to_t<T>(v);
-}
-
-__device__ __forceinline__ float clampf(float v, float lo, float hi)
-{
-    v = v < lo ? lo : v;
-    return v > hi ? hi : v;
-}
 
 constexpr float kScaleMin = 0.11f, kScaleMax = 16.0f;
 // log(0.11) and 127 / (log(16) - log(0.11)) rounded to float exactly as the reference's python
@@ -251,8 +226,7 @@ __global__ void frame_to_yuv420_kernel(const T* x, int HP, int WP, int H, int W,
     if (i >= ny + 2 * nc) return;
     if (i < ny) {
         const int xw = (int)(i % W), y = (int)(i / W);
-        const float s = (float)to_t<T>(ld(x, (int64_t)y * WP + xw) * 255.0f);   // product rounded to the storage type, as torch does
-        yp[i] = (uint8_t)dcvc_roundf(clampf(s, 0.f, 255.f));
+        yp[i] = (uint8_t)dcvc_roundf(yuv420_luma<T>(x, WP, y, xw));
         return;
     }
     const int64_t j = i - ny;
@@ -260,11 +234,7 @@ __global__ void frame_to_yuv420_kernel(const T* x, int HP, int WP, int H, int W,
     const int64_t k = c == 1 ? j : j - nc;
     const int w2 = W >> 1;
     const int xw = (int)(k % w2), y = (int)(k / w2);
-    const T* pl = x + (int64_t)c * HP * WP;
-    const float a = ld(pl, (int64_t)(2 * y) * WP + 2 * xw), b = ld(pl, (int64_t)(2 * y) * WP + 2 * xw + 1);
-    const float d = ld(pl, (int64_t)(2 * y + 1) * WP + 2 * xw), e = ld(pl, (int64_t)(2 * y + 1) * WP + 2 * xw + 1);
-    const float m = (float)to_t<T>(((a + b) + (d + e)) * 0.25f);                 // avg_pool2d(2) result in the storage type
-    float s = clampf((float)to_t<T>(m * 255.0f), 0.f, 255.f);
+    float s = yuv420_chroma<T>(x + (int64_t)c * HP * WP, WP, y, xw);
     if (round_uv) s = dcvc_roundf(s);
     (c == 1 ? up : vp)[k] = (uint8_t)s;                                      // truncation like `.to(uint8)`
 }

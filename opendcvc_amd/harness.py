@@ -278,12 +278,15 @@ def _to_device(planes, device):
 # ---------------------------------------------------------------------------------- one rate point
 def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=None, intra_period=-1,
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
-                  src_type="yuv420", calc_ssim=False):
+                  src_type="yuv420", calc_ssim=False, metrics="host"):
     """Encodes `frame_num` frames of a YUV 4:2:0 file (src_type "yuv420") or of a directory of PNGs ("png": RGB, converted
     to YCbCr around the codec) into the reference's container (optionally written to bin_path), decodes the container again,
     and returns the reference-schema log.  i_net / p_net: DMCI / DMC (weights loaded, .update() called, on `device`,
     optionally .half()).  calc_ssim: MS-SSIM per frame (host computation, slow) instead of zeros.  rec_path: the decoded
-    sequence as a planar YUV file / as PNGs in that directory."""
+    sequence as a planar YUV file / as PNGs in that directory.  metrics: "host" (torch glue + host numpy / scipy MS-SSIM) or
+    "device" (metrics.DeviceMetrics: PSNR and MS-SSIM by HIP kernels, one synchronisation per frame)."""
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics {metrics!r}: 'host' or 'device'")
     if src_type not in ("yuv420", "png"):
         raise ValueError(f"src_type {src_type!r}: the reference harness reads 'yuv420' or 'png'")
     png = src_type == "png"
@@ -325,6 +328,10 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         rec = open(rec_path, "wb")
     from .pipeline import FramePacket
     dec = SequenceDecoder(i_net, p_net, height, width, two)
+    dm = None
+    if metrics == "device":
+        from .metrics import DeviceMetrics
+        dm = DeviceMetrics(dev)
     for fi in range(frame_num):
         planes = _to_device(reader.read(), dev)
         torch.cuda.synchronize(dev)
@@ -335,7 +342,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         torch.cuda.synchronize(dev)
         dec_time.append(time.time() - t0)
         if png:
-            p_, s_ = rgb_distortion(x_hat, planes[0], calc_ssim)
+            # (the PNG reader's planes are a transposed view: the kernels read them planar, as load_rgb_frame does)
+            p_, s_ = dm.rgb(x_hat, planes[0].contiguous(), calc_ssim) if dm else rgb_distortion(x_hat, planes[0], calc_ssim)
             psnrs.append(p_)
             ssims.append(s_)
             if rec_path:        # clamp * 255 rounded to uint8 (test_video.py:314-318), names like the source's
@@ -344,8 +352,13 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                 Image.fromarray(rgb8.transpose(1, 2, 0)).save(os.path.join(rec_path, "im%s.png" % str(fi + 1).zfill(reader.digits)))
             continue
         y, u, v = planes
-        psnrs.append(yuv420_distortion(x_hat, y, u, v))
-        ssims.append(yuv420_msssim(x_hat, y, u, v) if calc_ssim else [0.0, 0.0, 0.0, 0.0])
+        if dm:
+            p_, s_ = dm.yuv420(x_hat, y, u, v, calc_ssim)
+            psnrs.append(p_)
+            ssims.append(s_)
+        else:
+            psnrs.append(yuv420_distortion(x_hat, y, u, v))
+            ssims.append(yuv420_msssim(x_hat, y, u, v) if calc_ssim else [0.0, 0.0, 0.0, 0.0])
         if rec is not None:     # clamp * 255, Y rounded, chroma truncated (test_video.py:307-311)
             for plane in store_yuv420_frame(x_hat, height, width):
                 rec.write(plane.cpu().numpy().tobytes())
@@ -555,7 +568,7 @@ def run_job(nets, job, opts):
                         job["qp_i"], job["qp_p"], intra_period=job["intra_period"], reset_interval=job["reset_interval"],
                         bin_path=bin_path, rec_path=rec_path, verbose=opts.get("verbose", 0),
                         verbose_json=opts.get("verbose_json", False), device="cuda:0", src_type=job.get("src_type", "yuv420"),
-                        calc_ssim=bool(opts.get("calc_ssim")))
+                        calc_ssim=bool(opts.get("calc_ssim")), metrics=opts.get("metrics") or "host")
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -622,6 +635,8 @@ def build_parser():
     ap.add_argument("--stream-path", "--stream_path", help="write every point's container to <stream-path>/<dataset>/<sequence>_q<qp>.bin")
     ap.add_argument("--output-path", "--output_path", help="merged JSON log of the manifest run")
     ap.add_argument("--calc-ssim", "--calc_ssim", **flag, help="MS-SSIM per frame (reference --calc_ssim; host computation, slow)")
+    ap.add_argument("--metrics", choices=("host", "device"), default="host",
+                    help="where PSNR / MS-SSIM are computed: host (torch glue + numpy / scipy MS-SSIM) or device (HIP kernels)")
     ap.add_argument("--force-intra", "--force_intra", **flag, help="every frame an I frame (reference --force_intra)")
     ap.add_argument("--check-existing", "--check_existing", **flag,
                     help="with --stream-path: do not code a point again whose .bin and .json exist (reference --check_existing)")
@@ -662,7 +677,7 @@ def manifest_options(args, ap):
                 force_frame_num=args.force_frame_num, force_intra_period=args.force_intra_period,
                 reset_interval=args.reset_interval, model_i=args.model_i, model_p=args.model_p,
                 force_zero_thres=args.force_zero_thres, fp32=args.fp32, stream_path=stream_path,
-                verbose=args.verbose, verbose_json=args.verbose_json, calc_ssim=args.calc_ssim,
+                verbose=args.verbose, verbose_json=args.verbose_json, calc_ssim=args.calc_ssim, metrics=args.metrics,
                 force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
     return opts, gpus
 
@@ -715,7 +730,7 @@ def main(argv=None):
     res = run_sweep(make_nets, args.src, args.width, args.height, args.frames, args.rate_num,
                     args.qp_i or None, args.qp_p or None, bin_prefix=args.bin_prefix,
                     intra_period=args.intra_period, reset_interval=args.reset_interval, verbose=args.verbose,
-                    verbose_json=args.verbose_json, src_type=args.src_type, calc_ssim=args.calc_ssim)
+                    verbose_json=args.verbose_json, src_type=args.src_type, calc_ssim=args.calc_ssim, metrics=args.metrics)
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:
