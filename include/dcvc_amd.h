@@ -34,7 +34,8 @@ extern "C" {
 enum {
     DCVC_F16 = 0,
     DCVC_F32 = 1,
-    DCVC_U8 = 2 /* uint8 planes: an element type of the metric entries (dcvc_sse, dcvc_msssim_stats) ONLY */
+    DCVC_U8 = 2, /* uint8 planes: an element type of the metric entries (dcvc_sse, dcvc_msssim_stats) ONLY */
+    DCVC_U16 = 3 /* uint16 planes (samples above 8 bits, value in the LOW bits): the same two entries ONLY */
 };
 
 enum {              /* epilogue of dcvc_conv_forward */
@@ -349,7 +350,7 @@ int dcvc_compact_symbols(const int16_t* packed, int n_per_part, int n_parts, int
 int dcvc_frame_to_yuv420_planes(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, void* y, void* u, void* v,
                                 void* stream);
 /* *out_host = sum over i < n of ((double)a[i] - (double)b[i])^2 (calc_psnr, metrics.py:81-96, before the mean and the
- * logarithm).  a_type / b_type: DCVC_F16, DCVC_F32 or DCVC_U8.  workspace: device, DCVC_SSE_BLOCKS doubles. */
+ * logarithm).  a_type / b_type: DCVC_F16, DCVC_F32, DCVC_U8 or DCVC_U16.  workspace: device, DCVC_SSE_BLOCKS doubles. */
 #define DCVC_SSE_BLOCKS 1024
 int dcvc_sse(int a_type, const void* a, int b_type, const void* b, int64_t n, void* workspace, double* out_host,
              void* stream);
@@ -363,6 +364,38 @@ int dcvc_sse(int a_type, const void* a, int b_type, const void* b, int64_t n, vo
 int64_t dcvc_msssim_ws_bytes(int H, int W);
 int dcvc_msssim_stats(int a_type, const void* a, int b_type, const void* b, int H, int W, double data_range,
                       void* workspace, double* out_host, int* levels_out, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Frame I/O for the other raw formats (csrc/dcvc_pixfmt.hip): bit depths 8 .. 16, 4:2:0 and 4:4:4, planar and
+ * semi-planar planes, rows with a pitch.  dcvc_yuv420_to_frame / dcvc_frame_to_yuv420 above keep the reference
+ * harness's 8-bit arithmetic; these entries follow the reference family's YUVReader / YUVWriter (DCVC-FM
+ * src/utils/video_reader.py:130-181, video_writer.py:85-128, src/transforms/functional.py:98-131) for every format.
+ *
+ * A pixel format is four integers: chroma (420 or 444), bit_depth (8 .. 16; above 8 a sample is a little-endian 16-bit
+ * word), semi_planar (0: planes y, u, v; 1: y and ONE plane of interleaved (U, V) pairs, v is ignored and may be
+ * NULL - NV12 / P010, 4:2:0 only), msb_aligned (the value sits in the TOP bit_depth bits of its word, as in P010; not
+ * with 8 bits).  max_val = (1 << bit_depth) - 1.  4:2:0 needs an even H and W.  y_stride / c_stride: distance between
+ * two rows of the luma plane / of a chroma plane in SAMPLES, at least the row length (W; W / 2 for planar 4:2:0
+ * chroma; W for an interleaved row), so that a surface with a pitch needs no repacking; an interleaved plane and its
+ * stride are aligned to a pair.  The kernels use the widest access (up to 16 bytes per lane) the planes' addresses and
+ * strides allow.  The model frame is 16-byte aligned and its row length a multiple of 8.
+ * All argument checks come before any launch and need no device.
+ *
+ * planes -> the padded YCbCr 4:4:4 model input [3][H+pad_b][W+pad_r]: (float)sample / (float)max_val as one fp32
+ * division, one rounding to the storage type, nearest chroma up-sampling for 4:2:0, replicate pad. */
+int dcvc_planes_to_frame(int dtype, int chroma, int bit_depth, int semi_planar, int msb_aligned, const void* y,
+                         const void* u_or_uv, const void* v, int64_t y_stride, int64_t c_stride, int H, int W, int pad_b,
+                         int pad_r, void* out_nchw, void* stream);
+/* reconstruction [3][Hp][Wp] -> the planes of the H x W picture: crop, every sample to fp32, 4:2:0 chroma
+ * ((a + b) + (d + e)) * 0.25f over the 2x2 block, clip(., 0, 1) * max_val, round to nearest even, clip to [0, max_val],
+ * shifted up if msb_aligned - luma and chroma alike. */
+int dcvc_frame_to_planes(int dtype, int chroma, int bit_depth, int semi_planar, int msb_aligned, const void* x_nchw, int Hp,
+                         int Wp, int H, int W, void* y, void* u_or_uv, void* v, int64_t y_stride, int64_t c_stride,
+                         void* stream);
+/* the values dcvc_frame_to_planes rounds, NOT rounded: clip(., 0, 1) * max_val as fp32 planes y [H][W], u / v [H/2][W/2]
+ * (4:2:0) or [H][W] (4:4:4), whatever the storage type - what PSNR and MS-SSIM (data_range = max_val) compare with the
+ * source's samples (DCVC_U8 / DCVC_U16 operands of dcvc_sse / dcvc_msssim_stats). */
+int dcvc_frame_to_metric_planes(int dtype, int chroma, int max_val, const void* x_nchw, int Hp, int Wp, int H, int W,
+                                float* y, float* u, float* v, void* stream);
 /* dst[0..n) = src[0..n) on the device by a kernel (the per-frame row of the quantisation tables: src/models/video_model.py:303-305
  * slices them per call; a runtime copy command costs an order of magnitude more than the kernel) */
 int dcvc_copy_f32(float* dst, const float* src, int n, void* stream);

@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("DCVC_AMD_LIB") or
 
 F16, F32 = 0, 1
 U8 = 2                    # uint8 planes: the metric entries only (dcvc_sse, dcvc_msssim_stats)
+U16 = 3                   # uint16 planes (low-bit-aligned samples above 8 bits): the same entries only
 SSE_BLOCKS = 1024         # DCVC_SSE_BLOCKS
 EPI_BIAS, EPI_BIAS_QUANT, EPI_SHUFFLE2, EPI_WSILU = 0, 1, 2, 3
 
@@ -123,6 +124,9 @@ _SIGS = {
     "dcvc_sse": (_I, [_I, _P, _I, _P, _L, _P, _P, _P]),
     "dcvc_msssim_ws_bytes": (_L, [_I, _I]),
     "dcvc_msssim_stats": (_I, [_I, _P, _I, _P, _I, _I, c_double, _P, _P, POINTER(_I), _P]),
+    "dcvc_planes_to_frame": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _I, _I, _I, _I, _P, _P]),
+    "dcvc_frame_to_planes": (_I, [_I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _L, _P]),
+    "dcvc_frame_to_metric_planes": (_I, [_I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dcvc_copy_f32": (_I, [_P, _P, _I, _P]),
     "dcvc_memcpy_d2h": (_I, [_P, _P, c_size_t, _P]),
     "dcvc_memcpy_h2d": (_I, [_P, _P, c_size_t, _P]),

@@ -12,10 +12,10 @@
 namespace {
 
 constexpr int MB = 256;          // threads per block
-constexpr int kF64 = 3;          // internal element type: the fp64 planes of the coarser MS-SSIM scales
+constexpr int kF64 = -1;         // internal element type: the fp64 planes of the coarser MS-SSIM scales
 
 inline int mblocks(int64_t n) { return (int)((n + MB - 1) / MB); }
-inline bool plane_type_ok(int t) { return t == DCVC_F16 || t == DCVC_F32 || t == DCVC_U8; }
+inline bool plane_type_ok(int t) { return t == DCVC_F16 || t == DCVC_F32 || t == DCVC_U8 || t == DCVC_U16; }
 
 __device__ __forceinline__ double ldd(const void* p, int type, int64_t i)
 {
@@ -23,6 +23,7 @@ __device__ __forceinline__ double ldd(const void* p, int type, int64_t i)
     case DCVC_F16: return (double)static_cast<const _Float16*>(p)[i];
     case DCVC_F32: return (double)static_cast<const float*>(p)[i];
     case DCVC_U8: return (double)static_cast<const uint8_t*>(p)[i];
+    case DCVC_U16: return (double)static_cast<const uint16_t*>(p)[i];
     default: return static_cast<const double*>(p)[i];
     }
 }

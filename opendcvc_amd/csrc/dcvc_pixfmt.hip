@@ -1,0 +1,444 @@
+// dcvc_pixfmt.hip - frame I/O for the raw formats beyond planar 8-bit 4:2:0: bit depths 8 .. 16 (little-endian 16-bit
+// words above 8 bits, value in the low or in the top bits), 4:2:0 and 4:4:4, planar and semi-planar (NV12 / P010: one
+// interleaved UV plane), rows with a pitch.  The arithmetic is the reference family's YUVReader / YUVWriter
+// (DCVC-FM src/utils/video_reader.py:130-181, video_writer.py:85-128, src/transforms/functional.py:98-131):
+//   load   (float)s / (float)max_val, ONE rounding to the storage type, nearest chroma up-sampling, replicate pad
+//   store  fp32: 4:2:0 chroma ((a + b) + (d + e)) * 0.25f, clip(., 0, 1) * max_val, rintf (nearest even), clip(0, max_val)
+//   metric the store's values before the rounding, fp32 planes
+// These are streaming kernels: a thread owns 8 consecutive pixels of a row (4:2:0: an 8 x 2 luma block and the 4 chroma
+// samples of both planes under it, read / formed once), the model side moves in 16-byte accesses, the sample side in the
+// widest access the planes' addresses and strides allow (chosen per launch, uniform over the grid).  No LDS, no atomics.
+#include "common.hpp"
+#include "plane_math.hpp"
+
+#include <algorithm>
+#include <cstdint>
+#include <type_traits>
+
+namespace {
+
+constexpr int PB = 256;                       // threads per block
+enum { L_420P = 0, L_420SP = 1, L_444P = 2 }; // plane layout of a launch
+
+template <typename E, int VW>
+struct alignas(sizeof(E) * VW) Pack {
+    E v[VW];
+};
+template <typename T>
+struct alignas(16) Pix8 {                     // 8 pixels of a model row: one 16-byte access in fp16, two in fp32
+    T v[8];
+};
+
+// an interleaved (U, V) pair of samples as one element: U in the low half (little-endian memory order U, V)
+template <typename S>
+struct PairOf;
+template <>
+struct PairOf<uint8_t> {
+    typedef uint16_t type;
+};
+template <>
+struct PairOf<uint16_t> {
+    typedef uint32_t type;
+};
+
+constexpr int cmin(int a, int b) { return a < b ? a : b; }
+constexpr int cmax(int a, int b) { return a > b ? a : b; }
+// elements per access of an 8-element (luma, 4:4:4 chroma, UV pairs seen as samples) and of a 4-element (4:2:0 chroma
+// samples or pairs) piece of a row at access class A (8, 4, 2, 1): at most 16 bytes
+template <typename E>
+constexpr int vw8(int A) { return cmin(A, 16 / (int)sizeof(E)); }
+template <typename E>
+constexpr int vw4(int A) { return cmin(cmax(A / 2, 1), 16 / (int)sizeof(E)); }
+
+// o[0..N) = row[x .. x + N), columns past n - 1 clamped to n - 1 (replicate pad); VW elements per access where the
+// whole piece lies inside the row
+template <typename E, int N, int VW>
+__device__ __forceinline__ void load_row(const E* row, int x, int n, E (&o)[N])
+{
+#pragma unroll
+    for (int c = 0; c < N; c += VW) {
+        if (x + c + VW <= n) {
+            const Pack<E, VW> p = *reinterpret_cast<const Pack<E, VW>*>(row + x + c);
+#pragma unroll
+            for (int k = 0; k < VW; ++k) o[c + k] = p.v[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) o[c + k] = row[min(x + c + k, n - 1)];
+        }
+    }
+}
+
+// row[x .. x + N) = v[0..N) for the columns below n
+template <typename E, int N, int VW>
+__device__ __forceinline__ void store_row(E* row, int x, int n, const E (&v)[N])
+{
+#pragma unroll
+    for (int c = 0; c < N; c += VW) {
+        if (x + c + VW <= n) {
+            Pack<E, VW> p;
+#pragma unroll
+            for (int k = 0; k < VW; ++k) p.v[k] = v[c + k];
+            *reinterpret_cast<Pack<E, VW>*>(row + x + c) = p;
+        } else {
+#pragma unroll
+            for (int k = 0; k < VW; ++k)
+                if (x + c + k < n) row[x + c + k] = v[c + k];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ planes -> padded model frame
+template <typename T, typename S>
+__device__ __forceinline__ T norm_sample(S s, int shift, float maxf)
+{
+    return to_t<T>((float)((unsigned)s >> shift) / maxf);
+}
+
+template <typename T, typename S, int N, int VW>
+__device__ __forceinline__ void load_plane_row(const S* row, int x0, int W, int shift, float maxf, T* dst)
+{
+    S s[N];
+    load_row<S, N, VW>(row, x0, W, s);
+    Pix8<T> o;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o.v[k] = norm_sample<T, S>(s[k], shift, maxf);
+    *reinterpret_cast<Pix8<T>*>(dst) = o;
+}
+
+template <typename T, typename S, int LAYOUT, int A>
+__global__ __launch_bounds__(PB) void planes_to_frame_kernel(const S* yp, const void* up_, const S* vp, int64_t ys, int64_t cs,
+                                                             int H, int W, int HO, int WO, int shift, float maxf, T* out)
+{
+    constexpr int RY = LAYOUT == L_444P ? 1 : 2;            // rows of the frame a thread owns
+    const int tw = WO >> 3;
+    const int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x;
+    const int ty = (int)(i / tw), tx = (int)(i - (int64_t)ty * tw);
+    if (ty >= HO / RY) return;
+    const int x0 = tx * 8;
+    const int64_t plane = (int64_t)HO * WO;
+#pragma unroll
+    for (int r = 0; r < RY; ++r) {
+        const int y = ty * RY + r, sy = min(y, H - 1);
+        load_plane_row<T, S, 8, vw8<S>(A)>(yp + sy * ys, x0, W, shift, maxf, out + (int64_t)y * WO + x0);
+    }
+    if constexpr (LAYOUT == L_444P) {
+        const int sy = min(ty, H - 1);
+        load_plane_row<T, S, 8, vw8<S>(A)>(static_cast<const S*>(up_) + sy * cs, x0, W, shift, maxf,
+                                           out + plane + (int64_t)ty * WO + x0);
+        load_plane_row<T, S, 8, vw8<S>(A)>(vp + sy * cs, x0, W, shift, maxf, out + 2 * plane + (int64_t)ty * WO + x0);
+    } else {
+        // 4 chroma samples of each plane, each used for two columns and both rows (nearest up-sampling); the clamped
+        // chroma coordinate is the clamped luma coordinate halved, H and W being even
+        const int cy = min(ty, (H >> 1) - 1), cx0 = tx * 4, cn = W >> 1;
+        S u[4], v[4];
+        if constexpr (LAYOUT == L_420P) {
+            load_row<S, 4, vw4<S>(A)>(static_cast<const S*>(up_) + cy * cs, cx0, cn, u);
+            load_row<S, 4, vw4<S>(A)>(vp + cy * cs, cx0, cn, v);
+        } else {
+            typedef typename PairOf<S>::type P;
+            P p[4];
+            load_row<P, 4, vw4<P>(A)>(reinterpret_cast<const P*>(static_cast<const S*>(up_) + cy * cs), cx0, cn, p);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                u[k] = (S)p[k];
+                v[k] = (S)(p[k] >> (8 * sizeof(S)));
+            }
+        }
+        Pix8<T> ou, ov;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            ou.v[2 * k] = ou.v[2 * k + 1] = norm_sample<T, S>(u[k], shift, maxf);
+            ov.v[2 * k] = ov.v[2 * k + 1] = norm_sample<T, S>(v[k], shift, maxf);
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int64_t o = (int64_t)(2 * ty + r) * WO + x0;
+            *reinterpret_cast<Pix8<T>*>(out + plane + o) = ou;
+            *reinterpret_cast<Pix8<T>*>(out + 2 * plane + o) = ov;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ model frame -> planes / metric planes
+// what becomes of an fp32 plane value: the integer sample of a file ...
+template <typename S>
+struct Quant {
+    typedef S E;
+    int shift;
+    float maxf;
+    __device__ __forceinline__ S operator()(float v) const
+    {
+        v = clampf(v, 0.f, 1.f) * maxf;
+        v = clampf(rintf(v), 0.f, maxf);
+        return (S)((unsigned)v << shift);
+    }
+};
+// ... or the value the metrics compare: the same product, not rounded
+struct Metric {
+    typedef float E;
+    float maxf;
+    __device__ __forceinline__ float operator()(float v) const { return clampf(v, 0.f, 1.f) * maxf; }
+};
+
+template <typename T>
+__device__ __forceinline__ void load_pix8(const T* p, float (&f)[8])
+{
+    const Pix8<T> a = *reinterpret_cast<const Pix8<T>*>(p);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = (float)a.v[k];
+}
+
+template <typename T, typename C, int LAYOUT, int A>
+__global__ __launch_bounds__(PB) void frame_to_planes_kernel(const T* x, int HP, int WP, int H, int W, C cvt, typename C::E* yp,
+                                                             void* up_, typename C::E* vp, int64_t ys, int64_t cs)
+{
+    typedef typename C::E E;
+    constexpr int RY = LAYOUT == L_444P ? 1 : 2;
+    const int tw = (W + 7) >> 3;
+    const int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x;
+    const int ty = (int)(i / tw), tx = (int)(i - (int64_t)ty * tw);
+    if (ty >= H / RY) return;
+    const int x0 = tx * 8;                                   // x0 + 7 < WP: WP is a multiple of 8 and x0 < W <= WP
+    const int64_t plane = (int64_t)HP * WP;
+    float f[8];
+    E q[8];
+#pragma unroll
+    for (int r = 0; r < RY; ++r) {
+        const int y = ty * RY + r;
+        load_pix8(x + (int64_t)y * WP + x0, f);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) q[k] = cvt(f[k]);
+        store_row<E, 8, vw8<E>(A)>(yp + y * ys, x0, W, q);
+    }
+    if constexpr (LAYOUT == L_444P) {
+#pragma unroll
+        for (int c = 1; c < 3; ++c) {
+            load_pix8(x + c * plane + (int64_t)ty * WP + x0, f);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) q[k] = cvt(f[k]);
+            store_row<E, 8, vw8<E>(A)>((c == 1 ? static_cast<E*>(up_) : vp) + ty * cs, x0, W, q);
+        }
+    } else {
+        E uv[2][4];
+#pragma unroll
+        for (int c = 1; c < 3; ++c) {
+            float d[8];
+            load_pix8(x + c * plane + (int64_t)(2 * ty) * WP + x0, f);
+            load_pix8(x + c * plane + (int64_t)(2 * ty + 1) * WP + x0, d);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) uv[c - 1][k] = cvt(((f[2 * k] + f[2 * k + 1]) + (d[2 * k] + d[2 * k + 1])) * 0.25f);
+        }
+        const int cx0 = tx * 4, cn = W >> 1;
+        if constexpr (LAYOUT == L_420P) {
+            store_row<E, 4, vw4<E>(A)>(static_cast<E*>(up_) + ty * cs, cx0, cn, uv[0]);
+            store_row<E, 4, vw4<E>(A)>(vp + ty * cs, cx0, cn, uv[1]);
+        } else if constexpr (!std::is_same<E, float>::value) {
+            typedef typename PairOf<E>::type P;
+            P p[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) p[k] = (P)((P)uv[0][k] | ((P)uv[1][k] << (8 * sizeof(E))));
+            store_row<P, 4, vw4<P>(A)>(reinterpret_cast<P*>(static_cast<E*>(up_) + ty * cs), cx0, cn, p);
+        }
+    }
+}
+
+// ------------------------------------------------------------------ host side
+template <int V>
+using IC = std::integral_constant<int, V>;
+
+template <typename F>
+void with_access(int a, F&& f)
+{
+    switch (a) {
+    case 8: f(IC<8>{}); break;
+    case 4: f(IC<4>{}); break;
+    case 2: f(IC<2>{}); break;
+    default: f(IC<1>{}); break;
+    }
+}
+template <typename F>
+void with_layout(int layout, F&& f)
+{
+    switch (layout) {
+    case L_420P: f(IC<L_420P>{}); break;
+    case L_420SP: f(IC<L_420SP>{}); break;
+    default: f(IC<L_444P>{}); break;
+    }
+}
+
+inline bool aligned(const void* p, int64_t stride, int vw, int es)
+{
+    return ((uintptr_t)p % (uintptr_t)(vw * es)) == 0 && stride % vw == 0;
+}
+
+// the widest access class (8, 4, 2, 1) every plane of the launch allows: `es` bytes per element; the luma plane (and
+// 4:4:4 chroma, and UV pairs seen as samples) moves vw8 elements per access, planar 4:2:0 chroma vw4
+int access_class(int layout, int es, const void* y, const void* u, const void* v, int64_t ys, int64_t cs)
+{
+    const int cap = 16 / es;
+    int a = 8;
+    for (; a > 1; a >>= 1) {
+        const int w8 = std::min(a, cap), w4 = std::min(std::max(a / 2, 1), cap);
+        bool ok = aligned(y, ys, w8, es);
+        if (layout == L_444P) ok = ok && aligned(u, cs, w8, es) && aligned(v, cs, w8, es);
+        if (layout == L_420P) ok = ok && aligned(u, cs, w4, es) && aligned(v, cs, w4, es);
+        if (layout == L_420SP) ok = ok && aligned(u, cs, 2 * std::min(std::max(a / 2, 1), 16 / (2 * es)), es);
+        if (ok) break;
+    }
+    return a;
+}
+
+struct Fmt {
+    int layout, shift, ss;     // ss: bytes per sample
+    float maxf;
+};
+
+// the argument checks every entry shares; no device is touched
+int check_format(const char* who, int dtype, int chroma, int bit_depth, int semi_planar, int msb_aligned, int H, int W, Fmt& f)
+{
+    DCVC_REQUIRE(dtype == DCVC_F16 || dtype == DCVC_F32, "%s: bad dtype %d", who, dtype);
+    DCVC_REQUIRE(chroma == 420 || chroma == 444, "%s: chroma %d (420 or 444)", who, chroma);
+    DCVC_REQUIRE(bit_depth >= 8 && bit_depth <= 16, "%s: bit depth %d outside 8 .. 16", who, bit_depth);
+    DCVC_REQUIRE(!(msb_aligned && bit_depth == 8), "%s: 8-bit samples fill their byte, msb_aligned has no meaning", who);
+    DCVC_REQUIRE(!(semi_planar && chroma != 420), "%s: the semi-planar layout is 4:2:0 (NV12 / P010)", who);
+    DCVC_REQUIRE(H > 0 && W > 0, "%s: bad size %d x %d", who, H, W);
+    DCVC_REQUIRE(chroma == 444 || (H % 2 == 0 && W % 2 == 0), "%s: 4:2:0 needs an even height and width (got %d x %d)", who, H, W);
+    f.layout = chroma == 444 ? L_444P : (semi_planar ? L_420SP : L_420P);
+    f.shift = msb_aligned ? 16 - bit_depth : 0;
+    f.ss = bit_depth > 8 ? 2 : 1;
+    f.maxf = (float)((1 << bit_depth) - 1);
+    return 0;
+}
+
+int check_planes(const char* who, const Fmt& f, const void* y, const void* u, const void* v, int64_t ys, int64_t cs, int W)
+{
+    const bool sp = f.layout == L_420SP;
+    DCVC_REQUIRE(y && u && (sp || v), "%s: null plane", who);
+    const int64_t crow = f.layout == L_420P ? W / 2 : W;      // samples per chroma row (an interleaved row holds W)
+    DCVC_REQUIRE(ys >= W && cs >= crow, "%s: row stride below the row length (%lld < %d or %lld < %lld)", who, (long long)ys, W,
+                 (long long)cs, (long long)crow);
+    const uintptr_t m = (uintptr_t)f.ss - 1;
+    DCVC_REQUIRE((((uintptr_t)y | (uintptr_t)u | (uintptr_t)v) & m) == 0, "%s: 16-bit plane not 2-byte aligned", who);
+    DCVC_REQUIRE(!sp || ((uintptr_t)u % (uintptr_t)(2 * f.ss) == 0 && cs % 2 == 0),
+                 "%s: the interleaved plane and its stride must be aligned to a (U, V) pair", who);
+    return 0;
+}
+
+inline unsigned blocks_for(int64_t threads) { return (unsigned)((threads + PB - 1) / PB); }
+
+template <typename T, typename S>
+void launch_load(const Fmt& f, const void* y, const void* u, const void* v, int64_t ys, int64_t cs, int H, int W, int HO, int WO,
+                 void* out, hipStream_t st)
+{
+    const int a = access_class(f.layout, f.ss, y, u, v, ys, cs);
+    const int64_t threads = (int64_t)(WO / 8) * (HO / (f.layout == L_444P ? 1 : 2));
+    with_layout(f.layout, [&](auto lt) {
+        with_access(a, [&](auto at) {
+            planes_to_frame_kernel<T, S, decltype(lt)::value, decltype(at)::value><<<blocks_for(threads), PB, 0, st>>>(
+                (const S*)y, u, (const S*)v, ys, cs, H, W, HO, WO, f.shift, f.maxf, (T*)out);
+        });
+    });
+}
+
+template <typename T, typename C>
+void launch_store(int layout, const C& cvt, const void* x, int HP, int WP, int H, int W, void* y, void* u, void* v, int64_t ys,
+                  int64_t cs, hipStream_t st)
+{
+    typedef typename C::E E;
+    const int a = access_class(layout, (int)sizeof(E), y, u, v, ys, cs);
+    const int64_t threads = (int64_t)((W + 7) / 8) * (H / (layout == L_444P ? 1 : 2));
+    with_layout(layout, [&](auto lt) {
+        with_access(a, [&](auto at) {
+            frame_to_planes_kernel<T, C, decltype(lt)::value, decltype(at)::value><<<blocks_for(threads), PB, 0, st>>>(
+                (const T*)x, HP, WP, H, W, cvt, (E*)y, u, (E*)v, ys, cs);
+        });
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int dcvc_planes_to_frame(int dtype, int chroma, int bit_depth, int semi_planar, int msb_aligned, const void* y,
+                         const void* u_or_uv, const void* v, int64_t y_stride, int64_t c_stride, int H, int W, int pad_b,
+                         int pad_r, void* out_nchw, void* stream)
+{
+    const char* who = "dcvc_planes_to_frame";
+    Fmt f;
+    if (int rc = check_format(who, dtype, chroma, bit_depth, semi_planar, msb_aligned, H, W, f)) return rc;
+    if (int rc = check_planes(who, f, y, u_or_uv, v, y_stride, c_stride, W)) return rc;
+    DCVC_REQUIRE(out_nchw && pad_b >= 0 && pad_r >= 0, "%s: bad output arguments", who);
+    const int HO = H + pad_b, WO = W + pad_r;
+    DCVC_REQUIRE(WO % 8 == 0 && ((uintptr_t)out_nchw & 15) == 0 && (f.layout == L_444P || HO % 2 == 0),
+                 "%s: the padded frame (%d x %d) must be 16-byte aligned, its width a multiple of 8 and, for 4:2:0, its "
+                 "height even", who, HO, WO);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == DCVC_F16) {
+        if (f.ss == 1)
+            launch_load<_Float16, uint8_t>(f, y, u_or_uv, v, y_stride, c_stride, H, W, HO, WO, out_nchw, st);
+        else
+            launch_load<_Float16, uint16_t>(f, y, u_or_uv, v, y_stride, c_stride, H, W, HO, WO, out_nchw, st);
+    } else {
+        if (f.ss == 1)
+            launch_load<float, uint8_t>(f, y, u_or_uv, v, y_stride, c_stride, H, W, HO, WO, out_nchw, st);
+        else
+            launch_load<float, uint16_t>(f, y, u_or_uv, v, y_stride, c_stride, H, W, HO, WO, out_nchw, st);
+    }
+    DCVC_LAUNCH_CHECK();
+    return 0;
+}
+
+int dcvc_frame_to_planes(int dtype, int chroma, int bit_depth, int semi_planar, int msb_aligned, const void* x_nchw, int Hp,
+                         int Wp, int H, int W, void* y, void* u_or_uv, void* v, int64_t y_stride, int64_t c_stride, void* stream)
+{
+    const char* who = "dcvc_frame_to_planes";
+    Fmt f;
+    if (int rc = check_format(who, dtype, chroma, bit_depth, semi_planar, msb_aligned, H, W, f)) return rc;
+    if (int rc = check_planes(who, f, y, u_or_uv, v, y_stride, c_stride, W)) return rc;
+    DCVC_REQUIRE(x_nchw && Hp >= H && Wp >= W && Wp % 8 == 0 && ((uintptr_t)x_nchw & 15) == 0,
+                 "%s: the frame (%d x %d) must hold the picture, be 16-byte aligned and have a width that is a multiple of 8", who,
+                 Hp, Wp);
+    hipStream_t st = (hipStream_t)stream;
+    if (f.ss == 1) {
+        const Quant<uint8_t> q{f.shift, f.maxf};
+        if (dtype == DCVC_F16)
+            launch_store<_Float16>(f.layout, q, x_nchw, Hp, Wp, H, W, y, u_or_uv, v, y_stride, c_stride, st);
+        else
+            launch_store<float>(f.layout, q, x_nchw, Hp, Wp, H, W, y, u_or_uv, v, y_stride, c_stride, st);
+    } else {
+        const Quant<uint16_t> q{f.shift, f.maxf};
+        if (dtype == DCVC_F16)
+            launch_store<_Float16>(f.layout, q, x_nchw, Hp, Wp, H, W, y, u_or_uv, v, y_stride, c_stride, st);
+        else
+            launch_store<float>(f.layout, q, x_nchw, Hp, Wp, H, W, y, u_or_uv, v, y_stride, c_stride, st);
+    }
+    DCVC_LAUNCH_CHECK();
+    return 0;
+}
+
+int dcvc_frame_to_metric_planes(int dtype, int chroma, int max_val, const void* x_nchw, int Hp, int Wp, int H, int W, float* y,
+                                float* u, float* v, void* stream)
+{
+    const char* who = "dcvc_frame_to_metric_planes";
+    DCVC_REQUIRE(dtype == DCVC_F16 || dtype == DCVC_F32, "%s: bad dtype %d", who, dtype);
+    DCVC_REQUIRE(chroma == 420 || chroma == 444, "%s: chroma %d (420 or 444)", who, chroma);
+    DCVC_REQUIRE(max_val >= 255 && max_val <= 65535, "%s: max_val %d outside 255 .. 65535", who, max_val);
+    DCVC_REQUIRE(H > 0 && W > 0 && (chroma == 444 || (H % 2 == 0 && W % 2 == 0)),
+                 "%s: bad size %d x %d (4:2:0 needs an even height and width)", who, H, W);
+    DCVC_REQUIRE(y && u && v && (((uintptr_t)y | (uintptr_t)u | (uintptr_t)v) & 3) == 0, "%s: null or misaligned plane", who);
+    DCVC_REQUIRE(x_nchw && Hp >= H && Wp >= W && Wp % 8 == 0 && ((uintptr_t)x_nchw & 15) == 0,
+                 "%s: the frame (%d x %d) must hold the picture, be 16-byte aligned and have a width that is a multiple of 8", who,
+                 Hp, Wp);
+    const int layout = chroma == 444 ? L_444P : L_420P;
+    const int64_t cs = chroma == 444 ? W : W / 2;
+    const Metric m{(float)max_val};
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == DCVC_F16)
+        launch_store<_Float16>(layout, m, x_nchw, Hp, Wp, H, W, y, u, v, W, cs, st);
+    else
+        launch_store<float>(layout, m, x_nchw, Hp, Wp, H, W, y, u, v, W, cs, st);
+    DCVC_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

@@ -13,6 +13,9 @@ Restates (no code shared) the behaviour of the reference harness:
   src/utils/common.py:49-60      dump_json (floats with six digits)
   test_video.py:66-127, src/utils/video_reader.py:10-47, transforms.py:27-53, metrics.py:9-79   PNG (RGB) sources: BT.709
                           rgb <-> ycbcr around the codec, RGB PSNR; --calc_ssim: MS-SSIM per plane (YUV: (6 Y + U + V) / 8)
+Beyond the reference's two source types: raw files of the other pixel formats (pipeline.PIXEL_FORMATS: 10 / 12 / 16 bits,
+4:4:4, NV12, P010) with the reference family's reader / writer arithmetic (DCVC-FM src/utils/video_reader.py:130-181,
+video_writer.py:85-128) - RawVideoReader, pixfmt_distortion, the frame I/O kernels of csrc/dcvc_pixfmt.hip.
 The codec calls are the drop-in DMCI / DMC of opendcvc_amd.models.
 
     python -m opendcvc_amd.harness --test-config cfg.json -w 16 --gpus 8 --output-path out.json     # configs[4]
@@ -27,8 +30,10 @@ import time
 import numpy as np
 
 from .bitstream import StreamReader, StreamWriter
-from .pipeline import (SequenceDecoder, SequenceEncoder, load_yuv420_frame, store_yuv420_frame,
-                       use_two_entropy_coders)
+from .pipeline import (PIXEL_FORMATS, PixelFormat, SequenceDecoder, SequenceEncoder, load_frame, load_yuv420_frame,
+                       store_frame, store_yuv420_frame, use_two_entropy_coders)
+
+SRC_TYPES = ("yuv420", "png") + tuple(PIXEL_FORMATS)     # "yuv420": planar 8-bit 4:2:0 with the reference harness's arithmetic
 
 
 # ---------------------------------------------------------------------------------- metrics / log
@@ -164,6 +169,47 @@ def yuv420_msssim(x_hat, y, u, v):
     return [(6 * vals[0] + vals[1] + vals[2]) / 8] + vals
 
 
+def source_planes(planes, fmt):
+    """the planes of a PixelFormat source as the metrics read them: planar (y, u, v), value in the LOW bits.  Planar
+    low-aligned formats pass through; the chroma of a semi-planar source is de-interleaved and msb-aligned words are
+    shifted down (torch glue through int16 / int32 views: the measuring side, not the codec's path)"""
+    import torch
+    planes = list(planes)
+    if fmt.semi_planar:
+        uv = planes[1].view(torch.int16) if fmt.sample_bytes == 2 else planes[1]
+        planes = [planes[0]] + [uv[:, k::2].contiguous().view(planes[1].dtype) for k in (0, 1)]
+    if fmt.msb_aligned and fmt.bit_depth < 16:
+        shift = 16 - fmt.bit_depth
+        planes = [((p.view(torch.int16).to(torch.int32) & 0xFFFF) >> shift).to(torch.int16).view(torch.uint16) for p in planes]
+    return planes
+
+
+def pixfmt_metric_planes(x_hat, height, width, fmt):
+    """the planes the metrics of a PixelFormat source compare, in torch: crop, fp32, 4:2:0 chroma the explicit fp32
+    ((a + b) + (d + e)) * 0.25 over the 2x2 block, clip(., 0, 1) * max_val, NOT rounded -> fp32 (y, u, v)"""
+    import torch
+    x = x_hat[0, :, :height, :width].float()
+    y, c = x[0], x[1:]
+    if fmt.chroma == 420:
+        c = ((c[:, 0::2, 0::2] + c[:, 0::2, 1::2]) + (c[:, 1::2, 0::2] + c[:, 1::2, 1::2])) * 0.25
+    scale = lambda p: torch.clamp(p, 0.0, 1.0) * float(fmt.max_val)
+    return scale(y), scale(c[0]), scale(c[1])
+
+
+def pixfmt_distortion(x_hat, planes, fmt, calc_ssim=False):
+    """host-path metrics of a PixelFormat source (the reference family's writer arithmetic before its rounding, PSNR and
+    MS-SSIM with data_range = max_val): -> (psnr, msssim), each [(6 Y + U + V) / 8, Y, U, V]; squared errors and MS-SSIM
+    in float64 on the host"""
+    src = [p.cpu().numpy().astype(np.float64) for p in source_planes(planes, fmt)]
+    H, W = src[0].shape
+    rec = [p.cpu().numpy().astype(np.float64) for p in pixfmt_metric_planes(x_hat, H, W, fmt)]
+    dr = float(fmt.max_val)
+    psnr = [calc_psnr(s, r, dr) for s, r in zip(src, rec)]
+    ms = [calc_msssim(s, r, dr) for s, r in zip(src, rec)] if calc_ssim else [0.0, 0.0, 0.0]
+    comb = lambda m: [(6 * m[0] + m[1] + m[2]) / 8] + m
+    return comb(psnr), comb(ms)
+
+
 def summarize(frame_pixel_num, test_time, frame_types, bits, psnrs, ssims, verbose=False,
               avg_encoding_time=None, avg_decoding_time=None):
     """The reference's per-sequence log (common.py:63-177): averages over I frames (type 0), P frames and
@@ -242,6 +288,32 @@ class YUV420FileReader:
         self.f.close()
 
 
+class RawVideoReader:
+    """a raw file of any PixelFormat: per frame its planes in file order as numpy views of the frame's buffer - (y, u, v),
+    or (y, uv) for semi-planar (the interleaved plane stays interleaved), uint8 or little-endian uint16 as stored
+    (msb-aligned words are not shifted: the loader does that).  EOFError on a missing or short frame."""
+
+    def __init__(self, path, width, height, fmt):
+        self.fmt = PixelFormat.parse(fmt)
+        self.shapes = self.fmt.plane_shapes(height, width)
+        self.frame_bytes = self.fmt.frame_bytes(height, width)
+        self.f = open(path, "rb")
+
+    def read(self):
+        buf = self.f.read(self.frame_bytes)
+        if len(buf) < self.frame_bytes:
+            raise EOFError("raw video file ended")
+        a = np.frombuffer(buf, self.fmt.numpy_dtype)
+        planes, off = [], 0
+        for h, w in self.shapes:
+            planes.append(a[off:off + h * w].reshape(h, w))
+            off += h * w
+        return tuple(planes)
+
+    def close(self):
+        self.f.close()
+
+
 class PNGSequenceReader:
     """a directory of im1.png, im2.png, ... or im00001.png, ... (video_reader.py:10-47): uint8 [3, H, W] RGB per frame"""
 
@@ -279,19 +351,29 @@ def _to_device(planes, device):
 def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=None, intra_period=-1,
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
                   src_type="yuv420", calc_ssim=False, metrics="host"):
-    """Encodes `frame_num` frames of a YUV 4:2:0 file (src_type "yuv420") or of a directory of PNGs ("png": RGB, converted
-    to YCbCr around the codec) into the reference's container (optionally written to bin_path), decodes the container again,
-    and returns the reference-schema log.  i_net / p_net: DMCI / DMC (weights loaded, .update() called, on `device`,
+    """Encodes `frame_num` frames of a YUV 4:2:0 file (src_type "yuv420"), of a raw file in another pixel format
+    (pipeline.PIXEL_FORMATS: "yuv420p10le", "yuv444p", "nv12", "p010le", ...; metrics with data_range = max_val, rec_path in
+    the source's format) or of a directory of PNGs ("png": RGB, converted to YCbCr around the codec) into the reference's
+    container (optionally written to bin_path), decodes the container again, and returns the reference-schema log.  i_net / p_net: DMCI / DMC (weights loaded, .update() called, on `device`,
     optionally .half()).  calc_ssim: MS-SSIM per frame (host computation, slow) instead of zeros.  rec_path: the decoded
     sequence as a planar YUV file / as PNGs in that directory.  metrics: "host" (torch glue + host numpy / scipy MS-SSIM) or
     "device" (metrics.DeviceMetrics: PSNR and MS-SSIM by HIP kernels, one synchronisation per frame)."""
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics {metrics!r}: 'host' or 'device'")
-    if src_type not in ("yuv420", "png"):
-        raise ValueError(f"src_type {src_type!r}: the reference harness reads 'yuv420' or 'png'")
+    if src_type not in SRC_TYPES:
+        raise ValueError(f"src_type {src_type!r}: one of {', '.join(SRC_TYPES)}")
     png = src_type == "png"
-    make_reader = (lambda: PNGSequenceReader(src_path, width, height)) if png else (lambda: YUV420FileReader(src_path, width, height))
-    to_input = (lambda planes, dt: load_rgb_frame(planes[0], dt)) if png else (lambda planes, dt: load_yuv420_frame(*planes, dt))
+    fmt = PIXEL_FORMATS.get(src_type)          # None: the reference harness's own two source types
+    if fmt is not None:
+        fmt.plane_shapes(height, width)        # (4:2:0 with an odd size is refused here)
+        make_reader = lambda: RawVideoReader(src_path, width, height, fmt)
+        to_input = lambda planes, dt: load_frame(planes, fmt, dt)
+    elif png:
+        make_reader = lambda: PNGSequenceReader(src_path, width, height)
+        to_input = lambda planes, dt: load_rgb_frame(planes[0], dt)
+    else:
+        make_reader = lambda: YUV420FileReader(src_path, width, height)
+        to_input = lambda planes, dt: load_yuv420_frame(*planes, dt)
     import torch
     dev = torch.device(device)
     dtype = next(p_net.parameters()).dtype
@@ -350,6 +432,14 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                 from PIL import Image
                 rgb8 = reconstruct_rgb(x_hat, height, width).float().round().to(torch.uint8).cpu().numpy()
                 Image.fromarray(rgb8.transpose(1, 2, 0)).save(os.path.join(rec_path, "im%s.png" % str(fi + 1).zfill(reader.digits)))
+            continue
+        if fmt is not None:
+            p_, s_ = dm.yuv(x_hat, planes, fmt, calc_ssim) if dm else pixfmt_distortion(x_hat, planes, fmt, calc_ssim)
+            psnrs.append(p_)
+            ssims.append(s_)
+            if rec is not None:     # the source's own format (pipeline.store_frame)
+                for plane in store_frame(x_hat, height, width, fmt):
+                    rec.write(plane.cpu().numpy().tobytes())
             continue
         y, u, v = planes
         if dm:
@@ -411,8 +501,8 @@ def jobs_from_config(config, opts):
     for ds_name, ds in config["test_classes"].items():
         if ds["test"] == 0:
             continue
-        if ds["src_type"] not in ("yuv420", "png"):
-            raise ValueError(f"{ds_name}: src_type {ds['src_type']!r} (the reference harness reads 'yuv420' or 'png')")
+        if ds["src_type"] not in SRC_TYPES:
+            raise ValueError(f"{ds_name}: src_type {ds['src_type']!r} (one of {', '.join(SRC_TYPES)})")
         for seq, info in ds["sequences"].items():
             for rate_idx, (q, qq) in enumerate(zip(qi, qp)):
                 ip = info["intra_period"]
@@ -642,8 +732,9 @@ def build_parser():
                     help="with --stream-path: do not code a point again whose .bin and .json exist (reference --check_existing)")
     ap.add_argument("--save-decoded-frame", "--save_decoded_frame", **flag,
                     help="with --stream-path: write the reconstruction beside the .bin (reference --save_decoded_frame)")
-    ap.add_argument("--src-type", choices=("yuv420", "png"), default="yuv420",
-                    help="--src is a planar 8-bit YUV 4:2:0 file, or a directory of im1.png ... / im00001.png ... (RGB)")
+    ap.add_argument("--src-type", "--src_type", choices=SRC_TYPES, default="yuv420",
+                    help="--src is a planar 8-bit YUV 4:2:0 file (yuv420), a directory of im1.png ... / im00001.png ... (RGB), or a "
+                         "raw file in one of the other formats under its ffmpeg name (10 / 12 / 16 bits, 4:4:4, NV12, P010)")
     ap.add_argument("--src")
     ap.add_argument("--width", type=int)
     ap.add_argument("--height", type=int)

@@ -12,9 +12,10 @@ import torch
 from . import _lib
 from . import nn as L
 from .entropy import PinnedBuffer
-from .harness import _MSSSIM_WEIGHTS, psnr_from_mse
+from .harness import _MSSSIM_WEIGHTS, psnr_from_mse, source_planes
 
-_TYPE = {torch.float16: _lib.F16, torch.float32: _lib.F32, torch.uint8: _lib.U8}
+# (16-bit samples travel as torch.uint16 or as an int16 view of the same words: the kernels read them unsigned)
+_TYPE = {torch.float16: _lib.F16, torch.float32: _lib.F32, torch.uint8: _lib.U8, torch.uint16: _lib.U16, torch.int16: _lib.U16}
 _SLOT = 1 + 2 * 5          # doubles per measured plane pair: the squared error, then (ssim mean, cs mean) per level
 _SLOTS = 4                 # Y, U, V / R, G, B and the whole RGB picture
 
@@ -33,7 +34,7 @@ def _type_code(t):
     try:
         return _TYPE[t.dtype]
     except KeyError:
-        raise _lib.DcvcError(f"unsupported plane dtype {t.dtype}: the metric kernels read uint8, float16 or float32") from None
+        raise _lib.DcvcError(f"unsupported plane dtype {t.dtype}: the metric kernels read uint8, uint16, float16 or float32") from None
 
 
 class DeviceMetrics:
@@ -141,6 +142,47 @@ class DeviceMetrics:
                 levels[k] = self._enqueue_msssim(k, L._p(src), _type_code(src), L._p(r), tr, r.shape[0], r.shape[1], 255, st)
         self._sync(st)
         psnr = [psnr_from_mse(float(self._out[k * _SLOT]) / rec[k].numel()) for k in range(3)]
+        ms = [msssim_from_stats(*self._stats(k, levels[k])) for k in range(3)] if calc_ssim else [0.0, 0.0, 0.0]
+        comb = lambda m: [(6 * m[0] + m[1] + m[2]) / 8] + m
+        return comb(psnr), comb(ms)
+
+    def metric_planes(self, x_hat, height, width, fmt):
+        """decoded [1,3,H',W'] -> the fp32 planes the metrics of a PixelFormat source compare: clip(., 0, 1) * max_val,
+        4:2:0 chroma = the fp32 2x2 mean, NOT rounded - fp32 whatever x_hat's dtype (fp16 cannot hold a 10-bit value with
+        sub-LSB precision).  Enqueued on the current stream; the tensors are this object's buffers."""
+        if not x_hat.is_contiguous():
+            raise ValueError("x_hat must be contiguous")
+        _, _, Hp, Wp = x_hat.shape
+        key = ("pix", height, width, fmt.chroma)
+        planes = self._planes.get(key)
+        if planes is None:
+            ch, cw = (height, width) if fmt.chroma == 444 else (height // 2, width // 2)
+            planes = self._planes[key] = (torch.empty((height, width), dtype=torch.float32, device=self.device),
+                                          torch.empty((ch, cw), dtype=torch.float32, device=self.device),
+                                          torch.empty((ch, cw), dtype=torch.float32, device=self.device))
+        _lib.check(self._lib.dcvc_frame_to_metric_planes(L.dtype_code(x_hat.dtype), fmt.chroma, fmt.max_val, L._p(x_hat), Hp, Wp,
+                                                         height, width, L._p(planes[0]), L._p(planes[1]), L._p(planes[2]),
+                                                         self._stream()), "dcvc_frame_to_metric_planes")
+        return planes
+
+    def yuv(self, x_hat, planes, fmt, calc_ssim=False):
+        """harness.pixfmt_distortion on the device: x_hat [1,3,H',W'] (model dtype), planes: the source's device planes as
+        its reader delivers them (uint8 / uint16; the chroma of NV12 / P010 is de-interleaved and P010's words are
+        shifted down here by harness.source_planes, torch glue on the measuring side) -> (psnr, msssim), each
+        [(6 Y + U + V) / 8, Y, U, V] with data_range = max_val; msssim zeros without calc_ssim"""
+        y, u, v = source_planes(planes, fmt)
+        H, W = y.shape
+        st = self._stream()
+        rec = self.metric_planes(x_hat, H, W, fmt)
+        levels = [0, 0, 0]
+        for k, (src, r) in enumerate(zip((y, u, v), rec)):
+            self._check_pair(src, r)
+            self._enqueue_sse(k, L._p(src), _type_code(src), L._p(r), _lib.F32, r.numel(), st)
+            if calc_ssim:
+                levels[k] = self._enqueue_msssim(k, L._p(src), _type_code(src), L._p(r), _lib.F32, r.shape[0], r.shape[1],
+                                                 fmt.max_val, st)
+        self._sync(st)
+        psnr = [psnr_from_mse(float(self._out[k * _SLOT]) / rec[k].numel(), float(fmt.max_val)) for k in range(3)]
         ms = [msssim_from_stats(*self._stats(k, levels[k])) for k in range(3)] if calc_ssim else [0.0, 0.0, 0.0]
         comb = lambda m: [(6 * m[0] + m[1] + m[2]) / 8] + m
         return comb(psnr), comb(ms)

@@ -257,6 +257,133 @@ def store_yuv420_frame(x_hat, height, width, round_uv=False):
     return y, u, v
 
 
+# ---------------------------------------------------------------------------------- the other raw formats
+@dataclass(frozen=True)
+class PixelFormat:
+    """A raw video format the frame I/O kernels of csrc/dcvc_pixfmt.hip read and write: chroma 420 / 444, bit depth
+    8 .. 16 (little-endian 16-bit words above 8 bits), planar or semi-planar (Y plane + one plane of interleaved (U, V)
+    pairs), value in the low or in the top bits of its word.  PixelFormat.parse(name) knows the ffmpeg spellings below."""
+    name: str
+    chroma: int
+    bit_depth: int
+    semi_planar: bool = False
+    msb_aligned: bool = False
+
+    def __post_init__(self):
+        if self.chroma not in (420, 444) or not 8 <= self.bit_depth <= 16:
+            raise ValueError(f"pixel format {self.name!r}: chroma 420 / 444 and 8 .. 16 bits")
+        if (self.semi_planar and self.chroma != 420) or (self.msb_aligned and self.bit_depth == 8):
+            raise ValueError(f"pixel format {self.name!r}: semi-planar is 4:2:0, msb_aligned needs more than 8 bits")
+
+    @staticmethod
+    def parse(name):
+        """'yuv420p10le', 'yuv444p', 'nv12', 'p010le', ... -> PixelFormat; ValueError for any other name ('yuv420', the
+        8-bit planar 4:2:0 of the reference harness, keeps its own kernels and is not one of these)"""
+        if isinstance(name, PixelFormat):
+            return name
+        try:
+            return PIXEL_FORMATS[name]
+        except (KeyError, TypeError):
+            raise ValueError(f"unknown pixel format {name!r}: one of {', '.join(PIXEL_FORMATS)}") from None
+
+    @property
+    def max_val(self):
+        return (1 << self.bit_depth) - 1
+
+    @property
+    def sample_bytes(self):
+        return 2 if self.bit_depth > 8 else 1
+
+    @property
+    def numpy_dtype(self):
+        import numpy as np
+        return np.dtype("<u2") if self.bit_depth > 8 else np.dtype(np.uint8)
+
+    @property
+    def torch_dtype(self):
+        import torch
+        return torch.uint16 if self.bit_depth > 8 else torch.uint8
+
+    def plane_shapes(self, height, width):
+        """shapes of a frame's planes in file order: (y, u, v), or (y, uv) with uv [H/2, W] interleaved for semi-planar"""
+        if self.chroma == 420 and (height % 2 or width % 2):
+            raise ValueError(f"{self.name}: 4:2:0 needs an even height and width (got {width}x{height})")
+        if self.chroma == 444:
+            return ((height, width),) * 3
+        if self.semi_planar:
+            return ((height, width), (height // 2, width))
+        return ((height, width), (height // 2, width // 2), (height // 2, width // 2))
+
+    def frame_bytes(self, height, width):
+        return sum(h * w for h, w in self.plane_shapes(height, width)) * self.sample_bytes
+
+
+PIXEL_FORMATS = {f.name: f for f in (
+    [PixelFormat(f"yuv420p{b}le", 420, b) for b in (10, 12, 16)] + [PixelFormat("yuv444p", 444, 8)] +
+    [PixelFormat(f"yuv444p{b}le", 444, b) for b in (10, 12, 16)] +
+    [PixelFormat("nv12", 420, 8, semi_planar=True), PixelFormat("p010le", 420, 10, semi_planar=True, msb_aligned=True)])}
+
+
+def _plane_args(planes, fmt, height, width, strides):
+    """(y, u_or_uv, v_or_None pointers, y_stride, c_stride) for the library; strides in samples (default: tight)"""
+    import ctypes
+    shapes = fmt.plane_shapes(height, width)
+    if len(planes) != len(shapes):
+        raise ValueError(f"{fmt.name}: {len(shapes)} planes expected, got {len(planes)}")
+    for p in planes:
+        if p.element_size() != fmt.sample_bytes:
+            raise ValueError(f"{fmt.name}: planes of {fmt.sample_bytes}-byte samples expected, got {p.dtype}")
+    ys, cs = strides if strides is not None else (shapes[0][1], shapes[1][1])
+    ptrs = [ctypes.c_void_p(p.data_ptr()) for p in planes] + [None] * (3 - len(planes))
+    return ptrs, int(ys), int(cs)
+
+
+def load_frame(planes, fmt, dtype, pad_to=16, height=None, width=None, strides=None):
+    """device planes of a PixelFormat -> padded model input [1,3,H',W'] (one kernel: sample / max_val as an fp32
+    division, one rounding to `dtype`, nearest chroma up-sampling for 4:2:0, replicate pad - the reference family's
+    YUVReader + ycbcr420_to_444 + this project's cast and replicate_pad).  planes: (y, u, v), or (y, uv) for semi-planar;
+    uint8, or torch.uint16 / an int16 view above 8 bits.  strides=(y_stride, c_stride) in samples with height / width
+    given reads pitched surfaces (flat or wider tensors) in place; by default the planes are tight [H, W] tensors."""
+    import ctypes
+    import torch
+    from . import _lib
+    from . import nn as L
+    fmt = PixelFormat.parse(fmt)
+    if strides is None:
+        planes = [p.contiguous() for p in planes]
+        height, width = planes[0].shape
+    if pad_to % 8:
+        raise ValueError("pad_to must be a multiple of 8 (the kernels store 8 pixels at a time)")
+    ptrs, ys, cs = _plane_args(planes, fmt, height, width, strides)
+    pr, pb = (-width) % pad_to, (-height) % pad_to
+    out = torch.empty((1, 3, height + pb, width + pr), dtype=dtype, device=planes[0].device)
+    _lib.check(_lib.lib().dcvc_planes_to_frame(L.dtype_code(dtype), fmt.chroma, fmt.bit_depth, int(fmt.semi_planar),
+                                               int(fmt.msb_aligned), *ptrs, ys, cs, height, width, pb, pr, L._p(out),
+                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               "dcvc_planes_to_frame")
+    return out
+
+
+def store_frame(x_hat, height, width, fmt):
+    """decoded [1,3,H',W'] -> the device planes of the height x width picture in `fmt` ((y, u, v), or (y, uv) for
+    semi-planar; uint8 / torch.uint16): crop, fp32, 4:2:0 chroma = 2x2 mean, clip(., 0, 1) * max_val, round to nearest
+    even, clip (the reference family's ycbcr444_to_420 + YUVWriter), shifted up for msb-aligned formats."""
+    import ctypes
+    import torch
+    from . import _lib
+    from . import nn as L
+    fmt = PixelFormat.parse(fmt)
+    x = x_hat.contiguous()
+    _, _, Hp, Wp = x.shape
+    planes = [torch.empty(s, dtype=fmt.torch_dtype, device=x.device) for s in fmt.plane_shapes(height, width)]
+    ptrs, ys, cs = _plane_args(planes, fmt, height, width, None)
+    _lib.check(_lib.lib().dcvc_frame_to_planes(L.dtype_code(x.dtype), fmt.chroma, fmt.bit_depth, int(fmt.semi_planar),
+                                               int(fmt.msb_aligned), L._p(x), Hp, Wp, height, width, *ptrs, ys, cs,
+                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               "dcvc_frame_to_planes")
+    return tuple(planes)
+
+
 def use_two_entropy_coders(height, width):
     """test_video.py:152"""
     return height * width > 1280 * 720
