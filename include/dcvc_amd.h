@@ -222,6 +222,15 @@ int dcvc_prior_dec_index_compact(int dtype, int n_groups, int step, const void* 
 int dcvc_prior_dec_restore_compact(int dtype, int n_groups, int step, const int8_t* sym_host, const uint8_t* idx_chw,
                                    void* workspace, const void* means, int64_t ldm, int H, int W, int C,
                                    const void* yhat_in, int64_t ldhi, void* yhat_out, int64_t ldho, void* stream);
+/* The same two calls with the hand-off left in DEVICE memory (the device entropy coder, dcvc_rans_dev_decode_y, sits between
+ * them): idx_dev receives the kept indexes (one byte per position rounded up to 16), *count_dev their number; sym_dev holds
+ * the decoded symbols in the same order.  Nothing crosses the host link and the host never learns the count. */
+int dcvc_prior_dec_index_compact_dev(int dtype, int n_groups, int step, const void* scales, int64_t lds_, int H, int W, int C,
+                                     float thres, uint8_t* idx_chw, void* workspace, uint8_t* idx_dev,
+                                     int32_t* count_dev, void* stream);
+int dcvc_prior_dec_restore_compact_dev(int dtype, int n_groups, int step, const int8_t* sym_dev, const uint8_t* idx_chw,
+                                       void* workspace, const void* means, int64_t ldm, int H, int W, int C,
+                                       const void* yhat_in, int64_t ldhi, void* yhat_out, int64_t ldho, void* stream);
 /* y_hat = y_hat * q   q_mode 0: max(qdec,0.5) per element; q_mode 1: sigmoid(qraw[p][1])*1.5+0.5
  * add_and_multiply (cuda_inference.py:48-55), common_model.py:246,294 */
 int dcvc_prior_finish(int dtype, int q_mode, void* yhat, int64_t ldh, const void* qsrc, int64_t ldq,
@@ -321,6 +330,17 @@ int dcvc_rans_dec_decode_compact(dcvc_rans_dec*, const uint8_t* indexes, int64_t
  * corrupt or truncated payload into garbage, rans.cpp:356-429): a rANS decoder that has undone every encoder step is back
  * in the encoder's initial state and has consumed every byte; returns 0, or -4 with dcvc_last_error() set. */
 int dcvc_rans_dec_check_end(dcvc_rans_dec*);
+/* Chunked y units: this project's stream extension (docs/chunked_stream.md; NOT readable by the reference).  A unit codes
+ * `count` KEPT symbols (no sentinels) in chunks of S = 1 << log2_s (8 .. 12) symbols: ceil(count / S) little-endian uint16
+ * chunk byte lengths, then the chunk bodies, each an independent stream of the coder above (what reset(); encode_y(chunk);
+ * flush() of one coder writes).  The coder objects only supply their table groups; set_use_two does not apply.
+ *   encode: symbols (sym << 8) | index -> out[0 .. capacity); returns the unit's bytes, or a negative error code.
+ *   decode: out[0 .. count) from the unit and the symbols' table indexes; -4 (dcvc_last_error() set) if the length table
+ *     does not match unit_bytes / count or a chunk does not end on its last byte in the coder's initial state. */
+int64_t dcvc_rans_chunked_encode_y(dcvc_rans_enc*, const int16_t* symbols, int64_t count, int group, int log2_s,
+                                   uint8_t* out, int64_t capacity);
+int dcvc_rans_chunked_decode_y(dcvc_rans_dec*, const uint8_t* unit, int64_t unit_bytes, const uint8_t* indexes,
+                               int64_t count, int group, int log2_s, int8_t* out);
 /* pmf_to_quantized_cdf (py_rans.cpp:307-364); out holds n+1 entries */
 int dcvc_pmf_to_quantized_cdf(const float* pmf, int n, int precision, uint32_t* out);
 
@@ -338,6 +358,46 @@ void* dcvc_host_device_ptr(void* host);
 #define DCVC_COMPACT_BLOCKS 256
 int dcvc_compact_symbols(const int16_t* packed, int n_per_part, int n_parts, int16_t* out_host, int32_t* counts_host,
                          int32_t* workspace, void* stream);
+/* dcvc_compact_symbols with the output left in DEVICE memory (input of dcvc_rans_dev_encode_y) */
+int dcvc_compact_symbols_dev(const int16_t* packed, int n_per_part, int n_parts, int16_t* out_dev, int32_t* counts_dev,
+                             int32_t* workspace, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Device entropy coder of the chunked y units (csrc/dcvc_rans_dev.hip): one lane codes one chunk, so a unit is encoded
+ * and decoded by kernels enqueued on the caller's stream, with no host step and no host read of the symbol count.
+ * Bytes and symbols are exactly those of dcvc_rans_chunked_encode_y / _decode_y.
+ *   create: device tables of one cdf group (arguments as dcvc_rans_enc_add_cdf).  n a multiple of 4 and
+ *     n * (stride + 21) <= 6144: 24 KB of tables beside the decoder's 40 KB of staged input in LDS; the 128 Gaussian
+ *     tables take 20 KB.
+ *   encode: sym_dev[0 .. *count_dev) (count <= max_symbols, both device) -> the unit in pinned host memory at
+ *     unit_host + 16, preceded by int32 info[4] = {unit bytes, overflow flag, count, chunks}.  A chunk is built in a
+ *     scratch slot of slot_bytes (a multiple of 4; 0 = the default, 2 * S + 64: two bytes is the worst case of a
+ *     table-coded symbol, 4 of the 64 are the flush); a chunk that does not fit its slot, or a unit that does not fit
+ *     unit_capacity, raises the overflow flag instead of writing - the unit bytes are then undefined and the caller
+ *     encodes on the host.
+ *     workspace: device, 16-byte aligned, dcvc_rans_dev_enc_ws_bytes(max_symbols, log2_s, slot_bytes) bytes.
+ *   decode: the unit at payload_dev + unit_desc_dev[0], unit_desc_dev[1] bytes long (device int32 pair, so a captured
+ *     launch serves every frame), must lie inside payload_dev[0 .. payload_capacity) (4-byte aligned).
+ *     idx_dev[0 .. *count_dev) are the symbols' table indexes; sym_dev receives the symbols.  No byte outside a
+ *     lane's chunk is ever used (a read past its end yields zero and marks the chunk); a damaged unit ORs
+ *     DCVC_RANS_DEV_E_* bits into *error_host (pinned, the caller clears and reads it) and writes nothing else.
+ *     workspace: device, 16-byte aligned, dcvc_rans_dev_dec_ws_bytes(max_symbols, log2_s) bytes. */
+#define DCVC_RANS_DEV_E_COUNT 1   /* the symbol count needs a longer length table than the unit has */
+#define DCVC_RANS_DEV_E_TABLE 2   /* the length table does not add up to the unit's bytes */
+#define DCVC_RANS_DEV_E_CHUNK 4   /* a chunk does not end on its last byte in the coder's initial state */
+#define DCVC_RANS_DEV_E_RANGE 8   /* the unit lies outside the payload buffer / a table index outside the group */
+typedef struct dcvc_rans_dev dcvc_rans_dev;
+int dcvc_rans_dev_create(const int32_t* cdf, int n, int stride, const int32_t* sizes, const int32_t* offsets,
+                         dcvc_rans_dev** out);
+void dcvc_rans_dev_destroy(dcvc_rans_dev*);
+int64_t dcvc_rans_dev_enc_ws_bytes(int64_t max_symbols, int log2_s, int slot_bytes);
+int dcvc_rans_dev_encode_y(const dcvc_rans_dev*, const int16_t* sym_dev, const int32_t* count_dev, int64_t max_symbols,
+                           int log2_s, int slot_bytes, void* workspace, uint8_t* unit_host, int64_t unit_capacity,
+                           void* stream);
+int64_t dcvc_rans_dev_dec_ws_bytes(int64_t max_symbols, int log2_s);
+int dcvc_rans_dev_decode_y(const dcvc_rans_dev*, const uint8_t* payload_dev, int64_t payload_capacity,
+                           const int32_t* unit_desc_dev, const uint8_t* idx_dev, const int32_t* count_dev,
+                           int64_t max_symbols, int log2_s, void* workspace, int8_t* sym_dev, int32_t* error_host,
+                           void* stream);
 /* ------------------------------------------------------------------------------------------
  * Distortion metrics of a decoded frame on the device (the reference computes them on the host from copied planes:
  * test_video.py:94-127 get_distortion, src/utils/metrics.py).  fp64 arithmetic, fixed reduction order.  Results are

@@ -116,6 +116,17 @@ _SIGS = {
     "dcvc_rans_dec_decode_compact": (_I, [_P, _P, _L, _I, _P]),
     "dcvc_rans_dec_check_end": (_I, [_P]),
     "dcvc_pmf_to_quantized_cdf": (_I, [_P, _I, _I, _P]),
+    "dcvc_rans_chunked_encode_y": (_L, [_P, _P, _L, _I, _I, _P, _L]),
+    "dcvc_rans_chunked_decode_y": (_I, [_P, _P, _L, _P, _L, _I, _I, _P]),
+    "dcvc_rans_dev_create": (_I, [_P, _I, _I, _P, _P, POINTER(_P)]),
+    "dcvc_rans_dev_destroy": (None, [_P]),
+    "dcvc_rans_dev_enc_ws_bytes": (_L, [_L, _I, _I]),
+    "dcvc_rans_dev_encode_y": (_I, [_P, _P, _P, _L, _I, _I, _P, _P, _L, _P]),
+    "dcvc_rans_dev_dec_ws_bytes": (_L, [_L, _I]),
+    "dcvc_rans_dev_decode_y": (_I, [_P, _P, _L, _P, _P, _P, _L, _I, _P, _P, _P, _P]),
+    "dcvc_prior_dec_index_compact_dev": (_I, [_I, _I, _I, _P, _L, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "dcvc_prior_dec_restore_compact_dev": (_I, [_I, _I, _I, _P, _P, _P, _P, _L, _I, _I, _I, _P, _L, _P, _L, _P]),
+    "dcvc_compact_symbols_dev": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "dcvc_host_alloc": (_P, [c_size_t]),
     "dcvc_host_free": (None, [_P]),
     "dcvc_host_device_ptr": (_P, [_P]),

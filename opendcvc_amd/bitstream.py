@@ -8,6 +8,7 @@ binary file-like object (io.BytesIO, open(..., 'wb')).
 Layout:  NAL header byte = type(4 bits) | sps_id(4 bits)
   SPS :  header, height (varint), width (varint), flags = ec_part << 2 | use_ada_i
   I/P :  header, qp (1 byte), payload length (varint), payload (the rANS stream of the frame)
+         (types 3 / 4 = I / P with a chunked payload: this project's extension, docs/chunked_stream.md)
 varint:  0xxxxxxx                      value < 2**7
          10xxxxxx xxxxxxxx             value < 2**14   (big endian)
          11xxxxxx + 3 bytes            value < 2**30   (big endian)
@@ -19,6 +20,10 @@ class NalType(enum.IntEnum):
     NAL_SPS = 0
     NAL_I = 1
     NAL_P = 2
+    # this project's extension (docs/chunked_stream.md), not readable by the reference: same NAL layout, the payload carries
+    # the y symbols in independent chunks that the GPU entropy-codes
+    NAL_I_CHUNKED = 3
+    NAL_P_CHUNKED = 4
 
 
 def write_uint_adaptive(f, value):
@@ -109,10 +114,14 @@ def read_sps_remaining(f, sps_id):
     return {"sps_id": sps_id, "height": height, "width": width, "ec_part": (flag >> 2) & 1, "use_ada_i": flag & 1}
 
 
-def write_ip(f, is_i_frame, sps_id, qp, bit_stream):
+def write_ip(f, is_i_frame, sps_id, qp, bit_stream, chunked=False):
     if not 0 <= qp < 256:
         raise ValueError(f"qp {qp} out of range")
-    f.write(bytes(((int(NalType.NAL_I if is_i_frame else NalType.NAL_P) << 4) | sps_id, qp)))
+    if chunked:
+        nal = NalType.NAL_I_CHUNKED if is_i_frame else NalType.NAL_P_CHUNKED
+    else:
+        nal = NalType.NAL_I if is_i_frame else NalType.NAL_P
+    f.write(bytes(((int(nal) << 4) | sps_id, qp)))
     n = 2 + write_uint_adaptive(f, len(bit_stream))
     f.write(bit_stream)
     return n + len(bit_stream)
@@ -140,15 +149,17 @@ class StreamWriter:
         sps_id, is_new = self.sps_helper.get_sps_id(sps)
         sps["sps_id"] = sps_id
         n = write_sps(self.f, sps) if is_new else 0
-        return n + write_ip(self.f, pkt.is_i, sps_id, pkt.qp, pkt.bit_stream)
+        return n + write_ip(self.f, pkt.is_i, sps_id, pkt.qp, pkt.bit_stream, chunked=getattr(pkt, "chunked", False))
 
 
 class StreamReader:
-    """test_video.py:265-276: yields (sps, is_i_frame, qp, payload) per frame."""
+    """test_video.py:265-276: yields (sps, is_i_frame, qp, payload) per frame; `chunked` tells whether the frame returned
+    last carries a chunked payload (NAL_I_CHUNKED / NAL_P_CHUNKED)."""
 
     def __init__(self, f):
         self.f = f
         self.sps_helper = SPSHelper()
+        self.chunked = False
 
     def read_frame(self):
         header = read_header(self.f)
@@ -159,4 +170,5 @@ class StreamReader:
         if sps is None:
             raise ValueError(f"frame refers to unknown SPS {header['sps_id']}")
         qp, payload = read_ip_remaining(self.f)
-        return sps, header["nal_type"] == NalType.NAL_I, qp, payload
+        self.chunked = header["nal_type"] in (NalType.NAL_I_CHUNKED, NalType.NAL_P_CHUNKED)
+        return sps, header["nal_type"] in (NalType.NAL_I, NalType.NAL_I_CHUNKED), qp, payload

@@ -1066,9 +1066,10 @@ int64_t dcvc_prior_dec_compact_ws_bytes(int H, int W, int C, int n_groups)
     return dec_ws(H, W, C, n_groups).bytes;
 }
 
-int dcvc_prior_dec_index_compact(int dtype, int n_groups, int step, const void* scales, int64_t lds_, int H, int W, int C,
-                                 float thres, uint8_t* idx_chw, void* workspace, uint8_t* idx_host, int32_t* count_host,
-                                 void* stream)
+// pinned: idx_host / count_host are dcvc_host_alloc buffers (the public form); else device memory (the _dev form)
+static int prior_dec_index_compact_impl(int dtype, int n_groups, int step, const void* scales, int64_t lds_, int H, int W, int C,
+                                        float thres, uint8_t* idx_chw, void* workspace, uint8_t* idx_host, int32_t* count_host,
+                                        void* stream, bool pinned)
 {
     DCVC_REQUIRE(scales && idx_chw && workspace && idx_host && count_host, "dcvc_prior_dec_index_compact: null pointer");
     DCVC_REQUIRE((int64_t)H * W < (1ll << 31), "dcvc_prior_dec_index_compact: map too large");
@@ -1079,10 +1080,12 @@ int dcvc_prior_dec_index_compact(int dtype, int n_groups, int step, const void* 
     DCVC_REQUIRE(w.n < (1ll << 31), "dcvc_prior_dec_index_compact: too many symbols");
     char* ws = (char*)workspace;
     uint8_t* cnt16 = (uint8_t*)(ws + w.off_cnt16);
-    uint8_t* out_dev = nullptr;
-    int32_t* count_dev = nullptr;
-    DCVC_HIP(hipHostGetDevicePointer((void**)&out_dev, idx_host, 0));
-    DCVC_HIP(hipHostGetDevicePointer((void**)&count_dev, count_host, 0));
+    uint8_t* out_dev = idx_host;
+    int32_t* count_dev = count_host;
+    if (pinned) {
+        DCVC_HIP(hipHostGetDevicePointer((void**)&out_dev, idx_host, 0));
+        DCVC_HIP(hipHostGetDevicePointer((void**)&count_dev, count_host, 0));
+    }
     const size_t lds = (size_t)(C / n_groups) * PT;
     int rc = typed(dtype, [&](auto tag) {
         using T = decltype(tag);
@@ -1096,31 +1099,70 @@ int dcvc_prior_dec_index_compact(int dtype, int n_groups, int step, const void* 
     return 0;
 }
 
-int dcvc_prior_dec_restore_compact(int dtype, int n_groups, int step, const int8_t* sym_host, const uint8_t* idx_chw,
-                                   void* workspace, const void* means, int64_t ldm, int H, int W, int C,
-                                   const void* yhat_in, int64_t ldhi, void* yhat_out, int64_t ldho, void* stream)
+int dcvc_prior_dec_index_compact(int dtype, int n_groups, int step, const void* scales, int64_t lds_, int H, int W, int C,
+                                 float thres, uint8_t* idx_chw, void* workspace, uint8_t* idx_host, int32_t* count_host,
+                                 void* stream)
 {
-    DCVC_REQUIRE(sym_host && idx_chw && workspace && means && yhat_out, "dcvc_prior_dec_restore_compact: null pointer");
+    return prior_dec_index_compact_impl(dtype, n_groups, step, scales, lds_, H, W, C, thres, idx_chw, workspace, idx_host,
+                                        count_host, stream, true);
+}
+
+int dcvc_prior_dec_index_compact_dev(int dtype, int n_groups, int step, const void* scales, int64_t lds_, int H, int W, int C,
+                                     float thres, uint8_t* idx_chw, void* workspace, uint8_t* idx_dev, int32_t* count_dev,
+                                     void* stream)
+{
+    return prior_dec_index_compact_impl(dtype, n_groups, step, scales, lds_, H, W, C, thres, idx_chw, workspace, idx_dev,
+                                        count_dev, stream, false);
+}
+
+// pinned: `sym` is a dcvc_host_alloc buffer the host coder filled (the public form: the symbols are fetched into the workspace
+// first); else they are in device memory already (the _dev form, written by dcvc_rans_dev_decode_y: no gather)
+static int prior_dec_restore_compact_impl(int dtype, int n_groups, int step, const int8_t* sym, const uint8_t* idx_chw,
+                                          void* workspace, const void* means, int64_t ldm, int H, int W, int C,
+                                          const void* yhat_in, int64_t ldhi, void* yhat_out, int64_t ldho, void* stream,
+                                          bool pinned)
+{
+    DCVC_REQUIRE(sym && idx_chw && workspace && means && yhat_out, "dcvc_prior_dec_restore_compact: null pointer");
     DCVC_REQUIRE((int64_t)H * W < (1ll << 31), "dcvc_prior_dec_restore_compact: map too large");
     DCVC_REQUIRE((n_groups == 2 || n_groups == 4) && step >= 0 && step < n_groups && C % n_groups == 0,
                  "dcvc_prior_dec_restore_compact: bad groups/step");
     DCVC_REQUIRE(step == 0 || yhat_in, "dcvc_prior_dec_restore_compact: yhat_in required after step 0");
     const DecWs w = dec_ws(H, W, C, n_groups);
     char* ws = (char*)workspace;
-    const int8_t* src_dev = nullptr;
-    DCVC_HIP(hipHostGetDevicePointer((void**)&src_dev, (void*)sym_host, 0));
-    DCVC_REQUIRE((reinterpret_cast<uintptr_t>(src_dev) & 15) == 0, "dcvc_prior_dec_restore_compact: symbol buffer must be 16-byte aligned");
-    const int cap16 = (int)((w.n + 15) / 16);
-    hipLaunchKernelGGL(dec_gather_kernel, dim3((cap16 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint4*)src_dev,
-                       (uint4*)(ws + w.off_csym), (const int32_t*)ws, cap16);
-    DCVC_LAUNCH_CHECK();
+    const int8_t* csym = sym;
+    if (pinned) {
+        const int8_t* src_dev = nullptr;
+        DCVC_HIP(hipHostGetDevicePointer((void**)&src_dev, (void*)sym, 0));
+        DCVC_REQUIRE((reinterpret_cast<uintptr_t>(src_dev) & 15) == 0, "dcvc_prior_dec_restore_compact: symbol buffer must be 16-byte aligned");
+        const int cap16 = (int)((w.n + 15) / 16);
+        hipLaunchKernelGGL(dec_gather_kernel, dim3((cap16 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint4*)src_dev,
+                           (uint4*)(ws + w.off_csym), (const int32_t*)ws, cap16);
+        DCVC_LAUNCH_CHECK();
+        csym = (const int8_t*)(ws + w.off_csym);
+    }
     const size_t lds = (size_t)(C / n_groups) * 8;
     return typed(dtype, [&](auto tag) {
         using T = decltype(tag);
         prior_dec_restore_compact_kernel<T><<<w.nblk, EB, lds, (hipStream_t)stream>>>(n_groups, step,
-                                    (const int8_t*)(ws + w.off_csym), idx_chw, (const uint32_t*)(ws + w.off_off16),
+                                    csym, idx_chw, (const uint32_t*)(ws + w.off_off16),
                                     (const T*)means, ldm, H, W, C, (const T*)yhat_in, ldhi, (T*)yhat_out, ldho);
     });
+}
+
+int dcvc_prior_dec_restore_compact(int dtype, int n_groups, int step, const int8_t* sym_host, const uint8_t* idx_chw,
+                                   void* workspace, const void* means, int64_t ldm, int H, int W, int C,
+                                   const void* yhat_in, int64_t ldhi, void* yhat_out, int64_t ldho, void* stream)
+{
+    return prior_dec_restore_compact_impl(dtype, n_groups, step, sym_host, idx_chw, workspace, means, ldm, H, W, C, yhat_in, ldhi,
+                                          yhat_out, ldho, stream, true);
+}
+
+int dcvc_prior_dec_restore_compact_dev(int dtype, int n_groups, int step, const int8_t* sym_dev, const uint8_t* idx_chw,
+                                       void* workspace, const void* means, int64_t ldm, int H, int W, int C,
+                                       const void* yhat_in, int64_t ldhi, void* yhat_out, int64_t ldho, void* stream)
+{
+    return prior_dec_restore_compact_impl(dtype, n_groups, step, sym_dev, idx_chw, workspace, means, ldm, H, W, C, yhat_in, ldhi,
+                                          yhat_out, ldho, stream, false);
 }
 
 int dcvc_prior_finish(int dtype, int q_mode, void* yhat, int64_t ldh, const void* qsrc, int64_t ldq, int H, int W, int C,
@@ -1312,22 +1354,36 @@ int dcvc_op_bias_wsilu_depthwise_conv2d(int dtype, const void* x, const void* we
     });
 }
 
-int dcvc_compact_symbols(const int16_t* packed, int n_per_part, int n_parts, int16_t* out_host, int32_t* counts_host,
-                         int32_t* workspace, void* stream)
+static int compact_symbols_impl(const int16_t* packed, int n_per_part, int n_parts, int16_t* out_host, int32_t* counts_host,
+                                int32_t* workspace, void* stream, bool pinned)
 {
     DCVC_REQUIRE(packed && out_host && counts_host && workspace, "dcvc_compact_symbols: null pointer");
     DCVC_REQUIRE(n_per_part > 0 && n_parts > 0 && n_parts <= 8, "dcvc_compact_symbols: bad sizes %d x %d", n_parts, n_per_part);
     const int nb = DCVC_COMPACT_BLOCKS, seg = (n_per_part + nb - 1) / nb;
     hipStream_t st = (hipStream_t)stream;
-    int16_t* out_dev = nullptr;
-    int32_t* counts_dev = nullptr;
-    DCVC_HIP(hipHostGetDevicePointer((void**)&out_dev, out_host, 0));
-    DCVC_HIP(hipHostGetDevicePointer((void**)&counts_dev, counts_host, 0));
+    int16_t* out_dev = out_host;
+    int32_t* counts_dev = counts_host;
+    if (pinned) {
+        DCVC_HIP(hipHostGetDevicePointer((void**)&out_dev, out_host, 0));
+        DCVC_HIP(hipHostGetDevicePointer((void**)&counts_dev, counts_host, 0));
+    }
     hipLaunchKernelGGL(compact_count_kernel, dim3(nb, n_parts), dim3(CB), 0, st, packed, n_per_part, seg, workspace);
     hipLaunchKernelGGL(compact_scatter_kernel, dim3(nb, n_parts), dim3(CB), 0, st, packed, n_per_part, seg, workspace, out_dev,
                        counts_dev);
     DCVC_LAUNCH_CHECK();
     return 0;
+}
+
+int dcvc_compact_symbols(const int16_t* packed, int n_per_part, int n_parts, int16_t* out_host, int32_t* counts_host,
+                         int32_t* workspace, void* stream)
+{
+    return compact_symbols_impl(packed, n_per_part, n_parts, out_host, counts_host, workspace, stream, true);
+}
+
+int dcvc_compact_symbols_dev(const int16_t* packed, int n_per_part, int n_parts, int16_t* out_dev, int32_t* counts_dev,
+                             int32_t* workspace, void* stream)
+{
+    return compact_symbols_impl(packed, n_per_part, n_parts, out_dev, counts_dev, workspace, stream, false);
 }
 
 int dcvc_copy_f32(float* dst, const float* src, int n, void* stream)

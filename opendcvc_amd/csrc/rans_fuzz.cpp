@@ -4,7 +4,8 @@
 // The reference decodes a corrupt or truncated payload into garbage without any check
 // (src/cpp/py_rans/rans.cpp:356-429 reads past the vector's end through a raw pointer); the drop-in must not read out of
 // bounds and must say so: every decode call returns 0 or -4 (E_STREAM), dcvc_rans_dec_check_end() fails on every damaged
-// stream, and the sanitizers see no invalid access / undefined behaviour on the way.
+// stream, and the sanitizers see no invalid access / undefined behaviour on the way.  The chunked y units
+// (dcvc_rans_chunked_encode_y / _decode_y) get the same treatment in chunked_round().
 //
 //   rans_fuzz_asan [rounds]      exit code 0 = all properties held
 #include <cstdint>
@@ -194,12 +195,73 @@ int decode(dcvc_rans_dec* d, const std::vector<uint8_t>& s, const Frame& f, int 
     return worst;
 }
 
+
+// The chunked y units (dcvc_rans_chunked_encode_y / _decode_y): exact round trip, every truncation, every bit of the length
+// table, bit flips in the bodies, a count that needs a longer table than the unit has - each damaged unit is refused with -4
+// (or, for a flip inside an escape's verbatim bits, decodes to other ESCAPED values only) and no read leaves the exact-size block.
+void chunked_round(Rng& r, dcvc_rans_enc* e, dcvc_rans_dec* d, const Tables& yt, const Frame& f, int yg, int round, long* n_cases)
+{
+    std::vector<int16_t> kept;
+    for (int16_t v : f.y[0])
+        if ((v & 0xff) != 0xff) kept.push_back(v);
+    const int log2_s = 8 + round % 3;
+    const int64_t n = (int64_t)kept.size(), S = 1ll << log2_s, nch = (n + S - 1) / S;
+    std::vector<uint8_t> unit((size_t)(4 * n + 6 * nch + 16));
+    const int64_t ub = dcvc_rans_chunked_encode_y(e, kept.data(), n, yg, log2_s, unit.data(), (int64_t)unit.size());
+    EXPECT(ub >= 2 * nch + 4 * nch, "round %d: chunked encode returned %lld: %s", round, (long long)ub, dcvc_last_error());
+    if (ub < 0) return;
+    EXPECT(dcvc_rans_chunked_encode_y(e, kept.data(), n, yg, log2_s, unit.data(), ub - 1) == -1 || n == 0, "short output accepted");
+    EXPECT(dcvc_rans_chunked_encode_y(e, kept.data(), n, yg, 7, unit.data(), ub) == -1, "chunk size 128 accepted");
+    unit.resize((size_t)ub);
+    std::vector<uint8_t> idx((size_t)n);
+    for (int64_t i = 0; i < n; ++i) idx[(size_t)i] = (uint8_t)(kept[(size_t)i] & 0xff);
+    std::vector<int8_t> out((size_t)n + 1);
+    auto run = [&](const std::vector<uint8_t>& u, int64_t count, bool* plain) {
+        std::vector<uint8_t> t(u);
+        t.shrink_to_fit();                       // exact-size heap block: ASan sees a read past the unit
+        const int rc = dcvc_rans_chunked_decode_y(d, t.data(), (int64_t)t.size(), idx.data(), count, yg, log2_s, out.data());
+        EXPECT(rc == 0 || rc == -4, "round %d: chunked decode rc %d", round, rc);
+        *plain = false;
+        if (rc == 0)
+            for (int64_t i = 0; i < count; ++i) {
+                const int want = (int8_t)(kept[(size_t)i] >> 8);
+                if (out[(size_t)i] != want && !is_escape(yt, idx[(size_t)i], want)) *plain = true;
+            }
+        ++*n_cases;
+        return rc;
+    };
+    bool plain = false;
+    EXPECT(run(unit, n, &plain) == 0 && !plain, "round %d: intact chunked unit does not round-trip: %s", round, dcvc_last_error());
+    for (int64_t i = 0; i < n; ++i) EXPECT(out[(size_t)i] == (int8_t)(kept[(size_t)i] >> 8), "round %d: symbol %lld", round, (long long)i);
+    for (size_t cut = 0; cut < unit.size(); cut += (cut < 24 || unit.size() - cut < 24) ? 1 : 1 + r.below(61))
+        EXPECT(run(std::vector<uint8_t>(unit.begin(), unit.begin() + cut), n, &plain) == -4, "round %d: unit cut to %zu accepted", round, cut);
+    {
+        std::vector<uint8_t> t(unit);
+        t.push_back(0);
+        EXPECT(run(t, n, &plain) == -4, "round %d: trailing byte accepted", round);
+    }
+    for (int64_t b = 0; b < 2 * nch * 8; ++b) {  // every bit of the length table
+        std::vector<uint8_t> t(unit);
+        t[(size_t)(b >> 3)] ^= (uint8_t)(1u << (b & 7));
+        EXPECT(run(t, n, &plain) == -4, "round %d: length table bit %lld flipped, accepted", round, (long long)b);
+    }
+    for (int k = 0; k < 200 && ub > 2 * nch; ++k) {
+        std::vector<uint8_t> t(unit);
+        t[(size_t)(2 * nch + r.below((int)(ub - 2 * nch)))] ^= (uint8_t)(1u << r.below(8));
+        const int rc = run(t, n, &plain);
+        EXPECT(rc == -4 || !plain, "round %d: body flip %d: wrong table-coded symbols accepted", round, k);
+    }
+    // a count whose length table is longer than the whole unit, and counts that disagree with the table
+    EXPECT(n == 0 || run(std::vector<uint8_t>(unit.begin(), unit.begin() + (nch > 1 ? 2 * nch - 1 : 1)), n, &plain) == -4, "long table accepted");
+    if (nch > 1) EXPECT(run(unit, n - S, &plain) == -4, "round %d: a chunk too few accepted", round);
+    EXPECT(dcvc_rans_chunked_decode_y(d, unit.data(), ub, idx.data(), n, yg + 7, log2_s, out.data()) == -1, "unknown group accepted");
+}
 }  // namespace
 
 int main(int argc, char** argv)
 {
     const int rounds = argc > 1 ? std::atoi(argv[1]) : 24;
-    long n_trunc = 0, n_flip = 0, n_caught_by_decode = 0, n_escape_only = 0;
+    long n_trunc = 0, n_flip = 0, n_caught_by_decode = 0, n_escape_only = 0, n_chunked = 0;
     for (int round = 0; round < rounds; ++round) {
         Rng r(1000 + round);
         const bool two = round & 1;
@@ -259,6 +321,8 @@ int main(int argc, char** argv)
             n_escape_only += end_rc == 0 && !same;
             ++n_flip;
         }
+        // 3b. the chunked units of the same symbols
+        chunked_round(r, e, d, yt, f, yg, round, &n_chunked);
         // 4. argument errors stay errors
         EXPECT(dcvc_rans_dec_set_stream(d, s.data(), 3) == -1, "short stream accepted");
         EXPECT(dcvc_rans_dec_set_stream(d, nullptr, 16) == -1, "null stream accepted");
@@ -277,7 +341,7 @@ int main(int argc, char** argv)
         dcvc_rans_dec_destroy(d);
     }
     std::printf("rans_fuzz: %d rounds, %ld truncations (%ld already refused by a decode call), %ld bit-flip streams (%ld of them "
-                "changed only the verbatim bits of escaped values = valid streams of another frame), %d failures\n",
-                rounds, n_trunc, n_caught_by_decode, n_flip, n_escape_only, g_fail);
+                "changed only the verbatim bits of escaped values = valid streams of another frame), %ld chunked-unit cases, %d failures\n",
+                rounds, n_trunc, n_caught_by_decode, n_flip, n_escape_only, n_chunked, g_fail);
     return g_fail ? 1 : 0;
 }

@@ -937,6 +937,104 @@ int dcvc_rans_dec_check_end(dcvc_rans_dec* d)
     return 0;
 }
 
+// ------------------------------------------------------------------ chunked y units (this project's stream extension)
+// One y unit = ceil(count / S) little-endian uint16 chunk byte lengths, then the chunk bodies.  A chunk is S kept symbols
+// (the last one fewer) coded as an independent stream of the arithmetic above: state kRansL, symbols pushed in reverse,
+// 4-byte flush - byte for byte what reset(); encode_y(chunk); flush() of ONE coder writes.  Independent chunks are what
+// lets csrc/dcvc_rans_dev.hip code a unit with one GPU lane per chunk; this is the format's normative implementation, the
+// encoder's fallback and what decodes such a stream on a machine without a GPU.  docs/chunked_stream.md has the layout.
+static bool chunked_args_ok(int log2_s) { return log2_s >= 8 && log2_s <= 12; }
+
+int64_t dcvc_rans_chunked_encode_y(dcvc_rans_enc* e, const int16_t* symbols, int64_t count, int group, int log2_s,
+                                   uint8_t* out, int64_t capacity)
+{
+    const char* who = "dcvc_rans_chunked_encode_y";
+    DCVC_REQUIRE(e && (symbols || count == 0) && count >= 0 && (out || capacity == 0) && capacity >= 0, "%s: bad arguments", who);
+    DCVC_REQUIRE(chunked_args_ok(log2_s), "%s: log2 of the chunk size is %d (8 .. 12)", who, log2_s);
+    DCVC_REQUIRE(group >= 0 && group < (int)e->groups.size(), "%s: unknown cdf group %d", who, group);
+    const CdfGroup& g = e->groups[group];
+    int mx = 0;
+    for (int64_t i = 0; i < count; ++i) mx = std::max(mx, symbols[i] & 0xff);
+    DCVC_REQUIRE(mx < g.n, "%s: cdf index %d out of range (%d tables; the symbols must be the kept ones only)", who, mx, g.n);
+    const int64_t S = (int64_t)1 << log2_s, nch = (count + S - 1) / S;
+    DCVC_REQUIRE(capacity >= 2 * nch, "%s: output buffer of %lld bytes is too small", who, (long long)capacity);
+    // an int8 symbol costs at most 30 bits (16 for the escape symbol, 14 bypass bits): 4 bytes each, 4 for the flush, and
+    // put_symbol's unconditional store below the pointer - 16 KB for S = 4096, so a chunk length always fits its uint16
+    static thread_local std::vector<uint8_t> scratch;
+    scratch.resize((size_t)S * 4 + 16);
+    int64_t pos = 2 * nch;
+    for (int64_t c = 0; c < nch; ++c) {
+        const int64_t a = c * S, b = std::min(count, a + S);
+        uint8_t* end = scratch.data() + scratch.size();
+        uint8_t* ptr = end;
+        uint32_t r = kRansL;
+        for (int64_t i = b - 1; i >= a; --i) {
+            const int32_t cs = symbols[i];
+            encode_symbol(r, ptr, cs >> 8, g, cs & 0xff);
+        }
+        ptr -= 4;
+        ptr[0] = (uint8_t)(r >> 0);
+        ptr[1] = (uint8_t)(r >> 8);
+        ptr[2] = (uint8_t)(r >> 16);
+        ptr[3] = (uint8_t)(r >> 24);
+        const int64_t len = end - ptr;
+        DCVC_REQUIRE(len <= 0xffff, "%s: chunk %lld takes %lld bytes (the length field has 16 bits)", who, (long long)c, (long long)len);
+        DCVC_REQUIRE(pos + len <= capacity, "%s: output buffer of %lld bytes is too small", who, (long long)capacity);
+        out[2 * c] = (uint8_t)(len & 0xff);
+        out[2 * c + 1] = (uint8_t)(len >> 8);
+        std::memcpy(out + pos, ptr, (size_t)len);
+        pos += len;
+    }
+    return pos;
+}
+
+int dcvc_rans_chunked_decode_y(dcvc_rans_dec* d, const uint8_t* unit, int64_t unit_bytes, const uint8_t* indexes, int64_t count,
+                               int group, int log2_s, int8_t* out)
+{
+    const char* who = "dcvc_rans_chunked_decode_y";
+    DCVC_REQUIRE(d && (unit || unit_bytes == 0) && unit_bytes >= 0 && ((indexes && out) || count == 0) && count >= 0,
+                 "%s: bad arguments", who);
+    DCVC_REQUIRE(chunked_args_ok(log2_s), "%s: log2 of the chunk size is %d (8 .. 12)", who, log2_s);
+    DCVC_REQUIRE(group >= 0 && group < (int)d->groups.size(), "%s: unknown cdf group %d", who, group);
+    const CdfGroup& g = d->groups[group];
+    int mx = 0;
+    for (int64_t i = 0; i < count; ++i) mx = indexes[i] > mx ? indexes[i] : mx;
+    DCVC_REQUIRE(mx < g.n, "%s: cdf index %d out of range (%d tables)", who, mx, g.n);
+    const int64_t S = (int64_t)1 << log2_s, nch = (count + S - 1) / S;
+    if (2 * nch > unit_bytes) {
+        dcvc::set_error("%s: %lld symbols need a length table of %lld bytes, the unit has %lld", who, (long long)count,
+                        (long long)(2 * nch), (long long)unit_bytes);
+        return dcvc::E_STREAM;
+    }
+    int64_t total = 2 * nch;
+    for (int64_t c = 0; c < nch; ++c) total += (int64_t)unit[2 * c] | ((int64_t)unit[2 * c + 1] << 8);
+    if (total != unit_bytes) {
+        dcvc::set_error("%s: the length table adds up to %lld bytes, the unit has %lld", who, (long long)total, (long long)unit_bytes);
+        return dcvc::E_STREAM;
+    }
+    const DecTable* tab = g.dtab.data();
+    const uint8_t* p = unit + 2 * nch;
+    for (int64_t c = 0; c < nch; ++c) {
+        const int64_t len = (int64_t)unit[2 * c] | ((int64_t)unit[2 * c + 1] << 8);
+        bool ok = len >= 4;
+        if (ok) {
+            DecCursor cur{(uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24), p + 4, p + len,
+                          false};
+            const int64_t a = c * S, b = std::min(count, a + S);
+            for (int64_t i = a; i < b; ++i) out[i] = (int8_t)cur.decode(tab[indexes[i]]);
+            // done with a chunk = exactly its bytes consumed and the state back at the encoder's initial one
+            ok = !cur.overrun && cur.cur == cur.end && cur.x == kRansL;
+        }
+        if (!ok) {
+            dcvc::set_error("%s: chunk %lld of %lld does not end on its last byte in the initial state (damaged payload)", who,
+                            (long long)c, (long long)nch);
+            return dcvc::E_STREAM;
+        }
+        p += len;
+    }
+    return 0;
+}
+
 int dcvc_pmf_to_quantized_cdf(const float* pmf, int n, int precision, uint32_t* out)
 {
     DCVC_REQUIRE(pmf && out && n > 0 && precision > 0 && precision <= 16, "dcvc_pmf_to_quantized_cdf: bad arguments");

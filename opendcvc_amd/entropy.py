@@ -10,16 +10,60 @@ reference's boolean-mask compaction (data-dependent size => device sync); the co
 sentinels, so the byte stream is unchanged.
 """
 import ctypes
+import io
 import math
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, bitstream
 from ._lib import DcvcError, check
 
 SCALE_MIN, SCALE_MAX, SCALE_LEVELS = 0.11, 16.0, 128
+
+# Chunked payloads (docs/chunked_stream.md; this project's extension, not readable by the reference): the y symbols of a
+# frame are coded in independent chunks of 1 << log2_s symbols, so that the GPU codes them with one lane per chunk.
+CHUNK_LOG2_MIN, CHUNK_LOG2_MAX = 8, 12
+CHUNK_LOG2_DEFAULT = 8          # DESIGN.md section 4: the fastest decode; the rate overhead is what tools/entropy_time.py reports
+DEV_E_COUNT, DEV_E_TABLE, DEV_E_CHUNK, DEV_E_RANGE = 1, 2, 4, 8      # DCVC_RANS_DEV_E_*
+
+
+def pack_chunked_payload(log2_s, z_part, units):
+    """payload of one chunked I / P frame: log2 S, varint len_z + the z part, then varint size + bytes of every y unit"""
+    if not CHUNK_LOG2_MIN <= log2_s <= CHUNK_LOG2_MAX:
+        raise DcvcError(f"chunked payload: log2 of the chunk size is {log2_s} ({CHUNK_LOG2_MIN} .. {CHUNK_LOG2_MAX})")
+    f = io.BytesIO()
+    f.write(bytes((log2_s,)))
+    for part in [z_part] + list(units):
+        bitstream.write_uint_adaptive(f, len(part))
+        f.write(part)
+    return f.getvalue()
+
+
+def parse_chunked_payload(payload, n_units):
+    """-> (log2_s, z part, [(offset, size) of each y unit inside `payload`]); DcvcError unless the header is well formed and
+    the parts add up to the payload exactly"""
+    f = io.BytesIO(payload)
+    try:
+        log2_s = bitstream._byte(f)
+        if not CHUNK_LOG2_MIN <= log2_s <= CHUNK_LOG2_MAX:
+            raise DcvcError(f"corrupt chunked payload: log2 of the chunk size is {log2_s}")
+        nz = bitstream.read_uint_adaptive(f)
+        z_part = f.read(nz)
+        if len(z_part) != nz:
+            raise DcvcError("corrupt or truncated chunked payload: the z part runs past the end")
+        units = []
+        for _ in range(n_units):
+            size = bitstream.read_uint_adaptive(f)
+            units.append((f.tell(), size))
+            if f.seek(size, io.SEEK_CUR) > len(payload):
+                raise DcvcError("corrupt or truncated chunked payload: a y unit runs past the end")
+    except EOFError as e:
+        raise DcvcError("corrupt or truncated chunked payload: header cut short") from e
+    if f.tell() != len(payload):
+        raise DcvcError(f"corrupt chunked payload: {len(payload) - f.tell()} bytes behind the last y unit")
+    return log2_s, z_part, units
 
 
 def _ip(a):
@@ -229,6 +273,27 @@ class EntropyCoder:
               "decode_compact")
         return count
 
+    # ---- chunked y units (both directions synchronous, on the calling thread)
+    def chunked_encode_y(self, symbols, cdf_group_index, log2_s):
+        """symbols: host int16 array of KEPT symbols ((sym << 8) + index, no sentinels) -> the unit's bytes"""
+        symbols = np.ascontiguousarray(symbols, np.int16)
+        nch = (symbols.size + (1 << log2_s) - 1) >> log2_s if CHUNK_LOG2_MIN <= log2_s <= CHUNK_LOG2_MAX else 0
+        out = np.empty(4 * symbols.size + 6 * nch + 16, np.uint8)        # 4 bytes per symbol, flush + length per chunk
+        n = check(_lib.lib().dcvc_rans_chunked_encode_y(self.enc, _ip(symbols), symbols.size, cdf_group_index, log2_s, _ip(out),
+                                                        out.size), "chunked_encode_y")
+        return out[:n].tobytes()
+
+    def chunked_decode_y(self, unit, indexes, count, cdf_group_index, log2_s, out):
+        """unit: bytes of one y unit; indexes[:count]: the kept table indexes in stream order; symbols into out[:count].
+        DcvcError on a damaged unit."""
+        unit = np.frombuffer(unit, np.uint8)
+        if indexes.dtype != np.uint8 or out.dtype != np.int8 or count < 0 or indexes.size < count or out.size < count or \
+                not indexes.flags.c_contiguous or not out.flags.c_contiguous:
+            raise DcvcError("chunked_decode_y: need contiguous uint8 indexes and an int8 output of at least `count` entries")
+        check(_lib.lib().dcvc_rans_chunked_decode_y(self.dec, _ip(unit), unit.size, _ip(indexes), int(count), cdf_group_index,
+                                                    log2_s, _ip(out)), "corrupt or truncated chunked y unit")
+        return count
+
     def decode_and_get_y(self, indexes, cdf_group_index, out):
         """Synchronous: decodes straight from `indexes` into `out` (both host arrays of the same length)."""
         if indexes.dtype != np.uint8 or out.dtype != np.int8 or out.size < indexes.size or \
@@ -237,3 +302,64 @@ class EntropyCoder:
         check(_lib.lib().dcvc_rans_dec_decode_and_get_y(self.dec, _ip(indexes), indexes.size, cdf_group_index,
                                                         _ip(out)), "decode_and_get_y")
         return indexes.size
+
+
+class DeviceCoder:
+    """Device tables of one cdf group for the chunked-unit kernels (csrc/dcvc_rans_dev.hip): dcvc_rans_dev_create / _destroy"""
+
+    def __init__(self, cdf, cdf_length, offset):
+        cdf = np.ascontiguousarray(cdf, np.int32)
+        cdf_length = np.ascontiguousarray(cdf_length, np.int32)
+        offset = np.ascontiguousarray(offset, np.int32)
+        self.handle = ctypes.c_void_p()
+        check(_lib.lib().dcvc_rans_dev_create(_ip(cdf), cdf.shape[0], cdf.shape[1], _ip(cdf_length), _ip(offset),
+                                              ctypes.byref(self.handle)), "rans_dev_create")
+
+    def __del__(self):
+        try:
+            if self.handle:
+                _lib.lib().dcvc_rans_dev_destroy(self.handle)
+        except Exception:
+            pass
+
+    UNIT_INFO_BYTES = 16     # int32 {unit bytes, overflow flag, count, chunks} in front of the unit in its pinned buffer
+
+    @staticmethod
+    def enc_ws_bytes(max_symbols, log2_s, slot_bytes=0):
+        return int(_lib.lib().dcvc_rans_dev_enc_ws_bytes(max_symbols, log2_s, slot_bytes))
+
+    @staticmethod
+    def dec_ws_bytes(max_symbols, log2_s):
+        return int(_lib.lib().dcvc_rans_dev_dec_ws_bytes(max_symbols, log2_s))
+
+    @staticmethod
+    def unit_buffer_bytes(max_symbols, log2_s):
+        """pinned bytes for a unit of up to max_symbols symbols: one byte per symbol (kept y symbols average well under
+        that; a unit that needs more raises its overflow flag and is coded on the host) + length table + info"""
+        nch = (max_symbols + (1 << log2_s) - 1) >> log2_s
+        return (DeviceCoder.UNIT_INFO_BYTES + max_symbols + 2 * nch + 64 + 15) // 16 * 16
+
+    def encode_y(self, sym_dev, count_dev, max_symbols, log2_s, workspace, unit_buf, stream, slot_bytes=0):
+        """enqueues the encode of sym_dev[:*count_dev] (device pointers) into the PinnedBuffer unit_buf; unit_info() /
+        unit_bytes() read the result once the stream has passed this point"""
+        check(_lib.lib().dcvc_rans_dev_encode_y(self.handle, sym_dev, count_dev, max_symbols, log2_s, slot_bytes, workspace,
+                                                ctypes.c_void_p(unit_buf.ptr), unit_buf.nbytes - self.UNIT_INFO_BYTES, stream),
+              "rans_dev_encode_y")
+
+    @staticmethod
+    def unit_info(unit_buf):
+        """-> (unit bytes, overflow flag, symbol count, chunks)"""
+        return tuple(int(v) for v in unit_buf.view(np.int32, 4))
+
+    @staticmethod
+    def unit_bytes(unit_buf):
+        n = int(unit_buf.view(np.int32, 1)[0])
+        return unit_buf.u8[DeviceCoder.UNIT_INFO_BYTES:DeviceCoder.UNIT_INFO_BYTES + n].tobytes()
+
+    def decode_y(self, payload_dev, payload_capacity, unit_desc_dev, idx_dev, count_dev, max_symbols, log2_s, workspace, sym_dev,
+                 error_buf, stream):
+        """enqueues the decode of the unit at payload_dev + desc[0] (desc[1] bytes; device int32 pair) into sym_dev; a damaged
+        unit ORs DEV_E_* bits into the first int32 of the PinnedBuffer error_buf"""
+        check(_lib.lib().dcvc_rans_dev_decode_y(self.handle, payload_dev, payload_capacity, unit_desc_dev, idx_dev, count_dev,
+                                                max_symbols, log2_s, workspace, sym_dev, ctypes.c_void_p(error_buf.ptr), stream),
+              "rans_dev_decode_y")

@@ -350,16 +350,20 @@ def _to_device(planes, device):
 # ---------------------------------------------------------------------------------- one rate point
 def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=None, intra_period=-1,
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
-                  src_type="yuv420", calc_ssim=False, metrics="host"):
+                  src_type="yuv420", calc_ssim=False, metrics="host", entropy="host"):
     """Encodes `frame_num` frames of a YUV 4:2:0 file (src_type "yuv420"), of a raw file in another pixel format
     (pipeline.PIXEL_FORMATS: "yuv420p10le", "yuv444p", "nv12", "p010le", ...; metrics with data_range = max_val, rec_path in
     the source's format) or of a directory of PNGs ("png": RGB, converted to YCbCr around the codec) into the reference's
     container (optionally written to bin_path), decodes the container again, and returns the reference-schema log.  i_net / p_net: DMCI / DMC (weights loaded, .update() called, on `device`,
     optionally .half()).  calc_ssim: MS-SSIM per frame (host computation, slow) instead of zeros.  rec_path: the decoded
     sequence as a planar YUV file / as PNGs in that directory.  metrics: "host" (torch glue + host numpy / scipy MS-SSIM) or
-    "device" (metrics.DeviceMetrics: PSNR and MS-SSIM by HIP kernels, one synchronisation per frame)."""
+    "device" (metrics.DeviceMetrics: PSNR and MS-SSIM by HIP kernels, one synchronisation per frame).  entropy: "host" (the
+    reference's stream, host rANS coder) or "device" (chunked payloads entropy-coded by HIP kernels, docs/chunked_stream.md:
+    this project's extension, NOT readable by the reference; same pictures, slightly larger streams)."""
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics {metrics!r}: 'host' or 'device'")
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy {entropy!r}: 'host' or 'device'")
     if src_type not in SRC_TYPES:
         raise ValueError(f"src_type {src_type!r}: one of {', '.join(SRC_TYPES)}")
     png = src_type == "png"
@@ -380,6 +384,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     two = use_two_entropy_coders(height, width)
     for m in (i_net, p_net):
         m.set_use_two_entropy_coders(two)
+        m.entropy = entropy
     t_start = time.time()
     reader = make_reader()
     enc = SequenceEncoder(i_net, p_net, qp_i, qp_p, intra_period, reset_interval)
@@ -420,7 +425,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         t0 = time.time()
         sps, is_i, qp, payload = stream_reader.read_frame()
         dec.h, dec.w, dec.two = sps["height"], sps["width"], bool(sps["ec_part"])
-        x_hat = dec.decode(FramePacket(is_i, qp, sps["use_ada_i"], payload))
+        x_hat = dec.decode(FramePacket(is_i, qp, sps["use_ada_i"], payload, chunked=stream_reader.chunked))
         torch.cuda.synchronize(dev)
         dec_time.append(time.time() - t0)
         if png:
@@ -658,7 +663,8 @@ def run_job(nets, job, opts):
                         job["qp_i"], job["qp_p"], intra_period=job["intra_period"], reset_interval=job["reset_interval"],
                         bin_path=bin_path, rec_path=rec_path, verbose=opts.get("verbose", 0),
                         verbose_json=opts.get("verbose_json", False), device="cuda:0", src_type=job.get("src_type", "yuv420"),
-                        calc_ssim=bool(opts.get("calc_ssim")), metrics=opts.get("metrics") or "host")
+                        calc_ssim=bool(opts.get("calc_ssim")), metrics=opts.get("metrics") or "host",
+                        entropy=opts.get("entropy") or "host")
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -727,6 +733,9 @@ def build_parser():
     ap.add_argument("--calc-ssim", "--calc_ssim", **flag, help="MS-SSIM per frame (reference --calc_ssim; host computation, slow)")
     ap.add_argument("--metrics", choices=("host", "device"), default="host",
                     help="where PSNR / MS-SSIM are computed: host (torch glue + numpy / scipy MS-SSIM) or device (HIP kernels)")
+    ap.add_argument("--entropy", choices=("host", "device"), default="host",
+                    help="host: the reference's stream format, host rANS coder.  device: chunked payloads entropy-coded by HIP "
+                         "kernels - this project's extension, not readable by the reference")
     ap.add_argument("--force-intra", "--force_intra", **flag, help="every frame an I frame (reference --force_intra)")
     ap.add_argument("--check-existing", "--check_existing", **flag,
                     help="with --stream-path: do not code a point again whose .bin and .json exist (reference --check_existing)")
@@ -769,7 +778,7 @@ def manifest_options(args, ap):
                 reset_interval=args.reset_interval, model_i=args.model_i, model_p=args.model_p,
                 force_zero_thres=args.force_zero_thres, fp32=args.fp32, stream_path=stream_path,
                 verbose=args.verbose, verbose_json=args.verbose_json, calc_ssim=args.calc_ssim, metrics=args.metrics,
-                force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
+                entropy=args.entropy, force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
     return opts, gpus
 
 
@@ -821,7 +830,8 @@ def main(argv=None):
     res = run_sweep(make_nets, args.src, args.width, args.height, args.frames, args.rate_num,
                     args.qp_i or None, args.qp_p or None, bin_prefix=args.bin_prefix,
                     intra_period=args.intra_period, reset_interval=args.reset_interval, verbose=args.verbose,
-                    verbose_json=args.verbose_json, src_type=args.src_type, calc_ssim=args.calc_ssim, metrics=args.metrics)
+                    verbose_json=args.verbose_json, src_type=args.src_type, calc_ssim=args.calc_ssim, metrics=args.metrics,
+                    entropy=args.entropy)
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:

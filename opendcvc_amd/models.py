@@ -22,6 +22,7 @@ from torch import nn as tnn
 from . import _lib, arch, entropy
 from . import nn as L
 from ._lib import DcvcError, check
+from .entropy import CHUNK_LOG2_DEFAULT
 
 
 def _register(root, dotted, tensor):
@@ -146,10 +147,22 @@ DEC_COMPACT = os.environ.get("DCVC_DEC_COMPACT", "1") != "0"
 class _CompactStep:
     """one checkerboard decoding step's hand-off in the compacted form: pinned kept-index / count buffers, the device-side
     index array and workspace the restore needs again, later the pinned decoded symbols"""
-    __slots__ = ("buf", "cnt", "idx", "ws", "cap", "sym")
+    __slots__ = ("buf", "cnt", "idx", "ws", "cap", "sym", "dsym")
 
-    def __init__(self, buf, cnt, idx, ws, cap):
+    def __init__(self, buf, cnt, idx, ws, cap, dsym=None):
         self.buf, self.cnt, self.idx, self.ws, self.cap, self.sym = buf, cnt, idx, ws, cap, None
+        self.dsym = dsym          # entropy="device": the decoded symbols, in device memory (buf / cnt are device tensors then)
+
+
+class _ChunkedFrame:
+    """the chunked payload of the frame being decoded (docs/chunked_stream.md): chunk size, the y units' (offset, size) inside
+    the payload and - entropy="device" - the uploaded copy the decode kernels read: [unit (offset, size) int32 pairs: 64
+    bytes][payload], so that a captured launch finds every frame's units through fixed addresses"""
+    DESC_BYTES = 64
+    __slots__ = ("log2_s", "payload", "units", "blob", "cap", "err")
+
+    def __init__(self, log2_s, payload, units):
+        self.log2_s, self.payload, self.units, self.blob, self.cap, self.err = log2_s, payload, units, None, 0, None
 
 
 # DCVC_NO_FORK=1: no second stream inside a run (the temporal prior encoder then runs behind the hyper decoder)
@@ -209,8 +222,19 @@ class RefFrame:
 class CompressionModel(tnn.Module):
     """reference: CompressionModel (common_model.py:13-61)"""
 
-    def __init__(self, model_name, z_channel, qp_total):
+    def __init__(self, model_name, z_channel, qp_total, entropy="host", chunk_log2=None):
         super().__init__()
+        # entropy = "host": the reference-compatible stream, coded by the host rANS coder (the default).
+        # entropy = "device": compress() writes the chunked payload (this project's extension, not readable by the
+        #   reference), its y units coded by the kernels of csrc/dcvc_rans_dev.hip in chunks of 1 << chunk_log2 symbols;
+        #   decompress(..., chunked=True) decodes such a payload on the device.  A "host" model reads (and, with
+        #   compress(..., chunked=True), writes) chunked payloads through the host implementation of the same format.
+        self.entropy = entropy
+        self.chunk_log2 = CHUNK_LOG2_DEFAULT if chunk_log2 is None else chunk_log2
+        self._dev_coder = None
+        self._slot_bytes = 0                      # device encoder scratch slot per chunk (0 = the library's default)
+        self.dev_fallbacks = 0                    # y units the host had to code after a device overflow flag
+        self._chunk = None                        # _ChunkedFrame while a chunked payload is being decoded
         self._model_name = model_name
         self.z_channel = z_channel
         self.qp_total = qp_total
@@ -256,7 +280,9 @@ class CompressionModel(tnn.Module):
         self.entropy_coder = entropy.EntropyCoder()
         self.entropy_coder.adopt_pinned(old)      # pinned staging outlives the coder that allocated it
         self._graphs.clear()                      # the threshold is baked into the captured runs
-        self._g_group = self.entropy_coder.add_cdf(*entropy.gaussian_cdf_tables())
+        self._g_tables = entropy.gaussian_cdf_tables()
+        self._g_group = self.entropy_coder.add_cdf(*self._g_tables)
+        self._dev_coder = None                    # device tables of the same group, built on first use (needs the GPU)
         sd = self.state_dict()
         pre = "bit_estimator_z."
         params = {k[len(pre):]: v.detach().float().cpu() for k, v in sd.items() if k.startswith(pre)}
@@ -444,6 +470,130 @@ class CompressionModel(tnn.Module):
                                        self._stream()), "compact_symbols")
         return hz, hp, hc
 
+    # ---- chunked payloads (docs/chunked_stream.md)
+    def _chunked_mode(self, chunked):
+        """compress(): None -> what the model's entropy attribute implies; returns (chunked, on the device)"""
+        if self.entropy not in ("host", "device"):
+            raise DcvcError(f"entropy must be 'host' or 'device', not {self.entropy!r}")
+        dev = self.entropy == "device"
+        chunked = dev if chunked is None else bool(chunked)
+        if dev and not chunked:
+            raise DcvcError("entropy='device' writes chunked payloads only: the reference's stream format is two serial "
+                            "coder chains per frame, which the GPU cannot produce in parallel")
+        if chunked and not entropy.CHUNK_LOG2_MIN <= self.chunk_log2 <= entropy.CHUNK_LOG2_MAX:
+            raise DcvcError(f"chunk_log2 is {self.chunk_log2} ({entropy.CHUNK_LOG2_MIN} .. {entropy.CHUNK_LOG2_MAX})")
+        return chunked, dev
+
+    def _device_coder(self):
+        if self._dev_coder is None:
+            self._dev_coder = entropy.DeviceCoder(*self._g_tables)
+        return self._dev_coder
+
+    def _symbols_to_units(self, key, z8, packed, log2_s):
+        """Encoder hand-off of entropy="device": z goes to pinned memory as in _symbols_to_host; the kept y symbols of each
+        part are compacted into DEVICE memory and entropy-coded there, one unit per part, each landing in its own pinned
+        buffer (info + unit).  Nothing waits for the host.  Returns (z buffer, unit buffers, compacted symbols, counts)."""
+        lib = _lib.lib()
+        ec = self.entropy_coder
+        parts, nsym = packed.shape
+        nz = z8.numel()
+        hz = ec.pinned(key + "_z", (nz + 3) // 4 * 4)
+        if nz % 4 == 0:
+            check(lib.dcvc_copy_f32(ctypes.c_void_p(hz.dptr), L._p(z8), nz // 4, self._stream()), "z to host")
+        else:
+            check(lib.dcvc_memcpy_d2h(ctypes.c_void_p(hz.ptr), L._p(z8), nz, self._stream()), "d2h")
+        dev = packed.device
+        ws = self._buffer("compact_ws", (256 * parts,), torch.int32, dev)
+        csym = self._buffer(key + "_csym", (parts, nsym), torch.int16, dev)
+        ccnt = self._buffer(key + "_ccnt", (parts,), torch.int32, dev)            # counts[p] of part p, dense
+        check(lib.dcvc_compact_symbols_dev(L._p(packed), nsym, parts, L._p(csym), L._p(ccnt), L._p(ws), self._stream()),
+              "compact_symbols_dev")
+        coder = self._device_coder()
+        ews = self._buffer("rans_enc_ws", (coder.enc_ws_bytes(nsym, log2_s, self._slot_bytes),), torch.uint8, dev)
+        units = []
+        for k in range(parts):
+            ub = ec.pinned(f"{key}_unit{k}_{log2_s}", coder.unit_buffer_bytes(nsym, log2_s))
+            coder.encode_y(L._p(csym[k]), ctypes.c_void_p(ccnt.data_ptr() + 4 * k), nsym, log2_s, L._p(ews), ub, self._stream(),
+                           slot_bytes=self._slot_bytes)
+            units.append(ub)
+        return hz, units, csym, ccnt
+
+    def _code_z_part(self, hz, nz, qp, zhw):
+        """the z part of a chunked payload: what the host coder writes for reset(); encode_z(...); flush()"""
+        ec = self.entropy_coder
+        ec.reset()
+        ec.encode_z(hz.view(np.int8, nz), self._z_group, qp * self.z_channel, zhw)
+        ec.flush()
+        return ec.get_encoded_stream()
+
+    def _code_chunked(self, job):
+        """host: assembles one frame's chunked payload (waits for the hand-off first).  Device mode: the units are already
+        coded - a unit whose overflow flag is up (a chunk outgrew its scratch slot, or the unit its buffer) is coded here
+        instead, from the compacted symbols, by the host implementation of the same format.  Host mode codes every unit."""
+        job["ready"].synchronize()
+        ec = self.entropy_coder
+        log2_s, nsym = job["log2_s"], job["nsym"]
+        z_part = self._code_z_part(job["hz"], job["nz"], job["qp"], job["zhw"])
+        units = []
+        if job["mode"] == "device":
+            for k, ub in enumerate(job["units"]):
+                _, overflow, count, _ = entropy.DeviceCoder.unit_info(ub)
+                if overflow:
+                    if not 0 <= count <= nsym:
+                        raise DcvcError("encoder hand-off: %d kept symbols of %d positions" % (count, nsym))
+                    units.append(ec.chunked_encode_y(job["csym"][k, :count].cpu().numpy(), self._g_group, log2_s))
+                    self.dev_fallbacks += 1
+                else:
+                    units.append(entropy.DeviceCoder.unit_bytes(ub))
+        else:
+            parts = job["parts"]
+            ps, kept = job["hp"].view(np.int16, parts * nsym), job["hc"].view(np.int32, parts)
+            for k in range(parts):
+                units.append(ec.chunked_encode_y(ps[k * nsym:k * nsym + kept[k]], self._g_group, log2_s))
+        return entropy.pack_chunked_payload(log2_s, z_part, units)
+
+    def _open_chunked(self, bit_stream, n_units, sps):
+        """decoder: parses and validates a chunked payload's header, hands the z part to the host coder and - entropy="device" -
+        uploads the payload with one stream-ordered copy.  Returns the graph-key suffix of the frame's captured runs."""
+        if not DEC_COMPACT:       # (checked for every frame: the captured runs of the whole-array hand-off must never serve one)
+            raise DcvcError("chunked payloads are decoded through the compacted hand-off (DCVC_DEC_COMPACT=0 is set)")
+        ec = self.entropy_coder
+        log2_s, z_part, units = entropy.parse_chunked_payload(bit_stream, n_units)
+        ec.set_use_two_entropy_coders(sps["ec_part"] == 1)
+        ec.set_stream(z_part)
+        cf = self._chunk = _ChunkedFrame(log2_s, bit_stream, units)
+        if self.entropy != "device":
+            return ()
+        n, D = len(bit_stream), _ChunkedFrame.DESC_BYTES
+        cap = 1 << 16
+        while cap < n:
+            cap *= 2
+        stage = ec.pinned("dev_payload", D + cap)
+        desc = stage.view(np.int32, D // 4)
+        desc[:] = 0
+        desc[:2 * n_units] = np.asarray(units, np.int32).reshape(-1)
+        stage.u8[D:D + n] = np.frombuffer(bit_stream, np.uint8)
+        cf.cap = cap
+        cf.blob = self._buffer("dev_payload", (D + cap,), torch.uint8, self._dtype_device()[1])
+        cf.err = ec.pinned("dev_err", 16)
+        cf.err.view(np.int32, 4)[:] = 0
+        check(_lib.lib().dcvc_memcpy_h2d(L._p(cf.blob), ctypes.c_void_p(stage.ptr), (D + n + 15) // 16 * 16, self._stream()), "h2d")
+        return ("dev", log2_s, cap)
+
+    def _close_chunked(self):
+        """end of a chunked frame on the device: waits for the frame's last kernel and reads the error word once"""
+        cf, self._chunk = self._chunk, None
+        if cf is None or cf.err is None:
+            return
+        ev = torch.cuda.Event()
+        ev.record()
+        ev.synchronize()
+        bits = int(cf.err.view(np.int32, 1)[0])
+        if bits:
+            raise DcvcError("corrupt or truncated frame payload: the device entropy decoder reports error bits 0x%x "
+                            "(1: symbol count vs length table, 2: length table vs unit size, 4: a chunk does not end in its "
+                            "initial state on its last byte, 8: range)" % bits)
+
     def _prior_enc_step(self, groups, step, q_mode, y, qsrc, scales, means, yhat, packed):
         H, W, C, ldy = L._geom(y)
         check(_lib.lib().dcvc_prior_enc_step(
@@ -470,6 +620,26 @@ class CompressionModel(tnn.Module):
         whole lines; only z (read coalesced, 65 KB) is taken in place."""
         n = (C // groups) * H * W
         idx = torch.empty(n, dtype=torch.uint8, device=scales.device)
+        cf = self._chunk
+        if cf is not None and cf.blob is not None:
+            # entropy="device": kept indexes and their count stay in device memory, the step's unit is decoded right behind
+            # them on the stream, and _symbols_to_device restores from the device symbols - no host step, no event wait
+            lib = _lib.lib()
+            cap = (n + 15) // 16 * 16
+            dev = scales.device
+            ws = torch.empty(int(lib.dcvc_prior_dec_compact_ws_bytes(H, W, C, groups)), dtype=torch.uint8, device=dev)
+            cidx = torch.empty(cap, dtype=torch.uint8, device=dev)
+            cnt = torch.empty(4, dtype=torch.int32, device=dev)
+            dsym = torch.empty(cap, dtype=torch.int8, device=dev)
+            check(lib.dcvc_prior_dec_index_compact_dev(L.dtype_code(scales.dtype), groups, step, L._p(scales), scales.stride(1),
+                                                       H, W, C, self._thres(), L._p(idx), L._p(ws), L._p(cidx), L._p(cnt),
+                                                       self._stream()), "prior_dec_index_compact_dev")
+            coder = self._device_coder()
+            dws = torch.empty(coder.dec_ws_bytes(n, cf.log2_s), dtype=torch.uint8, device=dev)
+            D = _ChunkedFrame.DESC_BYTES
+            coder.decode_y(ctypes.c_void_p(cf.blob.data_ptr() + D), cf.cap, ctypes.c_void_p(cf.blob.data_ptr() + 8 * int(key[1:])),
+                           L._p(cidx), L._p(cnt), n, cf.log2_s, L._p(dws), L._p(dsym), cf.err, self._stream())
+            return _CompactStep(cidx, cnt, idx, ws, cap, dsym=dsym)
         if DEC_COMPACT:
             lib = _lib.lib()
             cap = (n + 15) // 16 * 16
@@ -488,6 +658,19 @@ class CompressionModel(tnn.Module):
 
     def _decode_on_host(self, idx_host, n, key):
         """host: rANS-decode the step's symbols (the caller has waited for the stream to pass the index hand-off)"""
+        if isinstance(idx_host, _CompactStep) and idx_host.dsym is not None:
+            return idx_host                       # entropy="device": decoded on the stream already
+        if isinstance(idx_host, _CompactStep) and self._chunk is not None:
+            # a chunked payload on the host: the step's unit through the host implementation of the format
+            cs, cf = idx_host, self._chunk
+            count = int(cs.cnt.view(np.int32, 1)[0])
+            if not 0 <= count <= n:
+                raise DcvcError("decoder hand-off: %d kept symbols of %d positions" % (count, n))
+            cs.sym = self.entropy_coder.pinned(key + "_csym", cs.cap)
+            off, size = cf.units[int(key[1:])]
+            self.entropy_coder.chunked_decode_y(cf.payload[off:off + size], cs.buf.view(np.uint8, cs.cap), count, self._g_group,
+                                                cf.log2_s, cs.sym.view(np.int8, cs.cap))
+            return cs
         if isinstance(idx_host, _CompactStep):
             cs = idx_host
             count = int(cs.cnt.view(np.int32, 1)[0])
@@ -504,6 +687,13 @@ class CompressionModel(tnn.Module):
         """device: upload the decoded symbols (stream-ordered copy, see _index_to_host) and restore y_hat at the step's
         positions"""
         out = yhat if out is None else out
+        if isinstance(sym_host, _CompactStep) and sym_host.dsym is not None:
+            cs = sym_host
+            check(_lib.lib().dcvc_prior_dec_restore_compact_dev(
+                L.dtype_code(means.dtype), groups, step, L._p(cs.dsym), L._p(cs.idx), L._p(cs.ws), L._p(means),
+                means.stride(1), H, W, C, L._p(yhat), yhat.stride(1), L._p(out), out.stride(1), self._stream()),
+                "prior_dec_restore_compact_dev")
+            return
         if isinstance(sym_host, _CompactStep):
             cs = sym_host
             check(_lib.lib().dcvc_prior_dec_restore_compact(
@@ -523,8 +713,8 @@ class CompressionModel(tnn.Module):
 class DMC(CompressionModel):
     """reference: DMC (video_model.py:226-379)"""
 
-    def __init__(self):
-        super().__init__("dmc", arch.DMC_CH_Z, arch.QP_NUM + arch.DMC_EXTRA_QP)
+    def __init__(self, entropy="host", chunk_log2=None):
+        super().__init__("dmc", arch.DMC_CH_Z, arch.QP_NUM + arch.DMC_EXTRA_QP, entropy=entropy, chunk_log2=chunk_log2)
         self.qp_shift = list(arch.DMC_QP_SHIFT)
         self.dpb = []
         self.max_dpb_size = 1
@@ -748,6 +938,8 @@ class DMC(CompressionModel):
 
     def _code_symbols(self, job):
         """host: entropy-codes one frame's symbols (waits for their copy to the pinned staging first)"""
+        if isinstance(job, dict):
+            return self._code_chunked(job)        # chunked payload (entropy="device", or compress(chunked=True))
         ready, hz, hp, hc, nz, nsym, zhw, qp = job
         ready.synchronize()
         ec = self.entropy_coder
@@ -773,15 +965,15 @@ class DMC(CompressionModel):
         job, self._stream_pending = self._stream_pending, None
         return None if job is None else self._code_symbols(job)
 
-    def compress(self, x, qp, defer_stream=False):
+    def compress(self, x, qp, defer_stream=False, chunked=None):
         """compress inside this model's frame scope (_ModelScope): while another thread's GraphCache.run is capturing, a frame
         neither synchronises nor allocates (so two model INSTANCES may be driven from two host threads, through this
         reference-compatible API as well as through SequenceEncoder / SequenceDecoder); a second thread entering the SAME
         instance is refused.  The scope is re-entrant per thread."""
         with self._frame():
-            return self._compress_unguarded(x, qp, defer_stream=defer_stream)
+            return self._compress_unguarded(x, qp, defer_stream=defer_stream, chunked=chunked)
 
-    def _compress_unguarded(self, x, qp, defer_stream=False):
+    def _compress_unguarded(self, x, qp, defer_stream=False, chunked=None):
         """video_model.py:299-341.  x: [1,3,H,W] in [0,1], H and W multiples of 16.
         Two captured runs: everything up to the symbol hand-off, then the decoder (which overlaps the host
         entropy coding).
@@ -789,8 +981,13 @@ class DMC(CompressionModel):
         defer_stream=True (not in the reference API; the encoder-side mirror of decompress(defer_output=True)): the
         symbols of THIS frame are entropy coded during the next call, underneath that frame's kernels - the returned
         dict then carries the PREVIOUS frame's stream under 'bit_stream_prev' and 'bit_stream' is None;
-        finish_stream() returns the last one.  Same symbols, same bytes; a sequential encoder becomes GPU-bound."""
+        finish_stream() returns the last one.  Same symbols, same bytes; a sequential encoder becomes GPU-bound.
+
+        chunked (default: what the model's `entropy` attribute implies): the frame's payload is the chunked one of
+        docs/chunked_stream.md - with entropy="device" its y units are coded by kernels right behind the front run and the
+        host only codes z and concatenates; the returned dict then carries chunked=True (write it as NAL_P_CHUNKED)."""
         dtype, device = self._ensure_layers()
+        chunked, on_device = self._chunked_mode(chunked)
         n = self._layers
         C = arch.DMC_CH_Y
         x = x.to(device=device, dtype=dtype)
@@ -831,7 +1028,10 @@ class DMC(CompressionModel):
         # the host may still be coding the previous frame out of the other one while these writes land)
         par = self._stream_parity
         self._stream_parity ^= 1
-        hz, hp, hc = self._symbols_to_host(f"enc{par}", z8, packed)
+        if on_device:
+            hz, units, csym, ccnt = self._symbols_to_units(f"enc{par}", z8, packed, self.chunk_log2)
+        else:
+            hz, hp, hc = self._symbols_to_host(f"enc{par}", z8, packed)
         ready = torch.cuda.Event()
         ready.record()
         # the decoder keeps the GPU busy while the host codes
@@ -846,26 +1046,36 @@ class DMC(CompressionModel):
 
         # host entropy coding: the previous frame's deferred symbols first (its staging set is reused two frames on)
         prev = self.finish_stream()
-        job = (ready, hz, hp, hc, nz, nsym, zh * zw, qp)
+        if not chunked:
+            job = (ready, hz, hp, hc, nz, nsym, zh * zw, qp)
+        else:
+            job = dict(ready=ready, hz=hz, nz=nz, nsym=nsym, zhw=zh * zw, qp=qp, log2_s=self.chunk_log2, parts=2,
+                       mode="device" if on_device else "host")
+            job.update(dict(units=units, csym=csym, ccnt=ccnt) if on_device else dict(hp=hp, hc=hc))
         # no device synchronisation here (the reference has none either): the tail of the decoder stays in
         # flight on this stream and overlaps the caller's next host work; callers that time a frame sync.
         self.add_ref_frame(fbuf, None)
         self._ahead = nxt
+        # ("chunked" is present only for chunked payloads and tells the mode of THIS frame's stream, whichever call hands it out)
+        mode = {"chunked": True} if chunked else {}
         if defer_stream:
             self._stream_pending = job
-            return {"bit_stream": None, "bit_stream_prev": prev}
+            return dict({"bit_stream": None, "bit_stream_prev": prev}, **mode)
         bit_stream = self._code_symbols(job)
-        return {"bit_stream": bit_stream} if prev is None else {"bit_stream": bit_stream, "bit_stream_prev": prev}
+        return dict({"bit_stream": bit_stream} if prev is None else {"bit_stream": bit_stream, "bit_stream_prev": prev}, **mode)
 
-    def decompress(self, bit_stream, sps, qp, defer_output=False):
+    def decompress(self, bit_stream, sps, qp, defer_output=False, chunked=None):
         """decompress inside this model's frame scope (_ModelScope): while another thread's GraphCache.run is capturing, a frame
         neither synchronises nor allocates (so two model INSTANCES may be driven from two host threads, through this
         reference-compatible API as well as through SequenceEncoder / SequenceDecoder); a second thread entering the SAME
         instance is refused.  The scope is re-entrant per thread."""
         with self._frame():
-            return self._decompress_unguarded(bit_stream, sps, qp, defer_output=defer_output)
+            try:
+                return self._decompress_unguarded(bit_stream, sps, qp, defer_output=defer_output, chunked=chunked)
+            finally:
+                self._chunk = None
 
-    def _decompress_unguarded(self, bit_stream, sps, qp, defer_output=False):
+    def _decompress_unguarded(self, bit_stream, sps, qp, defer_output=False, chunked=None):
         """video_model.py:343-376.  Five captured runs, separated by the three host decoding steps
         (z, first and second checkerboard half).
 
@@ -876,7 +1086,14 @@ class DMC(CompressionModel):
         defer_output=True (not in the reference API): the reconstruction network of THIS frame is not run now
         but in the two host-decoding gaps of the next call (nothing else can use the GPU there: the next
         frame's symbols are not known yet) - the returned dict then carries the PREVIOUS frame under
-        'x_hat_prev' and 'x_hat' is None; finish_output() returns the last frame.  Same kernels, same values."""
+        'x_hat_prev' and 'x_hat' is None; finish_output() returns the last frame.  Same kernels, same values.
+
+        chunked (True: the frame came as NAL_P_CHUNKED; default: what the model's `entropy` attribute implies): the payload
+        is the chunked one of docs/chunked_stream.md.  With entropy="device" it is uploaded once and each checkerboard step
+        is index-compact -> device decode -> restore on the stream, with no host wait between the five runs; the decoder's
+        error word is read once behind the frame's last kernel, so a damaged payload raises DcvcError before the frame
+        enters the DPB (the feature buffer has been overwritten by then: resume at the next I frame, as above).  With
+        entropy="host" the same payload is decoded by the host implementation of the format."""
         dtype, device = self._ensure_layers()
         C = arch.DMC_CH_Y
         forced = None
@@ -884,8 +1101,14 @@ class DMC(CompressionModel):
             forced = self.finish_output()          # the refresh path needs the previous picture itself
         prev = self._pending
         ec = self.entropy_coder
-        ec.set_use_two_entropy_coders(sps["ec_part"] == 1)
-        ec.set_stream(bit_stream)
+        chunked = self.entropy == "device" if chunked is None else bool(chunked)
+        mode_key = ()
+        if chunked:
+            mode_key = self._open_chunked(bit_stream, 2, sps)
+        else:
+            ec.set_use_two_entropy_coders(sps["ec_part"] == 1)
+            ec.set_stream(bit_stream)
+        on_device = bool(mode_key)
         zh, zw = self.get_downsampled_shape(sps["height"], sps["width"], 64)
         yh, yw = self.get_downsampled_shape(sps["height"], sps["width"], 16)
         nz = self.z_channel * zh * zw
@@ -900,6 +1123,9 @@ class DMC(CompressionModel):
 
         x1 = self._graphs.run(("dec_0",) + key, lambda: self._extractor_part1(variant, ref_buf))
         ec.get_decoded(zb.view(np.int8, nz))
+        if chunked:
+            ec.check_end()                # the z part is a stream of its own: exactly consumed, or the payload is damaged
+        key = key + mode_key              # (the runs below read the uploaded payload: chunk size and buffer are baked in)
 
         def after_z():
             z_hat = self._z_to_device(zb, zh, zw, dtype, device)
@@ -910,9 +1136,10 @@ class DMC(CompressionModel):
         params, y_hat, idx0 = self._graphs.run(("dec_1",) + key, after_z)
         ev = torch.cuda.Event()
         ev.record()
-        ctx = self._graphs.run(("dec_2",) + key, lambda: self._extractor_part2(x1))   # overlaps the host decode
+        ctx = self._graphs.run(("dec_2",) + key[:3], lambda: self._extractor_part2(x1))   # overlaps the host decode
         self._pending_half(0)
-        ev.synchronize()
+        if not on_device:
+            ev.synchronize()
         sym0 = self._decode_on_host(idx0, n_half, "p0")
 
         def after_step0():
@@ -924,9 +1151,11 @@ class DMC(CompressionModel):
         ev = torch.cuda.Event()
         ev.record()
         self._pending_half(1)
-        ev.synchronize()
+        if not on_device:
+            ev.synchronize()
         sym1 = self._decode_on_host(idx1, n_half, "p1")
-        ec.check_end()                    # corrupt / truncated payload: DcvcError here, not a garbage picture
+        if not chunked:
+            ec.check_end()                # corrupt / truncated payload: DcvcError here, not a garbage picture
 
         def after_step1():
             # runs must be idempotent on buffers they did not allocate (see GraphCache): the second half is
@@ -943,6 +1172,13 @@ class DMC(CompressionModel):
             self._pending = None
         head = self._graphs.run(("dec_4d" if defer_output else "dec_4",) + key, after_step1)
         x_hat = None if head is None else self._picture_out(head)
+        if on_device:
+            try:
+                self._close_chunked()     # waits for the frame's last kernel, reads the error word: DcvcError if damaged
+            except DcvcError:
+                if prev is not None:
+                    self._pending = prev  # the previous frame's deferred picture stays retrievable (finish_output)
+                raise
         self.add_ref_frame(fbuf, x_hat)
         if defer_output:
             qrec = self._buffer("q_recon_pending", q["q_recon"].shape, torch.float32, device)
@@ -961,10 +1197,10 @@ DMC.decode_one_frame = DMC.decompress        # itself has only compress / decomp
 class DMCI(CompressionModel):
     """reference: DMCI (image_model.py:102-209)"""
 
-    def __init__(self, N=arch.DMCI_N, z_channel=arch.DMCI_CH_Z):
+    def __init__(self, N=arch.DMCI_N, z_channel=arch.DMCI_CH_Z, entropy="host", chunk_log2=None):
         if N != arch.DMCI_N or z_channel != arch.DMCI_CH_Z:
             raise DcvcError("only the published DCVC-RT-Intra configuration (N=256, z=128) is built")
-        super().__init__("dmci", z_channel, arch.QP_NUM)
+        super().__init__("dmci", z_channel, arch.QP_NUM, entropy=entropy, chunk_log2=chunk_log2)
 
     def _build_layers(self, sd, dt):
         D, C2, R, U = L.DepthConvBlock, L.Conv2d, L.ResidualBlockWithStride2, L.ResidualBlockUpsample
@@ -1004,18 +1240,20 @@ class DMCI(CompressionModel):
         n = self._layers
         return L.dcb_chain([n["sp_adaptor"][step]] + n["spatial"], y_hat, common, then_conv=n["spatial_out"])
 
-    def compress(self, x, qp):
+    def compress(self, x, qp, chunked=None):
         """compress inside this model's frame scope (_ModelScope): while another thread's GraphCache.run is capturing, a frame
         neither synchronises nor allocates (so two model INSTANCES may be driven from two host threads, through this
         reference-compatible API as well as through SequenceEncoder / SequenceDecoder); a second thread entering the SAME
         instance is refused.  The scope is re-entrant per thread."""
         with self._frame():
-            return self._compress_unguarded(x, qp)
+            return self._compress_unguarded(x, qp, chunked=chunked)
 
-    def _compress_unguarded(self, x, qp):
+    def _compress_unguarded(self, x, qp, chunked=None):
         """image_model.py:143-185 + compress_prior_4x (common_model.py:206-256).  Two captured runs, like DMC:
-        everything up to the symbol hand-off, then the synthesis transform (which overlaps the host entropy coder)."""
+        everything up to the symbol hand-off, then the synthesis transform (which overlaps the host entropy coder).
+        chunked: as DMC.compress (four y units; the returned dict carries chunked=True)."""
         dtype, device = self._ensure_layers()
+        chunked, on_device = self._chunked_mode(chunked)
         n = self._layers
         C = arch.DMCI_N
         x = x.to(device=device, dtype=dtype)
@@ -1044,11 +1282,19 @@ class DMCI(CompressionModel):
             return y_hat, z8, packed, z8.numel(), nsym, (z.shape[0], z.shape[1])
 
         y_hat, z8, packed, nz, nsym, (zh, zw) = self._graphs.run(("ienc_front",) + key, front)
-        hz, hp, hc = self._symbols_to_host("ienc", z8, packed)
+        if on_device:
+            hz, units, csym, ccnt = self._symbols_to_units("ienc", z8, packed, self.chunk_log2)
+        else:
+            hz, hp, hc = self._symbols_to_host("ienc", z8, packed)
         ready = torch.cuda.Event()
         ready.record()
         x_hat = self._picture_out(self._graphs.run(("ienc_back",) + key, lambda: self._dec(y_hat, q["q_scale_dec"])))
 
+        if chunked:
+            job = dict(ready=ready, hz=hz, nz=nz, nsym=nsym, zhw=zh * zw, qp=qp, log2_s=self.chunk_log2, parts=4,
+                       mode="device" if on_device else "host")
+            job.update(dict(units=units, csym=csym, ccnt=ccnt) if on_device else dict(hp=hp, hc=hc))
+            return {"bit_stream": self._code_chunked(job), "x_hat": x_hat, "chunked": True}
         ready.synchronize()
         ec = self.entropy_coder
         ec.reset()
@@ -1060,34 +1306,46 @@ class DMCI(CompressionModel):
         bit_stream = ec.get_encoded_stream()
         return {"bit_stream": bit_stream, "x_hat": x_hat}
 
-    def decompress(self, bit_stream, sps, qp):
+    def decompress(self, bit_stream, sps, qp, chunked=None):
         """decompress inside this model's frame scope (_ModelScope): while another thread's GraphCache.run is capturing, a frame
         neither synchronises nor allocates (so two model INSTANCES may be driven from two host threads, through this
         reference-compatible API as well as through SequenceEncoder / SequenceDecoder); a second thread entering the SAME
         instance is refused.  The scope is re-entrant per thread."""
         with self._frame():
-            return self._decompress_unguarded(bit_stream, sps, qp)
+            try:
+                return self._decompress_unguarded(bit_stream, sps, qp, chunked=chunked)
+            finally:
+                self._chunk = None
 
-    def _decompress_unguarded(self, bit_stream, sps, qp):
+    def _decompress_unguarded(self, bit_stream, sps, qp, chunked=None):
         """image_model.py:187-209 + decompress_prior_4x (common_model.py:258-296).  Five captured runs split at the
         four host decoding steps (the reference's dependency structure: each checkerboard step needs the symbols of
         the previous one); a run never updates an earlier run's output in place (GraphCache), so every step restores
-        into a fresh y_hat."""
+        into a fresh y_hat.  chunked=True (NAL_I_CHUNKED): as DMC.decompress - on the device the four steps run without a
+        host wait and the error word is read once behind the synthesis transform."""
         dtype, device = self._ensure_layers()
         n = self._layers
         C = arch.DMCI_N
         ec = self.entropy_coder
-        ec.set_use_two_entropy_coders(sps["ec_part"] == 1)
-        ec.set_stream(bit_stream)
+        chunked = self.entropy == "device" if chunked is None else bool(chunked)
+        mode_key = ()
+        if chunked:
+            mode_key = self._open_chunked(bit_stream, 4, sps)
+        else:
+            ec.set_use_two_entropy_coders(sps["ec_part"] == 1)
+            ec.set_stream(bit_stream)
+        on_device = bool(mode_key)
         zh, zw = self.get_downsampled_shape(sps["height"], sps["width"], 64)
         yh, yw = self.get_downsampled_shape(sps["height"], sps["width"], 16)
         nz = self.z_channel * zh * zw
         nsym = (C // 4) * yh * yw
-        key = (sps["height"], sps["width"])
+        key = (sps["height"], sps["width"]) + mode_key
         q = self._stage_q(qp)
         ec.decode_z(nz, self._z_group, qp * self.z_channel, zh * zw)
         zb = ec.pinned("z_dec", nz)
         ec.get_decoded(zb.view(np.int8, nz))
+        if chunked:
+            ec.check_end()                # the z part is a stream of its own
 
         def first():
             z_hat = self._z_to_device(zb, zh, zw, dtype, device)
@@ -1099,11 +1357,12 @@ class DMCI(CompressionModel):
         means = params[:, :, 2 + C:2 + 2 * C]
         y_prev = None
         for step in (0, 1, 2, 3):
-            ev = torch.cuda.Event()
-            ev.record()
-            ev.synchronize()                       # the index copy of this step has landed
+            if not on_device:
+                ev = torch.cuda.Event()
+                ev.record()
+                ev.synchronize()                   # the index copy of this step has landed
             sym = self._decode_on_host(idx, nsym, f"i{step}")
-            if step == 3:
+            if step == 3 and not chunked:
                 ec.check_end()            # corrupt / truncated payload: DcvcError here, not a garbage picture
 
             def after(step=step, sym=sym, means=means, y_prev=y_prev):
@@ -1121,7 +1380,10 @@ class DMCI(CompressionModel):
             else:
                 y_prev, sp, idx = res
                 means = sp[:, :, C:]
-        return {"x_hat": self._picture_out(x_hat)}
+        x_hat = self._picture_out(x_hat)
+        if on_device:
+            self._close_chunked()         # waits for the frame's last kernel, reads the error word: DcvcError if damaged
+        return {"x_hat": x_hat}
 
 
 DMCI.encode_one_frame = DMCI.compress

@@ -14,6 +14,7 @@ class FramePacket:
     qp: int
     use_ada_i: int
     bit_stream: bytes
+    chunked: bool = False        # chunked payload (the models' entropy="device" mode): written as NAL_I_CHUNKED / NAL_P_CHUNKED
 
 
 class SequenceEncoder:
@@ -25,7 +26,7 @@ class SequenceEncoder:
     def __init__(self, i_net, p_net, qp_i, qp_p=None, intra_period=-1, reset_interval=32, defer_stream=False):
         self.i_net, self.p_net = i_net, p_net
         self.defer = defer_stream
-        self._held = None            # (qp, use_ada_i) of the P frame whose stream is still pending
+        self._held = None            # (qp, use_ada_i, chunked) of the P frame whose stream is still pending
         self.qp_i = qp_i
         self.qp_p = qp_i if qp_p is None else qp_p
         self.intra_period = intra_period
@@ -42,7 +43,7 @@ class SequenceEncoder:
     def _take_held(self, stream):
         out = []
         if self._held is not None and stream is not None:
-            out.append(FramePacket(False, self._held[0], self._held[1], stream))
+            out.append(FramePacket(False, self._held[0], self._held[1], stream, chunked=self._held[2]))
             self._held = None
         return out
 
@@ -54,7 +55,7 @@ class SequenceEncoder:
             enc = self.i_net.compress(x_padded, self.qp_i)
             self.p_net.clear_dpb()
             self.p_net.add_ref_frame(None, enc["x_hat"])
-            pkt = FramePacket(True, self.qp_i, 0, enc["bit_stream"])
+            pkt = FramePacket(True, self.qp_i, 0, enc["bit_stream"], chunked=bool(enc.get("chunked", False)))
             return done + [pkt] if self.defer else pkt
         use_ada_i = 0
         if self.reset_interval > 0 and fi % self.reset_interval == 1:
@@ -63,10 +64,11 @@ class SequenceEncoder:
         qp = self.p_net.shift_qp(self.qp_p, INDEX_MAP[fi % 8])
         enc = self.p_net.compress(x_padded, qp, defer_stream=self.defer)
         self.last_qp = qp
+        chunked = bool(enc.get("chunked", False))         # (the models' entropy="device" mode: NAL_*_CHUNKED)
         if not self.defer:
-            return FramePacket(False, qp, use_ada_i, enc["bit_stream"])
+            return FramePacket(False, qp, use_ada_i, enc["bit_stream"], chunked=chunked)
         done = self._take_held(enc.get("bit_stream_prev"))
-        self._held = (qp, use_ada_i)
+        self._held = (qp, use_ada_i, chunked)
         return done
 
     def flush(self):
@@ -96,19 +98,21 @@ class SequenceDecoder:
     def _decode(self, pkt):
         sps = dict(height=self.h, width=self.w, ec_part=1 if self.two else 0, use_ada_i=pkt.use_ada_i)
         done = []
+        # the payload's mode comes with the packet (its NAL type); codecs without the mode never see the keyword
+        mode = {"chunked": bool(getattr(pkt, "chunked", False))} if hasattr(self.p_net, "entropy") else {}
         if pkt.is_i:
             if self.defer:
                 last = self.p_net.finish_output()
                 if last is not None:
                     done.append(last)
-            dec = self.i_net.decompress(pkt.bit_stream, sps, pkt.qp)
+            dec = self.i_net.decompress(pkt.bit_stream, sps, pkt.qp, **mode)
             self.p_net.clear_dpb()
             self.p_net.add_ref_frame(None, dec["x_hat"])
             done.append(dec["x_hat"])
         else:
             if pkt.use_ada_i:
                 self.p_net.reset_ref_feature()
-            dec = self.p_net.decompress(pkt.bit_stream, sps, pkt.qp, defer_output=self.defer)
+            dec = self.p_net.decompress(pkt.bit_stream, sps, pkt.qp, defer_output=self.defer, **mode)
             for k in ("x_hat_prev", "x_hat"):
                 if dec.get(k) is not None:
                     done.append(dec[k])
