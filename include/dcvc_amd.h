@@ -456,6 +456,25 @@ int dcvc_frame_to_planes(int dtype, int chroma, int bit_depth, int semi_planar, 
  * source's samples (DCVC_U8 / DCVC_U16 operands of dcvc_sse / dcvc_msssim_stats). */
 int dcvc_frame_to_metric_planes(int dtype, int chroma, int max_val, const void* x_nchw, int Hp, int Wp, int H, int W,
                                 float* y, float* u, float* v, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Frame analysis for the encoder's scene-cut decision (csrc/dcvc_analysis.hip; no reference counterpart: the reference
+ * harness places I frames by fi % intra_period only).  luma: H x W samples of the model input (DCVC_F16 / DCVC_F32), row
+ * stride ld elements, read in place.  Per sample q = (int)fminf(fmaxf(rintf(v * 1023.0f), 0.0f), 1023.0f) (one fp32
+ * multiply, ties to even, a NaN counts as 0); everything after it is integer arithmetic, so the result does not depend
+ * on the reduction order:
+ *   lowres_out[by][bx] = sum of q over the 8 x 8 block (uint16, at most 65472), shape [H/8][W/8]
+ *   inter = sum |L - L_prev| over all blocks (0 if lowres_prev is NULL)
+ *   intra = sum over the blocks of min(|L - left|, |L - top|); first row: |L - left|, first column: |L - top|,
+ *           block (0, 0): 0
+ *   total = sum L
+ * out_host (dcvc_host_alloc memory, 4 words): inter, intra, total, number of blocks - written by the last of the three
+ * kernels, valid for the host once the stream has passed that point; the call does not wait for the device.
+ * H and W: multiples of 8, at least 8 (anything else is an argument error and launches nothing).  The luma pass reads 16
+ * bytes per access where ld and the base address allow it, narrower otherwise.  workspace: device, 8-byte aligned,
+ * dcvc_frame_analysis_ws_bytes(H, W) bytes (< 0: bad size).  lowres_prev and lowres_out must differ. */
+int64_t dcvc_frame_analysis_ws_bytes(int H, int W);
+int dcvc_frame_analyze(int dtype, const void* luma, int64_t ld, int H, int W, const uint16_t* lowres_prev,
+                       uint16_t* lowres_out, void* workspace, uint64_t* out_host, void* stream);
 /* dst[0..n) = src[0..n) on the device by a kernel (the per-frame row of the quantisation tables: src/models/video_model.py:303-305
  * slices them per call; a runtime copy command costs an order of magnitude more than the kernel) */
 int dcvc_copy_f32(float* dst, const float* src, int n, void* stream);

@@ -350,7 +350,7 @@ def _to_device(planes, device):
 # ---------------------------------------------------------------------------------- one rate point
 def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=None, intra_period=-1,
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
-                  src_type="yuv420", calc_ssim=False, metrics="host", entropy="host"):
+                  src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4):
     """Encodes `frame_num` frames of a YUV 4:2:0 file (src_type "yuv420"), of a raw file in another pixel format
     (pipeline.PIXEL_FORMATS: "yuv420p10le", "yuv444p", "nv12", "p010le", ...; metrics with data_range = max_val, rec_path in
     the source's format) or of a directory of PNGs ("png": RGB, converted to YCbCr around the codec) into the reference's
@@ -359,7 +359,10 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     sequence as a planar YUV file / as PNGs in that directory.  metrics: "host" (torch glue + host numpy / scipy MS-SSIM) or
     "device" (metrics.DeviceMetrics: PSNR and MS-SSIM by HIP kernels, one synchronisation per frame).  entropy: "host" (the
     reference's stream, host rANS coder) or "device" (chunked payloads entropy-coded by HIP kernels, docs/chunked_stream.md:
-    this project's extension, NOT readable by the reference; same pictures, slightly larger streams)."""
+    this project's extension, NOT readable by the reference; same pictures, slightly larger streams).  scenecut (percent,
+    0 = off; 150 is the recommended value) / min_keyint: adaptive I frames at scene cuts found on the device
+    (pipeline.SequenceEncoder, analysis.FrameAnalyzer); the log then carries one extra key, scene_cuts - the frames coded
+    as I frames because of a cut - and intra_period / reset_interval count from the most recent I frame."""
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics {metrics!r}: 'host' or 'device'")
     if entropy not in ("host", "device"):
@@ -387,7 +390,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         m.entropy = entropy
     t_start = time.time()
     reader = make_reader()
-    enc = SequenceEncoder(i_net, p_net, qp_i, qp_p, intra_period, reset_interval)
+    adaptive = dict(scenecut=scenecut, min_keyint=min_keyint) if scenecut else {}
+    enc = SequenceEncoder(i_net, p_net, qp_i, qp_p, intra_period, reset_interval, **adaptive)
     out = io.BytesIO()
     writer = StreamWriter(out)
     frame_types, bits, enc_time, dec_time, psnrs, ssims = [], [], [], [], [], []
@@ -465,8 +469,11 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     if verbose >= 1 and frame_num > 10:     # the first 10 frames are warm-up (test_video.py:328-333)
         avg_e = sum(enc_time[10:]) / len(enc_time[10:])
         avg_d = sum(dec_time[10:]) / len(dec_time[10:])
-    return summarize(height * width, test_time, frame_types, bits, psnrs, ssims, verbose=verbose_json,
-                     avg_encoding_time=avg_e, avg_decoding_time=avg_d)
+    log = summarize(height * width, test_time, frame_types, bits, psnrs, ssims, verbose=verbose_json,
+                    avg_encoding_time=avg_e, avg_decoding_time=avg_d)
+    if scenecut:
+        log["scene_cuts"] = list(enc.scene_cuts)
+    return log
 
 
 def run_sweep(make_nets, src_path, width, height, frame_num, rate_num=4, qp_i=None, qp_p=None, bin_prefix=None, **kw):
@@ -664,7 +671,8 @@ def run_job(nets, job, opts):
                         bin_path=bin_path, rec_path=rec_path, verbose=opts.get("verbose", 0),
                         verbose_json=opts.get("verbose_json", False), device="cuda:0", src_type=job.get("src_type", "yuv420"),
                         calc_ssim=bool(opts.get("calc_ssim")), metrics=opts.get("metrics") or "host",
-                        entropy=opts.get("entropy") or "host")
+                        entropy=opts.get("entropy") or "host", scenecut=opts.get("scenecut") or 0,
+                        min_keyint=opts.get("min_keyint") or 4)
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -753,6 +761,12 @@ def build_parser():
     ap.add_argument("--qp-p", "--qp_p", type=int, nargs="*")
     ap.add_argument("--intra-period", type=int, default=-1)
     ap.add_argument("--reset-interval", "--reset_interval", type=int, default=32)
+    ap.add_argument("--scenecut", type=int, default=0, metavar="PCT",
+                    help="adaptive I frames: a frame whose low-resolution difference to its predecessor is at least PCT percent "
+                         "of its own spatial activity starts a new GOP (0 = off, the reference's placement; 150 is recommended); "
+                         "--intra-period and --reset-interval then count from the most recent I frame")
+    ap.add_argument("--min-keyint", "--min_keyint", type=int, default=4, metavar="N",
+                    help="with --scenecut: a cut fewer than N frames after the last I frame is coded as a P frame")
     ap.add_argument("--model-i", "--model_path_i", help="DMCI checkpoint (.pth.tar); synthetic weights if omitted")
     ap.add_argument("--model-p", "--model_path_p", help="DMC checkpoint")
     ap.add_argument("--force-zero-thres", "--force_zero_thres", type=float, default=0.12)
@@ -778,7 +792,7 @@ def manifest_options(args, ap):
                 reset_interval=args.reset_interval, model_i=args.model_i, model_p=args.model_p,
                 force_zero_thres=args.force_zero_thres, fp32=args.fp32, stream_path=stream_path,
                 verbose=args.verbose, verbose_json=args.verbose_json, calc_ssim=args.calc_ssim, metrics=args.metrics,
-                entropy=args.entropy, force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
+                entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint, force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
     return opts, gpus
 
 
@@ -831,7 +845,7 @@ def main(argv=None):
                     args.qp_i or None, args.qp_p or None, bin_prefix=args.bin_prefix,
                     intra_period=args.intra_period, reset_interval=args.reset_interval, verbose=args.verbose,
                     verbose_json=args.verbose_json, src_type=args.src_type, calc_ssim=args.calc_ssim, metrics=args.metrics,
-                    entropy=args.entropy)
+                    entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint)
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:

@@ -21,9 +21,21 @@ class SequenceEncoder:
     """defer_stream=False: encode(x) returns the frame's packet (the reference's loop).
     defer_stream=True: P-frame packets come out one call late - encode(x) returns a LIST of the packets completed by
     the call, in order, flush() the rest; the host entropy coding of a P frame then runs underneath the next frame's
-    kernels (DMC.compress(defer_stream=True)), which makes a sequential encoder GPU-bound."""
+    kernels (DMC.compress(defer_stream=True)), which makes a sequential encoder GPU-bound.
 
-    def __init__(self, i_net, p_net, qp_i, qp_p=None, intra_period=-1, reset_interval=32, defer_stream=False):
+    scenecut (percent, None / 0 = off: exactly the reference's placement, no analyzer, nothing launched): adaptive I
+    frames.  Every frame is analysed on the device (analysis.FrameAnalyzer) and the policy counts GOP-relative: with g
+    the number of frames since the most recent I frame (g = 0 at an I frame), a frame is an I frame if it is frame 0, if
+    intra_period > 0 and g == intra_period, or if analysis.is_cut(stats, scenecut) and g >= min_keyint (a cut closer to
+    the last I frame is coded as a P frame); P frames take use_ada_i from g % reset_interval == 1 and the qp offset
+    INDEX_MAP[g % 8].  Without a cut the stream equals the scenecut-off stream whenever g == fi for every frame:
+    intra_period = -1, or an intra_period that is a multiple of 8 and of reset_interval.  scene_cuts lists the frames
+    whose cut was honoured with an I frame (also where the period asked for one at the same frame).  encode(x, ready):
+    `ready` is a torch.cuda.Event recorded where x became ready, so the analysis need not wait for the kernels of the
+    previous frame that defer_stream keeps in flight.  analyzer: any object with analyze(x, ready) -> FrameStats."""
+
+    def __init__(self, i_net, p_net, qp_i, qp_p=None, intra_period=-1, reset_interval=32, defer_stream=False,
+                 scenecut=None, min_keyint=4, analyzer=None):
         self.i_net, self.p_net = i_net, p_net
         self.defer = defer_stream
         self._held = None            # (qp, use_ada_i, chunked) of the P frame whose stream is still pending
@@ -33,11 +45,20 @@ class SequenceEncoder:
         self.reset_interval = reset_interval
         self.frame_idx = 0
         self.last_qp = 0
+        self.scenecut = int(scenecut) if scenecut else 0
+        if self.scenecut < 0 or min_keyint < 1:
+            raise ValueError("scenecut is a percentage >= 0 and min_keyint is at least 1")
+        self.min_keyint = int(min_keyint)
+        self._analyzer = analyzer if self.scenecut else None      # (made at the first frame, on the frame's device)
+        self._gop_pos = 0            # g of the previous frame
+        self.scene_cuts = []
         p_net.set_curr_poc(0)
 
-    def encode(self, x_padded):
+    def encode(self, x_padded, ready=None):
         from .models import CAPTURE_GUARD
         with CAPTURE_GUARD.frame():          # (a HIP graph capture on another thread waits for / holds back this frame)
+            if self.scenecut:
+                return self._encode_adaptive(x_padded, ready)
             return self._encode(x_padded)
 
     def _take_held(self, stream):
@@ -50,7 +71,27 @@ class SequenceEncoder:
     def _encode(self, x_padded):
         fi = self.frame_idx
         self.frame_idx += 1
-        if fi == 0 or (self.intra_period > 0 and fi % self.intra_period == 0):
+        return self._code(x_padded, fi == 0 or (self.intra_period > 0 and fi % self.intra_period == 0), fi)
+
+    def _encode_adaptive(self, x_padded, ready):
+        from .analysis import is_cut
+        if self._analyzer is None:
+            from .analysis import FrameAnalyzer
+            self._analyzer = FrameAnalyzer(x_padded.device)
+        fi = self.frame_idx
+        self.frame_idx += 1
+        stats = self._analyzer.analyze(x_padded, ready)          # every frame: the next one needs this one's plane
+        g = self._gop_pos + 1
+        cut = fi > 0 and g >= self.min_keyint and is_cut(stats, self.scenecut)
+        is_i = fi == 0 or cut or (self.intra_period > 0 and g == self.intra_period)
+        if cut:
+            self.scene_cuts.append(fi)
+        self._gop_pos = 0 if is_i else g
+        return self._code(x_padded, is_i, self._gop_pos)
+
+    def _code(self, x_padded, is_i, pos):
+        """pos: what the P-frame rules count - the frame index (the reference), or the distance to the last I frame"""
+        if is_i:
             done = self._take_held(self.p_net.finish_stream()) if self.defer else []
             enc = self.i_net.compress(x_padded, self.qp_i)
             self.p_net.clear_dpb()
@@ -58,10 +99,10 @@ class SequenceEncoder:
             pkt = FramePacket(True, self.qp_i, 0, enc["bit_stream"], chunked=bool(enc.get("chunked", False)))
             return done + [pkt] if self.defer else pkt
         use_ada_i = 0
-        if self.reset_interval > 0 and fi % self.reset_interval == 1:
+        if self.reset_interval > 0 and pos % self.reset_interval == 1:
             use_ada_i = 1
             self.p_net.prepare_feature_adaptor_i(self.last_qp)
-        qp = self.p_net.shift_qp(self.qp_p, INDEX_MAP[fi % 8])
+        qp = self.p_net.shift_qp(self.qp_p, INDEX_MAP[pos % 8])
         enc = self.p_net.compress(x_padded, qp, defer_stream=self.defer)
         self.last_qp = qp
         chunked = bool(enc.get("chunked", False))         # (the models' entropy="device" mode: NAL_*_CHUNKED)
