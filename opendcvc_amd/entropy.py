@@ -1,5 +1,6 @@
-"""Host side of the entropy model: CDF table construction (once per model) and the hand-off
-between the GPU and the C++ rANS coder of libdcvc_amd.so.
+"""Host side of the entropy model: CDF table construction (once per model), the C++ rANS coder of
+libdcvc_amd.so with its pinned staging buffers, and the device coder's tables (handoff.py moves a
+frame's symbols between the GPU and these).
 
 Mirrors, with the same method names, the reference's
   EntropyCoder     src/models/entropy_models.py:11-81   (over MLCodec_extensions_cpp)

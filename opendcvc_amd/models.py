@@ -13,13 +13,14 @@ Reference behaviour restated (no code shared): video_model.py:226-379, image_mod
 common_model.py:13-296.
 """
 import ctypes
+import functools
 import os
 
 import numpy as np
 import torch
 from torch import nn as tnn
 
-from . import _lib, arch, entropy
+from . import _lib, arch, entropy, handoff
 from . import nn as L
 from ._lib import DcvcError, check
 from .entropy import CHUNK_LOG2_DEFAULT
@@ -57,13 +58,12 @@ class _CaptureGuard:
 
     def _enter(self):
         depth = getattr(self._local, "depth", 0)
+        if not depth:
+            with self._cv:
+                while self._capturing:
+                    self._cv.wait()       # (may raise, a KeyboardInterrupt for instance: the depth is still what it was)
+                self._active += 1
         self._local.depth = depth + 1
-        if depth:
-            return
-        with self._cv:
-            while self._capturing:
-                self._cv.wait()
-            self._active += 1
 
     def _exit(self):
         self._local.depth -= 1
@@ -124,7 +124,9 @@ class _ModelScope:
     """One per-frame call of one model: inside CAPTURE_GUARD.frame(), and the only thread inside this model instance.
     A model's captured runs share its scratch buffers, its branch stream and its persistent staging (like the reference's
     models share their DPB): two host threads may drive two DIFFERENT instances concurrently (the two-stage pipeline does),
-    never the same one - that is refused here instead of corrupting a layer's scratch between two of its kernels."""
+    never the same one - that is refused here instead of corrupting a layer's scratch between two of its kernels.
+    While another thread's GraphCache.run is capturing, a frame neither synchronises nor allocates: entry waits for the
+    capture to end.  The scope is re-entrant per thread (compress calls finish_stream, decompress calls finish_output)."""
 
     def __init__(self, model):
         self.m = model
@@ -133,36 +135,30 @@ class _ModelScope:
         if not self.m._owner.acquire(blocking=False):
             raise DcvcError("this model instance is already inside compress / decompress on another host thread: one "
                             "instance is driven by one thread at a time (use one instance per thread; they may share a GPU)")
-        CAPTURE_GUARD._enter()
+        try:
+            CAPTURE_GUARD._enter()
+        except BaseException:
+            self.m._owner.release()       # __exit__ will not run: the model must not stay locked
+            raise
 
     def __exit__(self, *exc):
         CAPTURE_GUARD._exit()
         self.m._owner.release()
 
 
-# DCVC_DEC_COMPACT=0: the decoder hands whole index / symbol arrays over by copy commands (round 3's path; A/B measurements)
+def _frame_scoped(method):
+    """a per-frame method of the public API (the reference-compatible one as well as what SequenceEncoder / SequenceDecoder
+    call): its whole body runs inside the model's _ModelScope"""
+    @functools.wraps(method)
+    def scoped(self, *args, **kwargs):
+        with self._frame():
+            return method(self, *args, **kwargs)
+    return scoped
+
+
+# DCVC_DEC_COMPACT=0: the decoder hands whole index / symbol arrays over by copy commands (A/B measurements, and the
+# reference of the compacted form's test); read when a frame is opened (CompressionModel._open_frame)
 DEC_COMPACT = os.environ.get("DCVC_DEC_COMPACT", "1") != "0"
-
-
-class _CompactStep:
-    """one checkerboard decoding step's hand-off in the compacted form: pinned kept-index / count buffers, the device-side
-    index array and workspace the restore needs again, later the pinned decoded symbols"""
-    __slots__ = ("buf", "cnt", "idx", "ws", "cap", "sym", "dsym")
-
-    def __init__(self, buf, cnt, idx, ws, cap, dsym=None):
-        self.buf, self.cnt, self.idx, self.ws, self.cap, self.sym = buf, cnt, idx, ws, cap, None
-        self.dsym = dsym          # entropy="device": the decoded symbols, in device memory (buf / cnt are device tensors then)
-
-
-class _ChunkedFrame:
-    """the chunked payload of the frame being decoded (docs/chunked_stream.md): chunk size, the y units' (offset, size) inside
-    the payload and - entropy="device" - the uploaded copy the decode kernels read: [unit (offset, size) int32 pairs: 64
-    bytes][payload], so that a captured launch finds every frame's units through fixed addresses"""
-    DESC_BYTES = 64
-    __slots__ = ("log2_s", "payload", "units", "blob", "cap", "err")
-
-    def __init__(self, log2_s, payload, units):
-        self.log2_s, self.payload, self.units, self.blob, self.cap, self.err = log2_s, payload, units, None, 0, None
 
 
 # DCVC_NO_FORK=1: no second stream inside a run (the temporal prior encoder then runs behind the hyper decoder)
@@ -234,7 +230,6 @@ class CompressionModel(tnn.Module):
         self._dev_coder = None
         self._slot_bytes = 0                      # device encoder scratch slot per chunk (0 = the library's default)
         self.dev_fallbacks = 0                    # y units the host had to code after a device overflow flag
-        self._chunk = None                        # _ChunkedFrame while a chunked payload is being decoded
         self._model_name = model_name
         self.z_channel = z_channel
         self.qp_total = qp_total
@@ -449,150 +444,16 @@ class CompressionModel(tnn.Module):
                                           L._p(out), self.z_channel, self._stream()), "z_from_int8")
         return out
 
-    # ---- host <-> device staging
-    def _symbols_to_host(self, key, z8, packed):
-        """Encoder hand-off without a copy command: z (int8) and the KEPT y symbols of each part of `packed`, compacted in
-        order on the device, are written by kernels straight into pinned host buffers (dcvc_compact_symbols).  Returns
-        (z buffer, symbol buffer, counts buffer); valid for the host once the stream has passed this point."""
-        lib = _lib.lib()
-        ec = self.entropy_coder
-        parts, nsym = packed.shape
-        nz = z8.numel()
-        hz = ec.pinned(key + "_z", (nz + 3) // 4 * 4)
-        hp = ec.pinned(key + "_sym", parts * nsym * 2)
-        hc = ec.pinned(key + "_cnt", 4 * parts)
-        ws = self._buffer("compact_ws", (256 * parts,), torch.int32, packed.device)
-        if nz % 4 == 0:
-            check(lib.dcvc_copy_f32(ctypes.c_void_p(hz.dptr), L._p(z8), nz // 4, self._stream()), "z to host")
-        else:
-            check(lib.dcvc_memcpy_d2h(ctypes.c_void_p(hz.ptr), L._p(z8), nz, self._stream()), "d2h")
-        check(lib.dcvc_compact_symbols(L._p(packed), nsym, parts, ctypes.c_void_p(hp.ptr), ctypes.c_void_p(hc.ptr), L._p(ws),
-                                       self._stream()), "compact_symbols")
-        return hz, hp, hc
-
-    # ---- chunked payloads (docs/chunked_stream.md)
-    def _chunked_mode(self, chunked):
-        """compress(): None -> what the model's entropy attribute implies; returns (chunked, on the device)"""
-        if self.entropy not in ("host", "device"):
-            raise DcvcError(f"entropy must be 'host' or 'device', not {self.entropy!r}")
-        dev = self.entropy == "device"
-        chunked = dev if chunked is None else bool(chunked)
-        if dev and not chunked:
-            raise DcvcError("entropy='device' writes chunked payloads only: the reference's stream format is two serial "
-                            "coder chains per frame, which the GPU cannot produce in parallel")
-        if chunked and not entropy.CHUNK_LOG2_MIN <= self.chunk_log2 <= entropy.CHUNK_LOG2_MAX:
-            raise DcvcError(f"chunk_log2 is {self.chunk_log2} ({entropy.CHUNK_LOG2_MIN} .. {entropy.CHUNK_LOG2_MAX})")
-        return chunked, dev
-
+    # ---- entropy hand-off (handoff.py)
     def _device_coder(self):
         if self._dev_coder is None:
             self._dev_coder = entropy.DeviceCoder(*self._g_tables)
         return self._dev_coder
 
-    def _symbols_to_units(self, key, z8, packed, log2_s):
-        """Encoder hand-off of entropy="device": z goes to pinned memory as in _symbols_to_host; the kept y symbols of each
-        part are compacted into DEVICE memory and entropy-coded there, one unit per part, each landing in its own pinned
-        buffer (info + unit).  Nothing waits for the host.  Returns (z buffer, unit buffers, compacted symbols, counts)."""
-        lib = _lib.lib()
-        ec = self.entropy_coder
-        parts, nsym = packed.shape
-        nz = z8.numel()
-        hz = ec.pinned(key + "_z", (nz + 3) // 4 * 4)
-        if nz % 4 == 0:
-            check(lib.dcvc_copy_f32(ctypes.c_void_p(hz.dptr), L._p(z8), nz // 4, self._stream()), "z to host")
-        else:
-            check(lib.dcvc_memcpy_d2h(ctypes.c_void_p(hz.ptr), L._p(z8), nz, self._stream()), "d2h")
-        dev = packed.device
-        ws = self._buffer("compact_ws", (256 * parts,), torch.int32, dev)
-        csym = self._buffer(key + "_csym", (parts, nsym), torch.int16, dev)
-        ccnt = self._buffer(key + "_ccnt", (parts,), torch.int32, dev)            # counts[p] of part p, dense
-        check(lib.dcvc_compact_symbols_dev(L._p(packed), nsym, parts, L._p(csym), L._p(ccnt), L._p(ws), self._stream()),
-              "compact_symbols_dev")
-        coder = self._device_coder()
-        ews = self._buffer("rans_enc_ws", (coder.enc_ws_bytes(nsym, log2_s, self._slot_bytes),), torch.uint8, dev)
-        units = []
-        for k in range(parts):
-            ub = ec.pinned(f"{key}_unit{k}_{log2_s}", coder.unit_buffer_bytes(nsym, log2_s))
-            coder.encode_y(L._p(csym[k]), ctypes.c_void_p(ccnt.data_ptr() + 4 * k), nsym, log2_s, L._p(ews), ub, self._stream(),
-                           slot_bytes=self._slot_bytes)
-            units.append(ub)
-        return hz, units, csym, ccnt
-
-    def _code_z_part(self, hz, nz, qp, zhw):
-        """the z part of a chunked payload: what the host coder writes for reset(); encode_z(...); flush()"""
-        ec = self.entropy_coder
-        ec.reset()
-        ec.encode_z(hz.view(np.int8, nz), self._z_group, qp * self.z_channel, zhw)
-        ec.flush()
-        return ec.get_encoded_stream()
-
-    def _code_chunked(self, job):
-        """host: assembles one frame's chunked payload (waits for the hand-off first).  Device mode: the units are already
-        coded - a unit whose overflow flag is up (a chunk outgrew its scratch slot, or the unit its buffer) is coded here
-        instead, from the compacted symbols, by the host implementation of the same format.  Host mode codes every unit."""
-        job["ready"].synchronize()
-        ec = self.entropy_coder
-        log2_s, nsym = job["log2_s"], job["nsym"]
-        z_part = self._code_z_part(job["hz"], job["nz"], job["qp"], job["zhw"])
-        units = []
-        if job["mode"] == "device":
-            for k, ub in enumerate(job["units"]):
-                _, overflow, count, _ = entropy.DeviceCoder.unit_info(ub)
-                if overflow:
-                    if not 0 <= count <= nsym:
-                        raise DcvcError("encoder hand-off: %d kept symbols of %d positions" % (count, nsym))
-                    units.append(ec.chunked_encode_y(job["csym"][k, :count].cpu().numpy(), self._g_group, log2_s))
-                    self.dev_fallbacks += 1
-                else:
-                    units.append(entropy.DeviceCoder.unit_bytes(ub))
-        else:
-            parts = job["parts"]
-            ps, kept = job["hp"].view(np.int16, parts * nsym), job["hc"].view(np.int32, parts)
-            for k in range(parts):
-                units.append(ec.chunked_encode_y(ps[k * nsym:k * nsym + kept[k]], self._g_group, log2_s))
-        return entropy.pack_chunked_payload(log2_s, z_part, units)
-
-    def _open_chunked(self, bit_stream, n_units, sps):
-        """decoder: parses and validates a chunked payload's header, hands the z part to the host coder and - entropy="device" -
-        uploads the payload with one stream-ordered copy.  Returns the graph-key suffix of the frame's captured runs."""
-        if not DEC_COMPACT:       # (checked for every frame: the captured runs of the whole-array hand-off must never serve one)
-            raise DcvcError("chunked payloads are decoded through the compacted hand-off (DCVC_DEC_COMPACT=0 is set)")
-        ec = self.entropy_coder
-        log2_s, z_part, units = entropy.parse_chunked_payload(bit_stream, n_units)
-        ec.set_use_two_entropy_coders(sps["ec_part"] == 1)
-        ec.set_stream(z_part)
-        cf = self._chunk = _ChunkedFrame(log2_s, bit_stream, units)
-        if self.entropy != "device":
-            return ()
-        n, D = len(bit_stream), _ChunkedFrame.DESC_BYTES
-        cap = 1 << 16
-        while cap < n:
-            cap *= 2
-        stage = ec.pinned("dev_payload", D + cap)
-        desc = stage.view(np.int32, D // 4)
-        desc[:] = 0
-        desc[:2 * n_units] = np.asarray(units, np.int32).reshape(-1)
-        stage.u8[D:D + n] = np.frombuffer(bit_stream, np.uint8)
-        cf.cap = cap
-        cf.blob = self._buffer("dev_payload", (D + cap,), torch.uint8, self._dtype_device()[1])
-        cf.err = ec.pinned("dev_err", 16)
-        cf.err.view(np.int32, 4)[:] = 0
-        check(_lib.lib().dcvc_memcpy_h2d(L._p(cf.blob), ctypes.c_void_p(stage.ptr), (D + n + 15) // 16 * 16, self._stream()), "h2d")
-        return ("dev", log2_s, cap)
-
-    def _close_chunked(self):
-        """end of a chunked frame on the device: waits for the frame's last kernel and reads the error word once"""
-        cf, self._chunk = self._chunk, None
-        if cf is None or cf.err is None:
-            return
-        ev = torch.cuda.Event()
-        ev.record()
-        ev.synchronize()
-        bits = int(cf.err.view(np.int32, 1)[0])
-        if bits:
-            raise DcvcError("corrupt or truncated frame payload: the device entropy decoder reports error bits 0x%x "
-                            "(1: symbol count vs length table, 2: length table vs unit size, 4: a chunk does not end in its "
-                            "initial state on its last byte, 8: range)" % bits)
+    def _open_frame(self, bit_stream, sps, chunked, units, prefix):
+        """decoder: the hand-off object of the frame in `bit_stream` (chunked None: what the model's entropy attribute implies)"""
+        chunked = self.entropy == "device" if chunked is None else bool(chunked)
+        return handoff.open_frame(self, bit_stream, sps, units, prefix, chunked, DEC_COMPACT)
 
     def _prior_enc_step(self, groups, step, q_mode, y, qsrc, scales, means, yhat, packed):
         H, W, C, ldy = L._geom(y)
@@ -605,107 +466,6 @@ class CompressionModel(tnn.Module):
         H, W, C, ld = L._geom(yhat)
         check(_lib.lib().dcvc_prior_finish(L.dtype_code(yhat.dtype), q_mode, L._p(yhat), ld, L._p(qsrc), qsrc.stride(1),
                                            H, W, C, self._stream()), "prior_finish")
-
-    # one checkerboard decoding step = three pieces, so that the device pieces can sit inside captured runs
-    # (device index build -> host rANS decode -> device restore)
-    def _index_to_host(self, groups, step, scales, H, W, C, key):
-        """device: cdf indexes of the step's symbols -> host.  Default (DEC_COMPACT): the KEPT indexes only, compacted in stream
-        order by a kernel that writes them (and their count) straight into pinned buffers - returns a _CompactStep; the
-        decoded symbols come back the same way (_symbols_to_device).  DCVC_DEC_COMPACT=0: the whole array, see below.
-
-        Whole-array form: pinned host buffer by a stream-ordered copy.
-        Measured in round 4 (profiles/r04_dec_inplace.txt): the kernel writing the indexes straight into the pinned buffer takes
-        39 us instead of 5.4 us + a ~10 us copy command, and the restore kernel reading the symbols in place 108 us instead
-        of 7.7 us + copy - a channel's run of 16 pixels is 16 bytes, one bus transaction per lane, where the copy moves
-        whole lines; only z (read coalesced, 65 KB) is taken in place."""
-        n = (C // groups) * H * W
-        idx = torch.empty(n, dtype=torch.uint8, device=scales.device)
-        cf = self._chunk
-        if cf is not None and cf.blob is not None:
-            # entropy="device": kept indexes and their count stay in device memory, the step's unit is decoded right behind
-            # them on the stream, and _symbols_to_device restores from the device symbols - no host step, no event wait
-            lib = _lib.lib()
-            cap = (n + 15) // 16 * 16
-            dev = scales.device
-            ws = torch.empty(int(lib.dcvc_prior_dec_compact_ws_bytes(H, W, C, groups)), dtype=torch.uint8, device=dev)
-            cidx = torch.empty(cap, dtype=torch.uint8, device=dev)
-            cnt = torch.empty(4, dtype=torch.int32, device=dev)
-            dsym = torch.empty(cap, dtype=torch.int8, device=dev)
-            check(lib.dcvc_prior_dec_index_compact_dev(L.dtype_code(scales.dtype), groups, step, L._p(scales), scales.stride(1),
-                                                       H, W, C, self._thres(), L._p(idx), L._p(ws), L._p(cidx), L._p(cnt),
-                                                       self._stream()), "prior_dec_index_compact_dev")
-            coder = self._device_coder()
-            dws = torch.empty(coder.dec_ws_bytes(n, cf.log2_s), dtype=torch.uint8, device=dev)
-            D = _ChunkedFrame.DESC_BYTES
-            coder.decode_y(ctypes.c_void_p(cf.blob.data_ptr() + D), cf.cap, ctypes.c_void_p(cf.blob.data_ptr() + 8 * int(key[1:])),
-                           L._p(cidx), L._p(cnt), n, cf.log2_s, L._p(dws), L._p(dsym), cf.err, self._stream())
-            return _CompactStep(cidx, cnt, idx, ws, cap, dsym=dsym)
-        if DEC_COMPACT:
-            lib = _lib.lib()
-            cap = (n + 15) // 16 * 16
-            ws = torch.empty(int(lib.dcvc_prior_dec_compact_ws_bytes(H, W, C, groups)), dtype=torch.uint8, device=scales.device)
-            buf = self.entropy_coder.pinned(key + "_cidx", cap)
-            cnt = self.entropy_coder.pinned(key + "_ccnt", 16)
-            check(lib.dcvc_prior_dec_index_compact(L.dtype_code(scales.dtype), groups, step, L._p(scales), scales.stride(1),
-                                                   H, W, C, self._thres(), L._p(idx), L._p(ws), ctypes.c_void_p(buf.ptr),
-                                                   ctypes.c_void_p(cnt.ptr), self._stream()), "prior_dec_index_compact")
-            return _CompactStep(buf, cnt, idx, ws, cap)
-        check(_lib.lib().dcvc_prior_dec_index(L.dtype_code(scales.dtype), groups, step, L._p(scales), scales.stride(1),
-                                              H, W, C, self._thres(), L._p(idx), self._stream()), "prior_dec_index")
-        buf = self.entropy_coder.pinned(key + "_idx", n)
-        check(_lib.lib().dcvc_memcpy_d2h(ctypes.c_void_p(buf.ptr), L._p(idx), n, self._stream()), "d2h")
-        return buf
-
-    def _decode_on_host(self, idx_host, n, key):
-        """host: rANS-decode the step's symbols (the caller has waited for the stream to pass the index hand-off)"""
-        if isinstance(idx_host, _CompactStep) and idx_host.dsym is not None:
-            return idx_host                       # entropy="device": decoded on the stream already
-        if isinstance(idx_host, _CompactStep) and self._chunk is not None:
-            # a chunked payload on the host: the step's unit through the host implementation of the format
-            cs, cf = idx_host, self._chunk
-            count = int(cs.cnt.view(np.int32, 1)[0])
-            if not 0 <= count <= n:
-                raise DcvcError("decoder hand-off: %d kept symbols of %d positions" % (count, n))
-            cs.sym = self.entropy_coder.pinned(key + "_csym", cs.cap)
-            off, size = cf.units[int(key[1:])]
-            self.entropy_coder.chunked_decode_y(cf.payload[off:off + size], cs.buf.view(np.uint8, cs.cap), count, self._g_group,
-                                                cf.log2_s, cs.sym.view(np.int8, cs.cap))
-            return cs
-        if isinstance(idx_host, _CompactStep):
-            cs = idx_host
-            count = int(cs.cnt.view(np.int32, 1)[0])
-            if not 0 <= count <= n:
-                raise DcvcError("decoder hand-off: %d kept symbols of %d positions" % (count, n))
-            cs.sym = self.entropy_coder.pinned(key + "_csym", cs.cap)
-            self.entropy_coder.decode_compact(cs.buf.view(np.uint8, cs.cap), count, self._g_group, cs.sym.view(np.int8, cs.cap))
-            return cs
-        sb = self.entropy_coder.pinned(key + "_sym", n)
-        self.entropy_coder.decode_and_get_y(idx_host.view(np.uint8, n), self._g_group, sb.view(np.int8, n))
-        return sb
-
-    def _symbols_to_device(self, sym_host, n, groups, step, means, yhat, H, W, C, out=None):
-        """device: upload the decoded symbols (stream-ordered copy, see _index_to_host) and restore y_hat at the step's
-        positions"""
-        out = yhat if out is None else out
-        if isinstance(sym_host, _CompactStep) and sym_host.dsym is not None:
-            cs = sym_host
-            check(_lib.lib().dcvc_prior_dec_restore_compact_dev(
-                L.dtype_code(means.dtype), groups, step, L._p(cs.dsym), L._p(cs.idx), L._p(cs.ws), L._p(means),
-                means.stride(1), H, W, C, L._p(yhat), yhat.stride(1), L._p(out), out.stride(1), self._stream()),
-                "prior_dec_restore_compact_dev")
-            return
-        if isinstance(sym_host, _CompactStep):
-            cs = sym_host
-            check(_lib.lib().dcvc_prior_dec_restore_compact(
-                L.dtype_code(means.dtype), groups, step, ctypes.c_void_p(cs.sym.ptr), L._p(cs.idx), L._p(cs.ws), L._p(means),
-                means.stride(1), H, W, C, L._p(yhat), yhat.stride(1), L._p(out), out.stride(1), self._stream()),
-                "prior_dec_restore_compact")
-            return
-        sym = torch.empty(n, dtype=torch.int8, device=yhat.device)
-        check(_lib.lib().dcvc_memcpy_h2d(L._p(sym), ctypes.c_void_p(sym_host.ptr), n, self._stream()), "h2d")
-        check(_lib.lib().dcvc_prior_dec_restore(L.dtype_code(means.dtype), groups, step, L._p(sym), L._p(means),
-                                                means.stride(1), H, W, C, L._p(yhat), yhat.stride(1), L._p(out),
-                                                out.stride(1), self._stream()), "prior_dec_restore")
 
 
 # =============================================================================== DMC (P frames)
@@ -898,15 +658,8 @@ class DMC(CompressionModel):
             head = self._graphs.run(("dec_rb",) + pd["key"], lambda: self._recon_second(mid, qrec))
             pd["x_hat"] = self._picture_out(head)
 
+    @_frame_scoped
     def finish_output(self):
-        """finish_output inside this model's frame scope (_ModelScope): while another thread's GraphCache.run is capturing, a frame
-        neither synchronises nor allocates (so two model INSTANCES may be driven from two host threads, through this
-        reference-compatible API as well as through SequenceEncoder / SequenceDecoder); a second thread entering the SAME
-        instance is refused.  The scope is re-entrant per thread."""
-        with self._frame():
-            return self._finish_output_unguarded()
-
-    def _finish_output_unguarded(self):
         """Deferred decoder output: completes and returns the reconstruction of the last decompress(...,
         defer_output=True) (None if there is none).  Called implicitly by the next decompress."""
         if self._pending is None:
@@ -936,44 +689,15 @@ class DMC(CompressionModel):
     def _feature_buf(self, shape, dtype, device):
         return self._buffer("feature", shape, dtype, device)
 
-    def _code_symbols(self, job):
-        """host: entropy-codes one frame's symbols (waits for their copy to the pinned staging first)"""
-        if isinstance(job, dict):
-            return self._code_chunked(job)        # chunked payload (entropy="device", or compress(chunked=True))
-        ready, hz, hp, hc, nz, nsym, zhw, qp = job
-        ready.synchronize()
-        ec = self.entropy_coder
-        ec.reset()
-        ec.encode_z(hz.view(np.int8, nz), self._z_group, qp * self.z_channel, zhw)
-        ps, kept = hp.view(np.int16, 2 * nsym), hc.view(np.int32, 2)
-        ec.encode_y(ps[:kept[0]], self._g_group, borrowed=True)                 # pinned staging buffer, untouched until
-        ec.encode_y(ps[nsym:nsym + kept[1]], self._g_group, borrowed=True)     # get_encoded_stream() below
-        ec.flush()
-        return ec.get_encoded_stream()
-
+    @_frame_scoped
     def finish_stream(self):
-        """finish_stream inside this model's frame scope (_ModelScope): while another thread's GraphCache.run is capturing, a frame
-        neither synchronises nor allocates (so two model INSTANCES may be driven from two host threads, through this
-        reference-compatible API as well as through SequenceEncoder / SequenceDecoder); a second thread entering the SAME
-        instance is refused.  The scope is re-entrant per thread."""
-        with self._frame():
-            return self._finish_stream_unguarded()
-
-    def _finish_stream_unguarded(self):
         """Deferred encoder stream: entropy-codes and returns the bit stream of the last compress(..., defer_stream=True)
         (None if there is none).  Called implicitly by the next compress."""
         job, self._stream_pending = self._stream_pending, None
-        return None if job is None else self._code_symbols(job)
+        return None if job is None else handoff.code(self, job)
 
+    @_frame_scoped
     def compress(self, x, qp, defer_stream=False, chunked=None):
-        """compress inside this model's frame scope (_ModelScope): while another thread's GraphCache.run is capturing, a frame
-        neither synchronises nor allocates (so two model INSTANCES may be driven from two host threads, through this
-        reference-compatible API as well as through SequenceEncoder / SequenceDecoder); a second thread entering the SAME
-        instance is refused.  The scope is re-entrant per thread."""
-        with self._frame():
-            return self._compress_unguarded(x, qp, defer_stream=defer_stream, chunked=chunked)
-
-    def _compress_unguarded(self, x, qp, defer_stream=False, chunked=None):
         """video_model.py:299-341.  x: [1,3,H,W] in [0,1], H and W multiples of 16.
         Two captured runs: everything up to the symbol hand-off, then the decoder (which overlaps the host
         entropy coding).
@@ -987,7 +711,7 @@ class DMC(CompressionModel):
         docs/chunked_stream.md - with entropy="device" its y units are coded by kernels right behind the front run and the
         host only codes z and concatenates; the returned dict then carries chunked=True (write it as NAL_P_CHUNKED)."""
         dtype, device = self._ensure_layers()
-        chunked, on_device = self._chunked_mode(chunked)
+        form = handoff.encoder_form(self, chunked)
         n = self._layers
         C = arch.DMC_CH_Y
         x = x.to(device=device, dtype=dtype)
@@ -1020,20 +744,15 @@ class DMC(CompressionModel):
             sp = self._spatial_prior(y_hat, params)
             self._prior_enc_step(2, 1, 0, y, params[:, :, :C], sp[:, :, :C], sp[:, :, C:], y_hat, packed[1])
             self._prior_finish(0, y_hat, params[:, :, :C])
-            return y_hat, ctx, z8, packed, z8.numel(), nsym, (z.shape[0], z.shape[1])
+            return y_hat, ctx, z8, packed, z.shape[0] * z.shape[1]
 
-        y_hat, ctx, z8, packed, nz, nsym, (zh, zw) = self._graphs.run(
+        y_hat, ctx, z8, packed, zhw = self._graphs.run(
             ("enc_front_ahead" if ahead is not None else "enc_front",) + key, front)
         # symbols -> pinned staging, compacted, by kernels (outside the captured run: two staging sets alternate, so that
         # the host may still be coding the previous frame out of the other one while these writes land)
         par = self._stream_parity
         self._stream_parity ^= 1
-        if on_device:
-            hz, units, csym, ccnt = self._symbols_to_units(f"enc{par}", z8, packed, self.chunk_log2)
-        else:
-            hz, hp, hc = self._symbols_to_host(f"enc{par}", z8, packed)
-        ready = torch.cuda.Event()
-        ready.record()
+        job = handoff.stage(self, f"enc{par}", form, z8, packed, qp, zhw)
         # the decoder keeps the GPU busy while the host codes
         # (keyed by the front run too: its y_hat / ctx are that run's static outputs)
         self._graphs.run(("enc_back", "ahead" if ahead is not None else "full") + key,
@@ -1046,36 +765,20 @@ class DMC(CompressionModel):
 
         # host entropy coding: the previous frame's deferred symbols first (its staging set is reused two frames on)
         prev = self.finish_stream()
-        if not chunked:
-            job = (ready, hz, hp, hc, nz, nsym, zh * zw, qp)
-        else:
-            job = dict(ready=ready, hz=hz, nz=nz, nsym=nsym, zhw=zh * zw, qp=qp, log2_s=self.chunk_log2, parts=2,
-                       mode="device" if on_device else "host")
-            job.update(dict(units=units, csym=csym, ccnt=ccnt) if on_device else dict(hp=hp, hc=hc))
         # no device synchronisation here (the reference has none either): the tail of the decoder stays in
         # flight on this stream and overlaps the caller's next host work; callers that time a frame sync.
         self.add_ref_frame(fbuf, None)
         self._ahead = nxt
         # ("chunked" is present only for chunked payloads and tells the mode of THIS frame's stream, whichever call hands it out)
-        mode = {"chunked": True} if chunked else {}
+        mode = {} if form == handoff.REFERENCE else {"chunked": True}
         if defer_stream:
             self._stream_pending = job
             return dict({"bit_stream": None, "bit_stream_prev": prev}, **mode)
-        bit_stream = self._code_symbols(job)
+        bit_stream = handoff.code(self, job)
         return dict({"bit_stream": bit_stream} if prev is None else {"bit_stream": bit_stream, "bit_stream_prev": prev}, **mode)
 
+    @_frame_scoped
     def decompress(self, bit_stream, sps, qp, defer_output=False, chunked=None):
-        """decompress inside this model's frame scope (_ModelScope): while another thread's GraphCache.run is capturing, a frame
-        neither synchronises nor allocates (so two model INSTANCES may be driven from two host threads, through this
-        reference-compatible API as well as through SequenceEncoder / SequenceDecoder); a second thread entering the SAME
-        instance is refused.  The scope is re-entrant per thread."""
-        with self._frame():
-            try:
-                return self._decompress_unguarded(bit_stream, sps, qp, defer_output=defer_output, chunked=chunked)
-            finally:
-                self._chunk = None
-
-    def _decompress_unguarded(self, bit_stream, sps, qp, defer_output=False, chunked=None):
         """video_model.py:343-376.  Five captured runs, separated by the three host decoding steps
         (z, first and second checkerboard half).
 
@@ -1101,14 +804,7 @@ class DMC(CompressionModel):
             forced = self.finish_output()          # the refresh path needs the previous picture itself
         prev = self._pending
         ec = self.entropy_coder
-        chunked = self.entropy == "device" if chunked is None else bool(chunked)
-        mode_key = ()
-        if chunked:
-            mode_key = self._open_chunked(bit_stream, 2, sps)
-        else:
-            ec.set_use_two_entropy_coders(sps["ec_part"] == 1)
-            ec.set_stream(bit_stream)
-        on_device = bool(mode_key)
+        fr = self._open_frame(bit_stream, sps, chunked, 2, "p")
         zh, zw = self.get_downsampled_shape(sps["height"], sps["width"], 64)
         yh, yw = self.get_downsampled_shape(sps["height"], sps["width"], 16)
         nz = self.z_channel * zh * zw
@@ -1118,50 +814,46 @@ class DMC(CompressionModel):
         variant, ref_buf = self._stage_reference(dtype, device)
         fbuf = self._feature_buf((2 * yh, 2 * yw, arch.DMC_CH_D), dtype, device)
         key = (variant, sps["height"], sps["width"])
-        n_half = (C // 2) * yh * yw
         zb = ec.pinned("z_dec", nz)
 
         x1 = self._graphs.run(("dec_0",) + key, lambda: self._extractor_part1(variant, ref_buf))
         ec.get_decoded(zb.view(np.int8, nz))
-        if chunked:
-            ec.check_end()                # the z part is a stream of its own: exactly consumed, or the payload is damaged
-        key = key + mode_key              # (the runs below read the uploaded payload: chunk size and buffer are baked in)
+        fr.end_z()
+        key = key + fr.suffix             # (device form: the runs below read the uploaded payload, chunk size and buffer are baked in)
 
         def after_z():
             z_hat = self._z_to_device(zb, zh, zw, dtype, device)
             params = self._prior_params(z_hat, x1, q["q_feature"], yh, yw)
             y_hat = torch.empty((yh, yw, C), dtype=dtype, device=device)
-            return params, y_hat, self._index_to_host(2, 0, params[:, :, C:2 * C], yh, yw, C, "p0")
+            return params, y_hat, fr.index(2, 0, params[:, :, C:2 * C], yh, yw, C)
 
-        params, y_hat, idx0 = self._graphs.run(("dec_1",) + key, after_z)
+        params, y_hat, st0 = self._graphs.run(("dec_1",) + key, after_z)
         ev = torch.cuda.Event()
         ev.record()
         ctx = self._graphs.run(("dec_2",) + key[:3], lambda: self._extractor_part2(x1))   # overlaps the host decode
         self._pending_half(0)
-        if not on_device:
+        if fr.host_waits:
             ev.synchronize()
-        sym0 = self._decode_on_host(idx0, n_half, "p0")
+        fr.decode(0, st0)
 
         def after_step0():
-            self._symbols_to_device(sym0, n_half, 2, 0, params[:, :, 2 * C:], y_hat, yh, yw, C)
+            fr.restore(st0, 2, 0, params[:, :, 2 * C:], y_hat, yh, yw, C, out=y_hat)
             sp = self._spatial_prior(y_hat, params)
-            return sp, self._index_to_host(2, 1, sp[:, :, :C], yh, yw, C, "p1")
+            return sp, fr.index(2, 1, sp[:, :, :C], yh, yw, C)
 
-        sp, idx1 = self._graphs.run(("dec_3",) + key, after_step0)
+        sp, st1 = self._graphs.run(("dec_3",) + key, after_step0)
         ev = torch.cuda.Event()
         ev.record()
         self._pending_half(1)
-        if not on_device:
+        if fr.host_waits:
             ev.synchronize()
-        sym1 = self._decode_on_host(idx1, n_half, "p1")
-        if not chunked:
-            ec.check_end()                # corrupt / truncated payload: DcvcError here, not a garbage picture
+        fr.decode(1, st1)                 # (a damaged reference stream raises DcvcError here, behind the frame's last symbol)
 
         def after_step1():
             # runs must be idempotent on buffers they did not allocate (see GraphCache): the second half is
             # accumulated into a fresh tensor, not into the first run's y_hat
             y_fin = torch.empty_like(y_hat)
-            self._symbols_to_device(sym1, n_half, 2, 1, sp[:, :, C:], y_hat, yh, yw, C, out=y_fin)
+            fr.restore(st1, 2, 1, sp[:, :, C:], y_hat, yh, yw, C, out=y_fin)
             self._prior_finish(0, y_fin, params[:, :, :C])
             feature = self._decoder(y_fin, ctx, q["q_decoder"], out=fbuf)
             return None if defer_output else self._recon_head(feature, q["q_recon"])
@@ -1172,13 +864,12 @@ class DMC(CompressionModel):
             self._pending = None
         head = self._graphs.run(("dec_4d" if defer_output else "dec_4",) + key, after_step1)
         x_hat = None if head is None else self._picture_out(head)
-        if on_device:
-            try:
-                self._close_chunked()     # waits for the frame's last kernel, reads the error word: DcvcError if damaged
-            except DcvcError:
-                if prev is not None:
-                    self._pending = prev  # the previous frame's deferred picture stays retrievable (finish_output)
-                raise
+        try:
+            fr.close()                    # device form: waits for the frame's last kernel, reads the error word
+        except DcvcError:
+            if prev is not None:
+                self._pending = prev      # the previous frame's deferred picture stays retrievable (finish_output)
+            raise
         self.add_ref_frame(fbuf, x_hat)
         if defer_output:
             qrec = self._buffer("q_recon_pending", q["q_recon"].shape, torch.float32, device)
@@ -1240,20 +931,13 @@ class DMCI(CompressionModel):
         n = self._layers
         return L.dcb_chain([n["sp_adaptor"][step]] + n["spatial"], y_hat, common, then_conv=n["spatial_out"])
 
+    @_frame_scoped
     def compress(self, x, qp, chunked=None):
-        """compress inside this model's frame scope (_ModelScope): while another thread's GraphCache.run is capturing, a frame
-        neither synchronises nor allocates (so two model INSTANCES may be driven from two host threads, through this
-        reference-compatible API as well as through SequenceEncoder / SequenceDecoder); a second thread entering the SAME
-        instance is refused.  The scope is re-entrant per thread."""
-        with self._frame():
-            return self._compress_unguarded(x, qp, chunked=chunked)
-
-    def _compress_unguarded(self, x, qp, chunked=None):
         """image_model.py:143-185 + compress_prior_4x (common_model.py:206-256).  Two captured runs, like DMC:
         everything up to the symbol hand-off, then the synthesis transform (which overlaps the host entropy coder).
         chunked: as DMC.compress (four y units; the returned dict carries chunked=True)."""
         dtype, device = self._ensure_layers()
-        chunked, on_device = self._chunked_mode(chunked)
+        form = handoff.encoder_form(self, chunked)
         n = self._layers
         C = arch.DMCI_N
         x = x.to(device=device, dtype=dtype)
@@ -1279,45 +963,17 @@ class DMCI(CompressionModel):
                 sp = self._spatial_prior(y_hat, common, step)
                 self._prior_enc_step(4, step, 1, y, params, sp[:, :, :C], sp[:, :, C:], y_hat, packed[step])
             self._prior_finish(1, y_hat, params)
-            return y_hat, z8, packed, z8.numel(), nsym, (z.shape[0], z.shape[1])
+            return y_hat, z8, packed, z.shape[0] * z.shape[1]
 
-        y_hat, z8, packed, nz, nsym, (zh, zw) = self._graphs.run(("ienc_front",) + key, front)
-        if on_device:
-            hz, units, csym, ccnt = self._symbols_to_units("ienc", z8, packed, self.chunk_log2)
-        else:
-            hz, hp, hc = self._symbols_to_host("ienc", z8, packed)
-        ready = torch.cuda.Event()
-        ready.record()
+        y_hat, z8, packed, zhw = self._graphs.run(("ienc_front",) + key, front)
+        job = handoff.stage(self, "ienc", form, z8, packed, qp, zhw)
         x_hat = self._picture_out(self._graphs.run(("ienc_back",) + key, lambda: self._dec(y_hat, q["q_scale_dec"])))
 
-        if chunked:
-            job = dict(ready=ready, hz=hz, nz=nz, nsym=nsym, zhw=zh * zw, qp=qp, log2_s=self.chunk_log2, parts=4,
-                       mode="device" if on_device else "host")
-            job.update(dict(units=units, csym=csym, ccnt=ccnt) if on_device else dict(hp=hp, hc=hc))
-            return {"bit_stream": self._code_chunked(job), "x_hat": x_hat, "chunked": True}
-        ready.synchronize()
-        ec = self.entropy_coder
-        ec.reset()
-        ec.encode_z(hz.view(np.int8, nz), self._z_group, qp * self.z_channel, zh * zw)
-        ps, kept = hp.view(np.int16, 4 * nsym), hc.view(np.int32, 4)
-        for k in range(4):
-            ec.encode_y(ps[k * nsym:k * nsym + kept[k]], self._g_group, borrowed=True)
-        ec.flush()
-        bit_stream = ec.get_encoded_stream()
-        return {"bit_stream": bit_stream, "x_hat": x_hat}
+        res = {"bit_stream": handoff.code(self, job), "x_hat": x_hat}
+        return res if form == handoff.REFERENCE else dict(res, chunked=True)
 
+    @_frame_scoped
     def decompress(self, bit_stream, sps, qp, chunked=None):
-        """decompress inside this model's frame scope (_ModelScope): while another thread's GraphCache.run is capturing, a frame
-        neither synchronises nor allocates (so two model INSTANCES may be driven from two host threads, through this
-        reference-compatible API as well as through SequenceEncoder / SequenceDecoder); a second thread entering the SAME
-        instance is refused.  The scope is re-entrant per thread."""
-        with self._frame():
-            try:
-                return self._decompress_unguarded(bit_stream, sps, qp, chunked=chunked)
-            finally:
-                self._chunk = None
-
-    def _decompress_unguarded(self, bit_stream, sps, qp, chunked=None):
         """image_model.py:187-209 + decompress_prior_4x (common_model.py:258-296).  Five captured runs split at the
         four host decoding steps (the reference's dependency structure: each checkerboard step needs the symbols of
         the previous one); a run never updates an earlier run's output in place (GraphCache), so every step restores
@@ -1327,62 +983,50 @@ class DMCI(CompressionModel):
         n = self._layers
         C = arch.DMCI_N
         ec = self.entropy_coder
-        chunked = self.entropy == "device" if chunked is None else bool(chunked)
-        mode_key = ()
-        if chunked:
-            mode_key = self._open_chunked(bit_stream, 4, sps)
-        else:
-            ec.set_use_two_entropy_coders(sps["ec_part"] == 1)
-            ec.set_stream(bit_stream)
-        on_device = bool(mode_key)
+        fr = self._open_frame(bit_stream, sps, chunked, 4, "i")
         zh, zw = self.get_downsampled_shape(sps["height"], sps["width"], 64)
         yh, yw = self.get_downsampled_shape(sps["height"], sps["width"], 16)
         nz = self.z_channel * zh * zw
-        nsym = (C // 4) * yh * yw
-        key = (sps["height"], sps["width"]) + mode_key
+        key = (sps["height"], sps["width"]) + fr.suffix
         q = self._stage_q(qp)
         ec.decode_z(nz, self._z_group, qp * self.z_channel, zh * zw)
         zb = ec.pinned("z_dec", nz)
         ec.get_decoded(zb.view(np.int8, nz))
-        if chunked:
-            ec.check_end()                # the z part is a stream of its own
+        fr.end_z()
 
         def first():
             z_hat = self._z_to_device(zb, zh, zw, dtype, device)
             params = self._prior_params(z_hat, yh, yw)
             common = n["reduction"](params)
-            return params, common, self._index_to_host(4, 0, params[:, :, 2:2 + C], yh, yw, C, "i0")
+            return params, common, fr.index(4, 0, params[:, :, 2:2 + C], yh, yw, C)
 
-        params, common, idx = self._graphs.run(("idec_0",) + key, first)
+        params, common, st = self._graphs.run(("idec_0",) + key, first)
         means = params[:, :, 2 + C:2 + 2 * C]
         y_prev = None
         for step in (0, 1, 2, 3):
-            if not on_device:
+            if fr.host_waits:
                 ev = torch.cuda.Event()
                 ev.record()
-                ev.synchronize()                   # the index copy of this step has landed
-            sym = self._decode_on_host(idx, nsym, f"i{step}")
-            if step == 3 and not chunked:
-                ec.check_end()            # corrupt / truncated payload: DcvcError here, not a garbage picture
+                ev.synchronize()                   # the index hand-off of this step has landed
+            fr.decode(step, st)           # (a damaged reference stream raises DcvcError behind the frame's last symbol)
 
-            def after(step=step, sym=sym, means=means, y_prev=y_prev):
+            def after(step=step, st=st, means=means, y_prev=y_prev):
                 y_new = torch.empty((yh, yw, C), dtype=dtype, device=device)
-                self._symbols_to_device(sym, nsym, 4, step, means, y_new if y_prev is None else y_prev, yh, yw, C, out=y_new)
+                fr.restore(st, 4, step, means, y_new if y_prev is None else y_prev, yh, yw, C, out=y_new)
                 if step == 3:
                     self._prior_finish(1, y_new, params)
                     return y_new, self._dec(y_new, q["q_scale_dec"])
                 sp = self._spatial_prior(y_new, common, step + 1)
-                return y_new, sp, self._index_to_host(4, step + 1, sp[:, :, :C], yh, yw, C, f"i{step + 1}")
+                return y_new, sp, fr.index(4, step + 1, sp[:, :, :C], yh, yw, C)
 
             res = self._graphs.run((f"idec_{step + 1}",) + key, after)
             if step == 3:
                 x_hat = res[1]
             else:
-                y_prev, sp, idx = res
+                y_prev, sp, st = res
                 means = sp[:, :, C:]
         x_hat = self._picture_out(x_hat)
-        if on_device:
-            self._close_chunked()         # waits for the frame's last kernel, reads the error word: DcvcError if damaged
+        fr.close()                        # device form: waits for the frame's last kernel, reads the error word
         return {"x_hat": x_hat}
 
 

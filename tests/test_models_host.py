@@ -88,6 +88,63 @@ def test_model_scope_is_per_instance_and_reentrant():
     assert out == ["refused", "ok"]
 
 
+def test_model_scope_entry_that_raises_leaves_the_model_unlocked(monkeypatch):
+    """the capture gate raising inside scope entry (its wait can be interrupted): the same exception comes out, and the
+    model is not left owned by the thread that never got in"""
+    from opendcvc_amd import models
+    m = DMC()
+
+    class Interrupted(BaseException):
+        pass
+
+    def enter():
+        raise Interrupted()
+
+    with monkeypatch.context() as mp:
+        mp.setattr(models.CAPTURE_GUARD, "_enter", enter)
+        with pytest.raises(Interrupted):
+            with m._frame():
+                pytest.fail("the scope was entered")
+    out = []
+
+    def other():
+        try:
+            with m._frame():
+                out.append("ok")
+        except DcvcError:
+            out.append("refused")
+
+    t = threading.Thread(target=other)
+    t.start()
+    t.join()
+    assert out == ["ok"]
+
+
+def test_capture_gate_wait_that_raises_restores_the_depth():
+    """an interrupted wait for a capture to end leaves the thread outside the gate: its next frame waits again instead of
+    walking in as if nested"""
+    from opendcvc_amd import models
+    g = models._CaptureGuard()
+
+    class Interrupted(BaseException):
+        pass
+
+    class Cv:
+        def __enter__(self):
+            return self
+
+        def __exit__(self, *exc):
+            return False
+
+        def wait(self):
+            raise Interrupted()
+
+    g._cv, g._capturing = Cv(), True
+    with pytest.raises(Interrupted):
+        g._enter()
+    assert getattr(g._local, "depth", 0) == 0 and g._active == 0
+
+
 def test_worker_gpu_ids_follow_the_parents_visible_devices():
     assert harness.visible_gpu_ids({"HIP_VISIBLE_DEVICES": "4,5"}) == ["4", "5"]
     assert harness.visible_gpu_ids({"ROCR_VISIBLE_DEVICES": "2", "CUDA_VISIBLE_DEVICES": "7"}) == ["2"]

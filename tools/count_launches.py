@@ -4,6 +4,8 @@
     rocprofv3 --kernel-trace --stats --output-format csv -d out4 -- python3 tools/count_launches.py 4
     rocprofv3 --kernel-trace --stats --output-format csv -d out12 -- python3 tools/count_launches.py 12
     python3 tools/count_launches.py --diff out4 out12 8
+
+An optional second argument is the models' entropy mode, `host` (the default) or `device` (chunked payloads coded by kernels).
 """
 import csv, glob, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -49,10 +51,12 @@ import bench
 from opendcvc_amd.pipeline import SequenceDecoder, SequenceEncoder
 torch.set_grad_enabled(False)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4
+mode = sys.argv[2] if len(sys.argv) > 2 else "host"
 dev = torch.device("cuda", 0)
 (ie, pe), (idec, pdec) = bench.load_models(torch.float16, dev, 1, 0)
 for m in (ie, pe, idec, pdec):
     m.set_use_two_entropy_coders(True)
+    m.entropy = mode
 frames = bench.make_frames(0, torch.float16, dev)[1][:n + 1]
 enc = SequenceEncoder(ie, pe, 32, intra_period=64, defer_stream=True)
 dec = SequenceDecoder(idec, pdec, 1080, 1920, True)
@@ -65,4 +69,4 @@ for p in pkts:
     dec.decode(p)
 dec.flush()
 torch.cuda.synchronize()
-print("coded", len(pkts), "frames")
+print("coded", len(pkts), "frames, entropy mode", mode)
