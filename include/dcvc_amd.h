@@ -475,6 +475,25 @@ int dcvc_frame_to_metric_planes(int dtype, int chroma, int max_val, const void* 
 int64_t dcvc_frame_analysis_ws_bytes(int H, int W);
 int dcvc_frame_analyze(int dtype, const void* luma, int64_t ld, int H, int W, const uint16_t* lowres_prev,
                        uint16_t* lowres_out, void* workspace, uint64_t* out_host, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Payload size estimate for rate control (csrc/dcvc_rate.hip; no reference counterpart).  The sum of the code lengths of
+ * one frame's symbols under the quantised CDF tables, in Q16 bits, all in integer arithmetic (independent of the
+ * reduction order).  Cost tables (device, uint32, built on the host in fp64 - entropy.cost_table):
+ *   row t = { meta, cost[0 .. stride - 2] },  meta = (max_value << 16) | (offset & 0xffff),  max_value = sizes[t] - 2,
+ *   cost[v] = rint(65536 * (16 - log2(cdf[t][v + 1] - cdf[t][v]))) for v = 0 .. max_value (max_value: the escape symbol)
+ * packed [parts][nsym] int16 (sym << 8) | idx: an entry with idx >= g_n (0xFF, the sentinel of a skipped entry) is not
+ * coded; value = sym - offset; inside the table (0 <= value < max_value) it costs cost[value], otherwise
+ * cost[max_value] + 2 * 65536 * (n_bypass / 3 + 1 + n_bypass) with raw / n_bypass formed as the host coder's
+ * encode_symbol does.  z8 [nz] int8: the same against row z_start + i / zhw of zcost.
+ * out_host (dcvc_host_alloc memory, 3 * parts + 2 words): per part {Q16 bits, kept symbols, escapes}, then z's
+ * {Q16 bits, escapes} - written by the second of two kernels, valid for the host once the stream has passed that point;
+ * the call does not wait for the device.  nsym: a multiple of 8, packed 16-byte aligned (read 16 bytes per access);
+ * parts 1 .. 8; g_n <= 255 and g_n * g_stride <= 12288 (the Gaussian rows are staged in LDS).  workspace: device, 8-byte
+ * aligned, dcvc_rate_estimate_ws_bytes(nsym, parts, nz) bytes (< 0: bad size). */
+int64_t dcvc_rate_estimate_ws_bytes(int nsym, int parts, int nz);
+int dcvc_rate_estimate(const int16_t* packed, int nsym, int parts, const uint32_t* gcost, int g_n, int g_stride,
+                       const int8_t* z8, int nz, int zhw, const uint32_t* zcost, int z_n, int z_stride, int z_start,
+                       void* workspace, uint64_t* out_host, void* stream);
 /* dst[0..n) = src[0..n) on the device by a kernel (the per-frame row of the quantisation tables: src/models/video_model.py:303-305
  * slices them per call; a runtime copy command costs an order of magnitude more than the kernel) */
 int dcvc_copy_f32(float* dst, const float* src, int n, void* stream);

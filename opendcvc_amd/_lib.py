@@ -140,6 +140,8 @@ _SIGS = {
     "dcvc_frame_to_metric_planes": (_I, [_I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dcvc_frame_analysis_ws_bytes": (_L, [_I, _I]),
     "dcvc_frame_analyze": (_I, [_I, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
+    "dcvc_rate_estimate_ws_bytes": (_L, [_I, _I, _I]),
+    "dcvc_rate_estimate": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "dcvc_copy_f32": (_I, [_P, _P, _I, _P]),
     "dcvc_memcpy_d2h": (_I, [_P, _P, c_size_t, _P]),
     "dcvc_memcpy_h2d": (_I, [_P, _P, c_size_t, _P]),

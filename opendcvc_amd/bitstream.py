@@ -127,6 +127,12 @@ def write_ip(f, is_i_frame, sps_id, qp, bit_stream, chunked=False):
     return n + len(bit_stream)
 
 
+def frame_overhead_bytes(payload_len):
+    """bytes write_ip puts in front of a payload of that length: NAL header, qp, the varint of the length (an SPS, written
+    when a frame's parameters are new to the stream - twice in a typical one - is not counted)"""
+    return 2 + (1 if payload_len < (1 << 7) else 2 if payload_len < (1 << 14) else 4)
+
+
 def read_ip_remaining(f):
     qp = _byte(f)
     length = read_uint_adaptive(f)

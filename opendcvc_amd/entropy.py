@@ -137,6 +137,28 @@ def factorized_cdf_tables(params, qp_num, channel):
     return cdf, (pmf_length.reshape(-1) + 2).numpy().astype(np.int32), (-minima).reshape(-1).numpy().astype(np.int32)
 
 
+def cost_table(cdf, cdf_length, offset):
+    """Code lengths of one cdf group as the uint32 rows csrc/dcvc_rate.hip reads (rate control's size estimate), from the
+    QUANTISED cdfs - the arrays add_cdf receives - in fp64:  row t = [meta, cost[0 .. sizes[t] - 2], 0 ...] with
+    meta = (max_value << 16) | (offset & 0xffff), max_value = sizes[t] - 2 (the escape symbol) and
+    cost[v] = rint(65536 * (16 - log2(cdf[t][v + 1] - cdf[t][v]))): Q16 bits of a 16-bit-precision rANS step."""
+    cdf = np.ascontiguousarray(cdf, np.int64)
+    sizes = np.ascontiguousarray(cdf_length, np.int64)
+    offset = np.ascontiguousarray(offset, np.int64)
+    n, stride = cdf.shape[0], int(sizes.max())
+    if sizes.min() < 2 or stride > cdf.shape[1] or np.abs(offset).max() >= 1 << 15 or stride - 2 >= 1 << 15:
+        raise DcvcError("cost_table: cdf lengths of 2 .. the row length and 16-bit offsets are needed")
+    freq = cdf[:, 1:stride] - cdf[:, :stride - 1]
+    valid = np.arange(stride - 1)[None, :] < (sizes - 1)[:, None]
+    if (freq[valid] <= 0).any() or (freq[valid] > 1 << 16).any():
+        raise DcvcError("cost_table: a symbol of a quantised cdf has no probability mass")
+    cost = np.rint(65536.0 * (16.0 - np.log2(np.where(valid, freq, 1).astype(np.float64))))
+    out = np.zeros((n, stride), np.uint32)
+    out[:, 0] = (((sizes - 2) << 16) | (offset & 0xffff)).astype(np.uint32)
+    out[:, 1:] = np.where(valid, cost, 0).astype(np.uint32)
+    return out
+
+
 class PinnedBuffer:
     """hipHostMalloc'ed staging buffer viewed as a numpy array."""
 
@@ -177,6 +199,8 @@ class EntropyCoder:
         if not self.enc or not self.dec:
             raise DcvcError("cannot create the rANS coder")
         self._pinned = {}
+        self.two = False             # set_use_two_entropy_coders: the frame's ec_part split
+        self.tables = []             # (cdf, cdf_length, offset) of every group, as add_cdf received them
 
     def __del__(self):
         try:
@@ -209,11 +233,13 @@ class EntropyCoder:
         offset = np.ascontiguousarray(offset, np.int32)
         a = check(L.dcvc_rans_enc_add_cdf(self.enc, _ip(cdf), cdf.shape[0], cdf.shape[1], _ip(cdf_length), _ip(offset)), "add_cdf")
         b = check(L.dcvc_rans_dec_add_cdf(self.dec, _ip(cdf), cdf.shape[0], cdf.shape[1], _ip(cdf_length), _ip(offset)), "add_cdf")
-        assert a == b
+        assert a == b == len(self.tables)
+        self.tables.append((cdf, cdf_length, offset))
         return a
 
     def set_use_two_entropy_coders(self, two):
         L = _lib.lib()
+        self.two = bool(two)
         L.dcvc_rans_enc_set_use_two(self.enc, int(bool(two)))
         L.dcvc_rans_dec_set_use_two(self.dec, int(bool(two)))
 

@@ -45,8 +45,9 @@ def encoder_form(m, chunked):
 class EncodeJob:
     """one frame's symbols on their way to the coder; valid for the host once `ready` has passed.
     hz: pinned z symbols (nz int8).  REFERENCE / CHUNKED_HOST: hp, hc = pinned kept symbols [parts, nsym] int16 and their
-    counts.  CHUNKED_DEVICE: units = one pinned buffer (info + unit) per part, csym = the compacted symbols on the device."""
-    __slots__ = ("form", "ready", "qp", "hz", "nz", "zhw", "parts", "nsym", "log2_s", "hp", "hc", "units", "csym")
+    counts.  CHUNKED_DEVICE: units = one pinned buffer (info + unit) per part, csym = the compacted symbols on the device.
+    est: the pinned words of dcvc_rate_estimate (None unless the model's rate_estimate is set), two: the ec_part split."""
+    __slots__ = ("form", "ready", "qp", "hz", "nz", "zhw", "parts", "nsym", "log2_s", "hp", "hc", "units", "csym", "est", "two")
 
 
 def stage(m, key, form, z8, packed, qp, zhw):
@@ -59,7 +60,8 @@ def stage(m, key, form, z8, packed, qp, zhw):
     job.form, job.qp, job.zhw, job.log2_s = form, qp, zhw, m.chunk_log2
     job.parts, job.nsym = packed.shape
     job.nz = nz = z8.numel()
-    job.hp = job.hc = job.units = job.csym = None
+    job.hp = job.hc = job.units = job.csym = job.est = None
+    job.two = ec.two
     parts, nsym, dev = job.parts, job.nsym, packed.device
     job.hz = ec.pinned(key + "_z", (nz + 3) // 4 * 4)
     if nz % 4 == 0:
@@ -86,9 +88,86 @@ def stage(m, key, form, z8, packed, qp, zhw):
             coder.encode_y(L._p(job.csym[k]), ctypes.c_void_p(ccnt.data_ptr() + 4 * k), nsym, log2_s, L._p(ews), ub, m._stream(),
                            slot_bytes=m._slot_bytes)
             job.units.append(ub)
+    if m.rate_estimate:
+        job.est = _enqueue_estimate(m, key, z8, packed, qp, zhw)
     job.ready = torch.cuda.Event()
     job.ready.record()
     return job
+
+
+def _rate_tables(m, dev):
+    """device copies of the two groups' cost tables (entropy.cost_table), uploaded once per update()"""
+    if m._rate_dev is None or m._rate_dev[0].device != dev:
+        g, z = (entropy.cost_table(*m.entropy_coder.tables[k]) for k in (m._g_group, m._z_group))
+        m._rate_dev = tuple(torch.from_numpy(t.view(np.int32)).to(dev) for t in (g, z))
+    return m._rate_dev
+
+
+def _enqueue_estimate(m, key, z8, packed, qp, zhw):
+    """dcvc_rate_estimate on the frame's symbols where the front run left them -> pinned words (per staging set, like the
+    symbols: the host may still be reading the other set's)"""
+    lib, dev = _lib.lib(), packed.device
+    parts, nsym = packed.shape
+    nz = z8.numel()
+    gcost, zcost = _rate_tables(m, dev)
+    out = m.entropy_coder.pinned(key + "_est", 8 * (3 * parts + 2))
+    ws = m._buffer("rate_ws", (int(check(lib.dcvc_rate_estimate_ws_bytes(nsym, parts, nz), "rate_estimate_ws_bytes")) // 8,),
+                   torch.int64, dev)
+    check(lib.dcvc_rate_estimate(L._p(packed), nsym, parts, L._p(gcost), gcost.shape[0], gcost.shape[1], L._p(z8), nz, zhw,
+                                 L._p(zcost), zcost.shape[0], zcost.shape[1], qp * m.z_channel, L._p(ws),
+                                 ctypes.c_void_p(out.ptr), m._stream()), "rate_estimate")
+    return out
+
+
+FLUSH_BYTES = 4          # rans_host.cpp: the coder's 32-bit state, written once per non-empty coder / per chunk
+CHUNK_LEN_BYTES = 2      # the uint16 entry of a chunk in its unit's length table
+
+
+def _varint_bytes(v):
+    """bitstream.write_uint_adaptive"""
+    return 1 if v < 1 << 7 else 2 if v < 1 << 14 else 4
+
+
+def _bytes_of(q16):
+    return -(-int(q16) // (8 << 16))
+
+
+def estimate_words(job):
+    """-> ([(Q16 bits, kept, escapes) per part], (Q16 bits, escapes) of z) once the hand-off has landed"""
+    if job.est is None:
+        raise DcvcError("this frame carries no size estimate: set the model's rate_estimate before compress()")
+    job.ready.synchronize()
+    w = [int(v) for v in job.est.view(np.uint64, 3 * job.parts + 2)]
+    return [tuple(w[3 * p:3 * p + 3]) for p in range(job.parts)], (w[3 * job.parts], w[3 * job.parts + 1])
+
+
+def coders_of(job, kept):
+    """streams that end in a flush: REFERENCE - the non-empty coders of the frame (ec_part = 1 gives the first coder
+    kept / 2 of every part's kept symbols and nz / 2 of z, the second one the rest); chunked - those of the z part plus
+    one per chunk"""
+    nz, halves = job.nz, ((lambda n: (n // 2, n - n // 2)) if job.two else (lambda n: (n,)))
+    z = sum(1 for n in halves(nz) if n)
+    if job.form == REFERENCE:
+        loads = [halves(nz)] + [halves(k) for k in kept]
+        return sum(1 for c in range(len(loads[0])) if any(l[c] for l in loads))
+    return z + sum((k + (1 << job.log2_s) - 1) >> job.log2_s for k in kept)
+
+
+def estimated_bytes(m, job):
+    """Predicted size of the payload code(m, job) returns, known as soon as job.ready has passed (before the host coder
+    has started): ceil(bits / 8) of the device's estimate plus the fixed costs of the job's form.  REFERENCE: FLUSH_BYTES
+    per non-empty coder.  Chunked (entropy.pack_chunked_payload): the log2 S byte, the z part (its coders' flushes) and
+    every unit - a length entry and a flush per chunk - each behind the varint of its size."""
+    ybits, (zbits, _) = estimate_words(job)
+    kept = [k for _, k, _ in ybits]
+    if job.form == REFERENCE:
+        return _bytes_of(zbits + sum(b for b, _, _ in ybits)) + FLUSH_BYTES * coders_of(job, kept)
+    zc = coders_of(job, [])
+    sizes = [_bytes_of(zbits) + FLUSH_BYTES * zc]
+    for b, k, _ in ybits:
+        nch = (k + (1 << job.log2_s) - 1) >> job.log2_s
+        sizes.append(_bytes_of(b) + (FLUSH_BYTES + CHUNK_LEN_BYTES) * nch)
+    return 1 + sum(_varint_bytes(s) + s for s in sizes)
 
 
 def code(m, job):

@@ -350,7 +350,8 @@ def _to_device(planes, device):
 # ---------------------------------------------------------------------------------- one rate point
 def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=None, intra_period=-1,
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
-                  src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4):
+                  src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
+                  target_bpp=None):
     """Encodes `frame_num` frames of a YUV 4:2:0 file (src_type "yuv420"), of a raw file in another pixel format
     (pipeline.PIXEL_FORMATS: "yuv420p10le", "yuv444p", "nv12", "p010le", ...; metrics with data_range = max_val, rec_path in
     the source's format) or of a directory of PNGs ("png": RGB, converted to YCbCr around the codec) into the reference's
@@ -362,7 +363,11 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     this project's extension, NOT readable by the reference; same pictures, slightly larger streams).  scenecut (percent,
     0 = off; 150 is the recommended value) / min_keyint: adaptive I frames at scene cuts found on the device
     (pipeline.SequenceEncoder, analysis.FrameAnalyzer); the log then carries one extra key, scene_cuts - the frames coded
-    as I frames because of a cut - and intra_period / reset_interval count from the most recent I frame."""
+    as I frames because of a cut - and intra_period / reset_interval count from the most recent I frame.  target_bpp (None =
+    off: the fixed qp of the reference's RD sweep): target-bitrate control (ratecontrol.RateController fed by the device's
+    size estimate); qp_i / qp_p are then the starting qp and the log carries target_bpp, rc_qp (the mean qp of the packets)
+    and rc_est_bpp (the mean of what the controller was fed, to hold against ave_all_frame_bpp) - with verbose_json also
+    the per-frame lists frame_rc_qp and frame_rc_est_bpp."""
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics {metrics!r}: 'host' or 'device'")
     if entropy not in ("host", "device"):
@@ -391,6 +396,11 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     t_start = time.time()
     reader = make_reader()
     adaptive = dict(scenecut=scenecut, min_keyint=min_keyint) if scenecut else {}
+    if target_bpp:
+        from .ratecontrol import RateController
+        adaptive["rate"] = RateController(float(target_bpp) * height * width, qp_i if qp_p is None else qp_p, qp_i_init=qp_i)
+    else:
+        i_net.rate_estimate = p_net.rate_estimate = False       # (one pair codes every point)
     enc = SequenceEncoder(i_net, p_net, qp_i, qp_p, intra_period, reset_interval, **adaptive)
     out = io.BytesIO()
     writer = StreamWriter(out)
@@ -473,6 +483,13 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                     avg_encoding_time=avg_e, avg_decoding_time=avg_d)
     if scenecut:
         log["scene_cuts"] = list(enc.scene_cuts)
+    if target_bpp:
+        log["target_bpp"] = float(target_bpp)
+        log["rc_qp"] = float(np.mean(enc.rc_qp))
+        log["rc_est_bpp"] = float(8 * np.sum(enc.rc_est_bytes) / (frame_num * height * width))
+        if verbose_json:
+            log["frame_rc_qp"] = [int(q) for q in enc.rc_qp]
+            log["frame_rc_est_bpp"] = [8 * b / (height * width) for b in enc.rc_est_bytes]
     return log
 
 
@@ -672,7 +689,7 @@ def run_job(nets, job, opts):
                         verbose_json=opts.get("verbose_json", False), device="cuda:0", src_type=job.get("src_type", "yuv420"),
                         calc_ssim=bool(opts.get("calc_ssim")), metrics=opts.get("metrics") or "host",
                         entropy=opts.get("entropy") or "host", scenecut=opts.get("scenecut") or 0,
-                        min_keyint=opts.get("min_keyint") or 4)
+                        min_keyint=opts.get("min_keyint") or 4, target_bpp=target_bpp(opts, job["src_width"], job["src_height"]))
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -701,6 +718,30 @@ def run_config(config, opts, workers=1, gpus=1):
                                                 initargs=(opts, gpus)) as pool:
         results = [f.result() for f in [pool.submit(_worker, j) for j in jobs]]
     return merge_results(config, results)
+
+
+def target_bpp(opts, width, height):
+    """--target-bpp, or --target-kbps with --fps, as bits per pixel of a width x height sequence (None: no rate control)"""
+    if opts.get("target_bpp"):
+        return float(opts["target_bpp"])
+    if opts.get("target_kbps"):
+        return float(opts["target_kbps"]) * 1000.0 / (float(opts["fps"]) * width * height)
+    return None
+
+
+def check_rate_options(args, ap):
+    if args.target_bpp is not None and args.target_kbps is not None:
+        ap.error("--target-bpp and --target-kbps are two spellings of one target: give one")
+    if (args.target_kbps is not None) != (args.fps is not None):
+        ap.error("--target-kbps and --fps go together")
+    if any(v is not None and not v > 0 for v in (args.target_bpp, args.target_kbps, args.fps)):
+        ap.error("--target-bpp / --target-kbps / --fps must be positive")
+    if args.target_bpp is None and args.target_kbps is None:
+        return
+    # one rate point: the controller chooses the qp, --qp-i / --qp-p (default 32) only say where it starts
+    args.qp_i = list(args.qp_i)[:1] if args.qp_i else [32]
+    args.qp_p = list(args.qp_p)[:1] if args.qp_p else list(args.qp_i)
+    args.rate_num = 1
 
 
 def _str2bool(v):
@@ -767,6 +808,11 @@ def build_parser():
                          "--intra-period and --reset-interval then count from the most recent I frame")
     ap.add_argument("--min-keyint", "--min_keyint", type=int, default=4, metavar="N",
                     help="with --scenecut: a cut fewer than N frames after the last I frame is coded as a P frame")
+    ap.add_argument("--target-bpp", "--target_bpp", type=float, default=None, metavar="X",
+                    help="target-bitrate control: aim at X bits per pixel (one rate point; --qp-i / --qp-p give the starting qp)")
+    ap.add_argument("--target-kbps", "--target_kbps", type=float, default=None, metavar="K",
+                    help="the same as a bitrate: K * 1000 / (--fps * width * height) bits per pixel, per sequence")
+    ap.add_argument("--fps", type=float, default=None, metavar="F", help="frame rate of the source, for --target-kbps")
     ap.add_argument("--model-i", "--model_path_i", help="DMCI checkpoint (.pth.tar); synthetic weights if omitted")
     ap.add_argument("--model-p", "--model_path_p", help="DMC checkpoint")
     ap.add_argument("--force-zero-thres", "--force_zero_thres", type=float, default=0.12)
@@ -792,7 +838,8 @@ def manifest_options(args, ap):
                 reset_interval=args.reset_interval, model_i=args.model_i, model_p=args.model_p,
                 force_zero_thres=args.force_zero_thres, fp32=args.fp32, stream_path=stream_path,
                 verbose=args.verbose, verbose_json=args.verbose_json, calc_ssim=args.calc_ssim, metrics=args.metrics,
-                entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint, force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
+                entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint, target_bpp=args.target_bpp,
+                target_kbps=args.target_kbps, fps=args.fps, force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
     return opts, gpus
 
 
@@ -802,6 +849,7 @@ def main(argv=None):
     from .models import DMC, DMCI
     ap = build_parser()
     args = ap.parse_args(argv)
+    check_rate_options(args, ap)
     if args.test_config:
         with open(args.test_config) as f:
             config = json.load(f)
@@ -845,7 +893,8 @@ def main(argv=None):
                     args.qp_i or None, args.qp_p or None, bin_prefix=args.bin_prefix,
                     intra_period=args.intra_period, reset_interval=args.reset_interval, verbose=args.verbose,
                     verbose_json=args.verbose_json, src_type=args.src_type, calc_ssim=args.calc_ssim, metrics=args.metrics,
-                    entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint)
+                    entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint,
+                    target_bpp=target_bpp(vars(args), args.width, args.height))
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:

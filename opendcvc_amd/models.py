@@ -230,6 +230,10 @@ class CompressionModel(tnn.Module):
         self._dev_coder = None
         self._slot_bytes = 0                      # device encoder scratch slot per chunk (0 = the library's default)
         self.dev_fallbacks = 0                    # y units the host had to code after a device overflow flag
+        # rate_estimate = True: every compress() also runs dcvc_rate_estimate on the frame's symbols (two small launches
+        #   behind the hand-off) and returns 'est_bytes', the predicted payload size, known before the host coder starts
+        self.rate_estimate = False
+        self._rate_dev = None                     # device cost tables, uploaded on first use after update()
         self._model_name = model_name
         self.z_channel = z_channel
         self.qp_total = qp_total
@@ -278,6 +282,7 @@ class CompressionModel(tnn.Module):
         self._g_tables = entropy.gaussian_cdf_tables()
         self._g_group = self.entropy_coder.add_cdf(*self._g_tables)
         self._dev_coder = None                    # device tables of the same group, built on first use (needs the GPU)
+        self._rate_dev = None
         sd = self.state_dict()
         pre = "bit_estimator_z."
         params = {k[len(pre):]: v.detach().float().cpu() for k, v in sd.items() if k.startswith(pre)}
@@ -771,6 +776,8 @@ class DMC(CompressionModel):
         self._ahead = nxt
         # ("chunked" is present only for chunked payloads and tells the mode of THIS frame's stream, whichever call hands it out)
         mode = {} if form == handoff.REFERENCE else {"chunked": True}
+        if job.est is not None:      # (the hand-off has landed long before the host coder above is done)
+            mode["est_bytes"] = handoff.estimated_bytes(self, job)
         if defer_stream:
             self._stream_pending = job
             return dict({"bit_stream": None, "bit_stream_prev": prev}, **mode)
@@ -970,6 +977,8 @@ class DMCI(CompressionModel):
         x_hat = self._picture_out(self._graphs.run(("ienc_back",) + key, lambda: self._dec(y_hat, q["q_scale_dec"])))
 
         res = {"bit_stream": handoff.code(self, job), "x_hat": x_hat}
+        if job.est is not None:
+            res["est_bytes"] = handoff.estimated_bytes(self, job)
         return res if form == handoff.REFERENCE else dict(res, chunked=True)
 
     @_frame_scoped

@@ -32,10 +32,17 @@ class SequenceEncoder:
     intra_period = -1, or an intra_period that is a multiple of 8 and of reset_interval.  scene_cuts lists the frames
     whose cut was honoured with an I frame (also where the period asked for one at the same frame).  encode(x, ready):
     `ready` is a torch.cuda.Event recorded where x became ready, so the analysis need not wait for the kernels of the
-    previous frame that defer_stream keeps in flight.  analyzer: any object with analyze(x, ready) -> FrameStats."""
+    previous frame that defer_stream keeps in flight.  analyzer: any object with analyze(x, ready) -> FrameStats.
+
+    rate (a ratecontrol.RateController, None = off: the fixed qp_i / qp_p above, nothing launched): target-bitrate control.
+    Both models then estimate every frame's payload size on the device (their rate_estimate attribute is set); before a
+    frame's qp is chosen the controller is fed the previous frame's estimate plus the container's bytes - the same number
+    with and without defer_stream, since it never waits for the exact stream - and gives the base qp: a P frame is coded at
+    shift_qp(base, INDEX_MAP[g % 8]), an I frame at rate.i_qp(base).  Per frame: rc_qp (the qp in the packet), rc_est_bytes
+    (what the controller was fed) and rc_bytes (payload + container bytes, filled in when the packet comes out)."""
 
     def __init__(self, i_net, p_net, qp_i, qp_p=None, intra_period=-1, reset_interval=32, defer_stream=False,
-                 scenecut=None, min_keyint=4, analyzer=None):
+                 scenecut=None, min_keyint=4, analyzer=None, rate=None):
         self.i_net, self.p_net = i_net, p_net
         self.defer = defer_stream
         self._held = None            # (qp, use_ada_i, chunked) of the P frame whose stream is still pending
@@ -52,14 +59,47 @@ class SequenceEncoder:
         self._analyzer = analyzer if self.scenecut else None      # (made at the first frame, on the frame's device)
         self._gop_pos = 0            # g of the previous frame
         self.scene_cuts = []
+        self.rate = rate
+        self.rc_qp, self.rc_est_bytes, self.rc_bytes = [], [], []
+        self._rc_pending = None      # (class, base qp, estimated bytes) of the frame coded last, not yet fed back
+        self._rc_out = 0             # packets handed out so far (their order is the frame order)
+        if rate is not None:
+            i_net.rate_estimate = p_net.rate_estimate = True
         p_net.set_curr_poc(0)
 
     def encode(self, x_padded, ready=None):
         from .models import CAPTURE_GUARD
         with CAPTURE_GUARD.frame():          # (a HIP graph capture on another thread waits for / holds back this frame)
             if self.scenecut:
-                return self._encode_adaptive(x_padded, ready)
-            return self._encode(x_padded)
+                return self._sized(self._encode_adaptive(x_padded, ready))
+            return self._sized(self._encode(x_padded))
+
+    def _sized(self, pkts):
+        """rate control's log: the exact size of every packet handed out (never fed back to the controller)"""
+        if self.rate is not None:
+            from .bitstream import frame_overhead_bytes
+            for pkt in (pkts if isinstance(pkts, list) else [pkts]):
+                n = len(pkt.bit_stream)
+                self.rc_bytes.append(n + frame_overhead_bytes(n))
+                self.rate.record_exact(self._rc_out, n)
+                self._rc_out += 1
+        return pkts
+
+    def _rc_base(self):
+        """feeds the previous frame's estimate to the controller and returns the base qp of this frame"""
+        if self._rc_pending is not None:
+            klass, base, est = self._rc_pending
+            self.rate.observe(klass, base, 8 * est)
+            self._rc_pending = None
+        return self.rate.base_qp()
+
+    def _rc_note(self, klass, base, qp, enc):
+        from .bitstream import frame_overhead_bytes
+        est = int(enc["est_bytes"])          # (compress() has waited for the hand-off's event, not for the host coder)
+        est += frame_overhead_bytes(est)
+        self._rc_pending = (klass, base, est)
+        self.rc_qp.append(qp)
+        self.rc_est_bytes.append(est)
 
     def _take_held(self, stream):
         out = []
@@ -93,17 +133,25 @@ class SequenceEncoder:
         """pos: what the P-frame rules count - the frame index (the reference), or the distance to the last I frame"""
         if is_i:
             done = self._take_held(self.p_net.finish_stream()) if self.defer else []
-            enc = self.i_net.compress(x_padded, self.qp_i)
+            base = self._rc_base() if self.rate is not None else None
+            qp_i = self.qp_i if base is None else self.rate.i_qp(base)
+            enc = self.i_net.compress(x_padded, qp_i)
+            if base is not None:
+                from .ratecontrol import I_CLASS
+                self._rc_note(I_CLASS, base, qp_i, enc)
             self.p_net.clear_dpb()
             self.p_net.add_ref_frame(None, enc["x_hat"])
-            pkt = FramePacket(True, self.qp_i, 0, enc["bit_stream"], chunked=bool(enc.get("chunked", False)))
+            pkt = FramePacket(True, qp_i, 0, enc["bit_stream"], chunked=bool(enc.get("chunked", False)))
             return done + [pkt] if self.defer else pkt
         use_ada_i = 0
         if self.reset_interval > 0 and pos % self.reset_interval == 1:
             use_ada_i = 1
             self.p_net.prepare_feature_adaptor_i(self.last_qp)
-        qp = self.p_net.shift_qp(self.qp_p, INDEX_MAP[pos % 8])
+        base = self._rc_base() if self.rate is not None else self.qp_p
+        qp = self.p_net.shift_qp(base, INDEX_MAP[pos % 8])
         enc = self.p_net.compress(x_padded, qp, defer_stream=self.defer)
+        if self.rate is not None:
+            self._rc_note(INDEX_MAP[pos % 8], base, qp, enc)
         self.last_qp = qp
         chunked = bool(enc.get("chunked", False))         # (the models' entropy="device" mode: NAL_*_CHUNKED)
         if not self.defer:
@@ -116,7 +164,7 @@ class SequenceEncoder:
         """defer_stream: the packet still pending (empty list otherwise)"""
         from .models import CAPTURE_GUARD
         with CAPTURE_GUARD.frame():
-            return self._take_held(self.p_net.finish_stream()) if self.defer else []
+            return self._sized(self._take_held(self.p_net.finish_stream()) if self.defer else [])
 
 
 class SequenceDecoder:
