@@ -900,9 +900,13 @@ struct DevBuf {
     }
 };
 
-// get(n, k) -> logical weight (0 outside the logical range)
+// A weight matrix as the packers see it: W(n, k) = the logical weight at physical row n, column k (0 outside the logical
+// range); a conv's taps: W(n, tap, k)
+using Mat = std::function<float(int, int)>;
+using Taps = std::function<float(int, int, int)>;
+
 template <typename T>
-int pack_upload(DevBuf& dst, int Np, int Kp, const std::function<float(int, int)>& get)
+int pack_upload(DevBuf& dst, int Np, int Kp, const Mat& get)
 {
     const int kgs = Kp / KG, nt = Np / 16;
     std::vector<T> buf((size_t)nt * kgs * 64 * 8);
@@ -918,7 +922,7 @@ int pack_upload(DevBuf& dst, int Np, int Kp, const std::function<float(int, int)
     return dst.upload(buf.data(), buf.size() * sizeof(T));
 }
 
-int pack_any(int dtype, DevBuf& dst, int Np, int Kp, const std::function<float(int, int)>& get)
+int pack_any(int dtype, DevBuf& dst, int Np, int Kp, const Mat& get)
 {
     return dtype == DCVC_F16 ? pack_upload<half_t>(dst, Np, Kp, get) : pack_upload<float>(dst, Np, Kp, get);
 }
@@ -965,22 +969,6 @@ size_t head_lds(int kstage, int c, bool adapt)    // kstage: input channels stag
     const int kx = kstage > c ? kstage : c;
     return (size_t)Tile<MT>::M * ((kx + Traits<T>::kPad) + (adapt ? c + Traits<T>::kPad : 0)) * sizeof(T);
 }
-template <typename T, int MT, int NTW, int NW>
-size_t tail_lds(int c)
-{
-    return TailLds<T, MT, TailCfg<MT, NTW, NW>::NTV, NW>::bytes(c);
-}
-
-template <typename T, int MT, int NTW, int NW, bool RAG = false, bool HEADIN = false>
-int launch_tail(const TailParams& tp, int grid, int C, hipStream_t st)
-{
-    const size_t lds = TailLds<T, MT, TailCfg<MT, NTW, NW>::NTV, NW>::bytes(C, HEADIN);
-    int rc = set_lds(dcb_tail_kernel<T, MT, NTW, NW, RAG, HEADIN>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((dcb_tail_kernel<T, MT, NTW, NW, RAG, HEADIN>), dim3(grid), dim3(NW * 64), lds, st, tp);
-    return 0;
-}
-
 template <typename K>
 int set_lds(K kernel, size_t bytes)
 {
@@ -1003,32 +991,37 @@ int set_lds(K kernel, size_t bytes)
 }
 
 
-// ---- dcb_tail128_kernel: weight streams (one per wave, 1 KiB fragments of v_mfma_f32_32x32x16_f16's A operand in the
-// order the wave consumes them) and launch
+// ---- fragment streams: the weights of the kernels in dcb_t128.hpp as 1 KiB fragments of v_mfma_f32_32x32x16_f16's A operand,
+// in the order a wave consumes them
+// One fragment: rows row(0..31) x k-step s of W.  The only place that knows the lane layout: lane l holds row l & 31,
+// columns 16 s + 8 (l >> 5) + [0, 8)
+template <typename F, typename R>
+void put_frag(half_t* o, F&& W, R&& row, int s)
+{
+    for (int l = 0; l < 64; ++l)
+        for (int j = 0; j < 8; ++j) o[l * 8 + j] = (half_t)W(row(l & 31), 16 * s + 8 * (l >> 5) + j);
+}
+
+// dcb_tail128_kernel: W2 | W3 | W4, one stream per wave
 template <int C>
-int pack_t128(DevBuf& dst, const std::function<float(int, int)>& W2, const std::function<float(int, int)>& W3,
-              const std::function<float(int, int)>& W4)
+int pack_t128(DevBuf& dst, const Mat& W2, const Mat& W3, const Mat& W4)
 {
     using CF = t128::Wcfg<C>;
     std::vector<half_t> buf((size_t)4 * CF::STREAM * 512, (half_t)0.f);
     for (int wave = 0; wave < 4; ++wave) {
         size_t f = 0;
-        auto put = [&](const std::function<float(int, int)>& get, const std::function<int(int)>& row, int s) {
-            half_t* o = &buf[((size_t)wave * CF::STREAM + f) * 512];
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) o[l * 8 + j] = (half_t)get(row(l & 31), 16 * s + 8 * (l >> 5) + j);
-            ++f;
-        };
+        auto next = [&] { return &buf[((size_t)wave * CF::STREAM + f++) * 512]; };
+        auto tile = [&](int i) { return [=](int r) { return 32 * (wave + 4 * i) + r; }; };
         auto g3 = [&](int j) {   // u tile of chunk j: 16 u_lo rows | the 16 u_hi rows they pair with (physical halves 2 C wide)
             for (int s = 0; s < CF::KS; ++s)
-                put(W3, [&](int r) { return (r < 16 ? 0 : 2 * C - 16) + 64 * j + 16 * wave + r; }, s);
+                put_frag(next(), W3, [&](int r) { return (r < 16 ? 0 : 2 * C - 16) + 64 * j + 16 * wave + r; }, s);
         };
         auto g4 = [&](int j) {
             for (int s4 = 0; s4 < 4; ++s4)
-                for (int i = 0; i < CF::NTW; ++i) put(W4, [&](int r) { return 32 * (wave + 4 * i) + r; }, 4 * j + s4);
+                for (int i = 0; i < CF::NTW; ++i) put_frag(next(), W4, tile(i), 4 * j + s4);
         };
         for (int s = 0; s < CF::KS; ++s)
-            for (int i = 0; i < CF::NTW; ++i) put(W2, [&](int r) { return 32 * (wave + 4 * i) + r; }, s);
+            for (int i = 0; i < CF::NTW; ++i) put_frag(next(), W2, tile(i), s);
         g3(0);
         for (int j = 0; j < CF::NCH; ++j) {
             if (j >= 1) g4(j - 1);
@@ -1045,63 +1038,21 @@ int pack_t128(DevBuf& dst, const std::function<float(int, int)>& W2, const std::
 
 inline bool t128_width_ok(int c_p) { return c_p == 128 || c_p == 256 || c_p == 320 || c_p == 384 || c_p == 512; }   // (128, 512: 32-pixel tiles only)
 
-// a C x C matrix (next block's first conv, a fused 1x1 conv) as the per-quarter fragment stream gemm_c reads
-template <int C>
-int pack_t128_square(DevBuf& dst, const std::function<float(int, int)>& W)
+// The per-quarter streams of every other kernel: `nsl` slices of 128 ntw output channels x 4 channel quarters (tile i of
+// quarter cq = rows 32 (cq + 4 i) of the slice), each stream in (tap, k-step, tile) order with `padf` dummy fragments behind
+// it.  (Width 320: one slice of ntw = 3, whose two missing tiles pack as the zeros W gives there.)
+inline int pack_quarters(DevBuf& dst, int nsl, int ntw, int taps, int ks, int padf, const Taps& W)
 {
-    using CF = t128::Wcfg<C>;
-    constexpr int LEN = CF::KS * CF::NTW + t128::PADF;
-    std::vector<half_t> buf((size_t)4 * LEN * 512, (half_t)0.f);
-    for (int cq = 0; cq < 4; ++cq) {
-        size_t f = 0;
-        for (int s = 0; s < CF::KS; ++s)
-            for (int i = 0; i < CF::NTW; ++i, ++f) {
-                half_t* o = &buf[((size_t)cq * LEN + f) * 512];
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 8; ++j) o[l * 8 + j] = (half_t)W(32 * (cq + 4 * i) + (l & 31), 16 * s + 8 * (l >> 5) + j);
-            }
-    }
-    return dst.upload(buf.data(), buf.size() * sizeof(half_t));
-}
-
-// a C x K matrix (the adaptor: K = padded input channels) in the same form: K / 16 k-steps
-template <int C>
-int pack_t128_rect(DevBuf& dst, int Kp, const std::function<float(int, int)>& W)
-{
-    using CF = t128::Wcfg<C>;
-    const int ks = Kp / 16, LEN = ks * CF::NTW + t128::PADF;
-    std::vector<half_t> buf((size_t)4 * LEN * 512, (half_t)0.f);
-    for (int cq = 0; cq < 4; ++cq) {
-        size_t f = 0;
-        for (int s = 0; s < ks; ++s)
-            for (int i = 0; i < CF::NTW; ++i, ++f) {
-                half_t* o = &buf[((size_t)cq * LEN + f) * 512];
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 8; ++j) o[l * 8 + j] = (half_t)W(32 * (cq + 4 * i) + (l & 31), 16 * s + 8 * (l >> 5) + j);
-            }
-    }
-    return dst.upload(buf.data(), buf.size() * sizeof(half_t));
-}
-
-// a conv with `taps` taps, Np / (128 ntw) slices x 4 quarters: fragments in (tap, k-step, tile) order, `padf` dummy fragments
-// behind every quarter stream; W(n, tap, ci) = physical row n
-inline int pack_t128_conv(DevBuf& dst, int ntw, int taps, int padf, int Np, int Kp, const std::function<float(int, int, int)>& W)
-{
-    const int slice = 128 * ntw;
-    const int ks = Kp / 16, LEN = taps * ks * ntw + padf, nsl = Np / slice;
+    const int LEN = taps * ks * ntw + padf;
     std::vector<half_t> buf((size_t)nsl * 4 * LEN * 512, (half_t)0.f);
-    for (int sl = 0; sl < nsl; ++sl)
-        for (int cq = 0; cq < 4; ++cq) {
-            size_t f = 0;
-            for (int tap = 0; tap < taps; ++tap)
-                for (int s = 0; s < ks; ++s)
-                    for (int i = 0; i < ntw; ++i, ++f) {
-                        half_t* o = &buf[(((size_t)sl * 4 + cq) * LEN + f) * 512];
-                        for (int l = 0; l < 64; ++l)
-                            for (int j = 0; j < 8; ++j)
-                                o[l * 8 + j] = (half_t)W(sl * slice + 32 * (cq + 4 * i) + (l & 31), tap, 16 * s + 8 * (l >> 5) + j);
-                    }
-        }
+    for (int q = 0; q < nsl * 4; ++q) {
+        half_t* o = &buf[(size_t)q * LEN * 512];
+        for (int tap = 0; tap < taps; ++tap)
+            for (int s = 0; s < ks; ++s)
+                for (int i = 0; i < ntw; ++i, o += 512)
+                    put_frag(o, [&](int n, int k) { return W(n, tap, k); },
+                             [&](int r) { return (q / 4) * 128 * ntw + 32 * (q % 4 + 4 * i) + r; }, s);
+    }
     return dst.upload(buf.data(), buf.size() * sizeof(half_t));
 }
 
@@ -1119,9 +1070,12 @@ int visit_t128_width(int c_p, F&& f)
     }
 }
 
-inline int pack_t128_square_any(int c_p, DevBuf& dst, const std::function<float(int, int)>& W)
+// a c_p x Kp matrix (a block's W1, a fused 1x1 conv, the adaptor) as the stream gemm_c reads: one slice, one tap
+inline int pack_t128_matrix(DevBuf& dst, int c_p, int Kp, const Mat& W)
 {
-    return visit_t128_width(c_p, [&](auto w) { return pack_t128_square<decltype(w)::value>(dst, W); });
+    return visit_t128_width(c_p, [&](auto w) {
+        return pack_quarters(dst, 1, t128::Wcfg<decltype(w)::value>::NTW, 1, Kp / 16, t128::PADF, [&](int n, int, int k) { return W(n, k); });
+    });
 }
 
 // Developer switches, read once per process.  DCVC_T128=0, DCVC_T32=0, DCVC_H128=0 and DCVC_C128=0 select the reference
@@ -1158,6 +1112,9 @@ static const Switches& switches()
     return sw;
 }
 
+// workgroups of a th x tw pixel tile over an H x W map
+constexpr int tile_grid(int H, int W, int th, int tw) { return ((H + th - 1) / th) * ((W + tw - 1) / tw); }
+
 template <typename K, typename P>
 int launch_kernel(K kernel, dim3 grid, int threads, size_t lds, hipStream_t st, const P& p)
 {
@@ -1190,37 +1147,88 @@ static int stamp_medians(unsigned long long* d, int grid, int per, const char* c
     }
     return 0;
 }
+
+// The two tails launched with in-kernel phase stamps: the medians over the workgroups go to stderr
+template <int C, class G, bool HEADIN>
+int stamped_tail128(TailParams tp, int grid, size_t lds, hipStream_t st)
+{
+    DCVC_HIP(hipMalloc(&tp.stamps, (size_t)grid * 16 * sizeof(unsigned long long)));
+    int rc = launch_kernel(t128::dcb_tail128_kernel<C, G, HEADIN>, dim3(grid), t128::Geo<G>::NTHR, lds, st, tp);
+    if (rc) return rc;
+    const char* names[16] = {"loads+dw", "gemm2", "o_pass", "u0", "ffn", "r+store", nullptr, nullptr, "dw:issue+stage0",
+                             "barrier0", "slab0", "slab1", "slab2", "slab3", "fused", nullptr};
+    for (int k = C / G::DW_SLAB; k < 4; ++k) names[10 + k] = nullptr;    // the kernel stamps min(slabs, 4) slabs
+    char tag[64];
+    snprintf(tag, sizeof tag, "t128 stamps C=%d tile=%d grid=%d", C, t128::Geo<G>::M, grid);
+    static int calls = 0;
+    std::vector<unsigned long long> hs;
+    bool printed = false;
+    rc = stamp_medians(tp.stamps, grid, 16, names, tag, calls, st, hs, printed);
+    if (rc || !printed) return rc;
+    std::vector<unsigned long long> du(grid);
+    for (int b = 0; b < grid; ++b) du[b] = hs[(size_t)b * 16 + 7] - hs[(size_t)b * 16 + 6];
+    std::sort(du.begin(), du.end());
+    fprintf(stderr, " | wg total min/med/max %llu %llu %llu\n", du[0], du[grid / 2], du[grid - 1]);
+    return 0;
+}
+
+template <int MT, typename K>
+int stamped_tail(K kernel, int threads, TailParams tp, int grid, size_t lds, hipStream_t st)
+{
+    DCVC_HIP(hipMalloc(&tp.stamps, (size_t)grid * 8 * sizeof(unsigned long long)));
+    int rc = launch_kernel(kernel, dim3(grid), threads, lds, st, tp);
+    if (rc) return rc;
+    const char* names[8] = {"dw", "gemm2", "o_pass", "gemm3", "ffn_epi", "gemm4", "final", "total"};
+    char tag[64];
+    snprintf(tag, sizeof tag, "stamps C=%d MT=%d grid=%d", tp.C, MT, grid);
+    static int calls = 0;
+    std::vector<unsigned long long> hs;
+    bool printed = false;
+    rc = stamp_medians(tp.stamps, grid, 8, names, tag, calls, st, hs, printed);
+    if (rc || !printed) return rc;
+    fprintf(stderr, "\n");
+    if (tp.ablate & 16) {   // the kernel stored absolute start / end stamps instead of two phase counters
+        unsigned long long t0 = ~0ull, t1 = 0;
+        for (int b = 0; b < grid; ++b) {
+            t0 = std::min(t0, hs[(size_t)b * 8]);
+            t1 = std::max(t1, hs[(size_t)b * 8 + 1]);
+        }
+        std::vector<unsigned long long> s(grid), e(grid), du(grid);
+        for (int b = 0; b < grid; ++b) {
+            s[b] = hs[(size_t)b * 8] - t0;
+            e[b] = hs[(size_t)b * 8 + 1] - t0;
+            du[b] = hs[(size_t)b * 8 + 7];
+        }
+        std::sort(s.begin(), s.end());
+        std::sort(e.begin(), e.end());
+        std::sort(du.begin(), du.end());
+        fprintf(stderr, "[span %llu] start min/med/p90/max %llu %llu %llu %llu | end med/p90/max %llu %llu %llu | dur min/med/p90/max %llu %llu %llu %llu\n",
+                t1 - t0, s[0], s[grid / 2], s[grid * 9 / 10], s[grid - 1], e[grid / 2], e[grid * 9 / 10],
+                e[grid - 1], du[0], du[grid / 2], du[grid * 9 / 10], du[grid - 1]);
+    }
+    return 0;
+}
 #endif
 
 template <int C, class G = t128::G128, bool HEADIN = false>
 int launch_tail128(const TailParams& tp, int H, int W, hipStream_t st)
 {
-    const int grid = ((H + G::TH - 1) / G::TH) * ((W + G::TW - 1) / G::TW);
+    const int grid = tile_grid(H, W, G::TH, G::TW);
     const size_t lds = t128::Cfg<C, G, HEADIN>::LDS;
-#ifdef DCVC_DIAG      // developer build only (make diag): in-kernel phase stamps, median over the workgroups
-    if (switches().stamps) {
-        TailParams q = tp;
-        DCVC_HIP(hipMalloc(&q.stamps, (size_t)grid * 16 * sizeof(unsigned long long)));
-        int rc = launch_kernel(t128::dcb_tail128_kernel<C, G, HEADIN>, dim3(grid), t128::Geo<G>::NTHR, lds, st, q);
-        if (rc) return rc;
-        const char* names[16] = {"loads+dw", "gemm2", "o_pass", "u0", "ffn", "r+store", nullptr, nullptr, "dw:issue+stage0",
-                                 "barrier0", "slab0", "slab1", "slab2", "slab3", "fused", nullptr};
-        for (int k = C / G::DW_SLAB; k < 4; ++k) names[10 + k] = nullptr;    // the kernel stamps min(slabs, 4) slabs
-        char tag[64];
-        snprintf(tag, sizeof tag, "t128 stamps C=%d tile=%d grid=%d", C, t128::Geo<G>::M, grid);
-        static int calls = 0;
-        std::vector<unsigned long long> hs;
-        bool printed = false;
-        rc = stamp_medians(q.stamps, grid, 16, names, tag, calls, st, hs, printed);
-        if (rc || !printed) return rc;
-        std::vector<unsigned long long> du(grid);
-        for (int b = 0; b < grid; ++b) du[b] = hs[(size_t)b * 16 + 7] - hs[(size_t)b * 16 + 6];
-        std::sort(du.begin(), du.end());
-        fprintf(stderr, " | wg total min/med/max %llu %llu %llu\n", du[0], du[grid / 2], du[grid - 1]);
-        return 0;
-    }
+#ifdef DCVC_DIAG
+    if (switches().stamps) return stamped_tail128<C, G, HEADIN>(tp, grid, lds, st);
 #endif
     return launch_kernel(t128::dcb_tail128_kernel<C, G, HEADIN>, dim3(grid), t128::Geo<G>::NTHR, lds, st, tp);
+}
+
+template <typename T, int MT, int NTW, int NW, bool RAG = false, bool HEADIN = false>
+int launch_tail(const TailParams& tp, int grid, int C, hipStream_t st)
+{
+    const size_t lds = TailLds<T, MT, TailCfg<MT, NTW, NW>::NTV, NW>::bytes(C, HEADIN);
+#ifdef DCVC_DIAG
+    if (switches().stamps) return stamped_tail<MT>(dcb_tail_kernel<T, MT, NTW, NW, RAG, HEADIN>, NW * 64, tp, grid, lds, st);
+#endif
+    return launch_kernel(dcb_tail_kernel<T, MT, NTW, NW, RAG, HEADIN>, dim3(grid), NW * 64, lds, st, tp);
 }
 
 // chained launches: this block's `a` lives in scratch slot a_slot (already there if head_done: the previous
@@ -1366,7 +1374,7 @@ int launch_dcb(const DcbPlan& pl, const dcvc_dcb* h, const SrcPair& src, int H, 
     constexpr bool f16 = sizeof(T) == 2;
     using G = typename std::conditional<MT == 4, t128::G128, t128::G32>::type;
     const int C = h->c_p;
-    const int grid = ((H + Tile<MT>::TH - 1) / Tile<MT>::TH) * ((W + Tile<MT>::TW - 1) / Tile<MT>::TW);
+    const int grid = tile_grid(H, W, Tile<MT>::TH, Tile<MT>::TW);
     const size_t P = (size_t)H * W;
     T* slots = reinterpret_cast<T*>(scratch);           // [a slot 0 | a slot 1 | x' of an adaptor block]
     T* a_buf = slots + (size_t)(ch.a_slot & 1) * P * C;
@@ -1438,7 +1446,7 @@ int launch_dcb(const DcbPlan& pl, const dcvc_dcb* h, const SrcPair& src, int H, 
     int rc = 0;
     if (pl.head == DcbPlan::Head::head128) {
         if constexpr (has_head128(f16, MT, NTW)) {
-            const dim3 g128(((H + G::TH - 1) / G::TH) * ((W + G::TW - 1) / G::TW));
+            const dim3 g128(tile_grid(H, W, G::TH, G::TW));
             const size_t lds = t128::HeadCfg<NTW * 64, G>::LDS;
             rc = pl.head_adapt ? launch_kernel(t128::dcb_head128_kernel<NTW * 64, true, G>, g128, t128::Geo<G>::NTHR, lds, st, hp)
                                : launch_kernel(t128::dcb_head128_kernel<NTW * 64, false, G>, g128, t128::Geo<G>::NTHR, lds, st, hp);
@@ -1450,7 +1458,7 @@ int launch_dcb(const DcbPlan& pl, const dcvc_dcb* h, const SrcPair& src, int H, 
         if (!pl.head_adapt) {
             rc = launch_kernel(dcb_head_kernel<T, MT, NTW, false>, dim3(grid), NTHREADS, head_lds<T, MT>(kstage, C, false), st, hp);
         } else if (pl.head_t32) {
-            const int grid2 = ((H + Tile<2>::TH - 1) / Tile<2>::TH) * ((W + Tile<2>::TW - 1) / Tile<2>::TW);
+            const int grid2 = tile_grid(H, W, Tile<2>::TH, Tile<2>::TW);
             rc = launch_kernel(dcb_head_kernel<T, 2, NTW, true>, dim3(grid2), NTHREADS, head_lds<T, 2>(kstage, C, true), st, hp);
         } else {
             rc = launch_kernel(dcb_head_kernel<T, MT, NTW, true>, dim3(grid), NTHREADS, head_lds<T, MT>(kstage, C, true), st, hp);
@@ -1468,54 +1476,17 @@ int launch_dcb(const DcbPlan& pl, const dcvc_dcb* h, const SrcPair& src, int H, 
             if constexpr (has_tail128(f16, MT, NTW, false)) rc = launch_tail128<NTW * 64, G>(tp, H, W, st);
             else rc = not_built("dcb_tail128_kernel", pl);
         }
-        if (rc) return rc;
-        DCVC_LAUNCH_CHECK();
     } else {
         constexpr TailForm F = tail_form(f16, NTW);
-#ifdef DCVC_DIAG      // developer build only (make diag): in-kernel phase stamps, median over the workgroups
-        if (switches().stamps) DCVC_HIP(hipMalloc(&tp.stamps, (size_t)grid * 8 * sizeof(unsigned long long)));
-#endif
         if (pl.headin) {
             if constexpr (has_tail_headin(f16, MT, NTW)) rc = launch_tail<T, MT, F.ntw, F.nw, F.rag, true>(tp, grid, C, st);
             else rc = not_built("dcb_tail_kernel<..., HEADIN>", pl);
         } else {
             rc = launch_tail<T, MT, F.ntw, F.nw, F.rag>(tp, grid, C, st);
         }
-        if (rc) return rc;
-        DCVC_LAUNCH_CHECK();
-#ifdef DCVC_DIAG
-        if (tp.stamps) {
-            const char* names[8] = {"dw", "gemm2", "o_pass", "gemm3", "ffn_epi", "gemm4", "final", "total"};
-            char tag[64];
-            snprintf(tag, sizeof tag, "stamps C=%d MT=%d grid=%d", C, MT, grid);
-            static int calls = 0;
-            std::vector<unsigned long long> hs;
-            bool printed = false;
-            rc = stamp_medians(tp.stamps, grid, 8, names, tag, calls, st, hs, printed);
-            if (rc) return rc;
-            if (printed) fprintf(stderr, "\n");
-            if (printed && (tp.ablate & 16)) {   // the kernel stored absolute start / end stamps instead of two phase counters
-                unsigned long long t0 = ~0ull, t1 = 0;
-                for (int b = 0; b < grid; ++b) {
-                    t0 = std::min(t0, hs[(size_t)b * 8]);
-                    t1 = std::max(t1, hs[(size_t)b * 8 + 1]);
-                }
-                std::vector<unsigned long long> s(grid), e(grid), du(grid);
-                for (int b = 0; b < grid; ++b) {
-                    s[b] = hs[(size_t)b * 8] - t0;
-                    e[b] = hs[(size_t)b * 8 + 1] - t0;
-                    du[b] = hs[(size_t)b * 8 + 7];
-                }
-                std::sort(s.begin(), s.end());
-                std::sort(e.begin(), e.end());
-                std::sort(du.begin(), du.end());
-                fprintf(stderr, "[span %llu] start min/med/p90/max %llu %llu %llu %llu | end med/p90/max %llu %llu %llu | dur min/med/p90/max %llu %llu %llu %llu\n",
-                        t1 - t0, s[0], s[grid / 2], s[grid * 9 / 10], s[grid - 1], e[grid / 2], e[grid * 9 / 10],
-                        e[grid - 1], du[0], du[grid / 2], du[grid * 9 / 10], du[grid - 1]);
-            }
-        }
-#endif
     }
+    if (rc) return rc;
+    DCVC_LAUNCH_CHECK();
     if (ev) DCVC_HIP(hipEventRecord(ev[2], st));
     return 0;
 }
@@ -1549,7 +1520,7 @@ static int run_dcb(const dcvc_dcb* h, const SrcPair& src, int H, int W, const fl
 template <typename T, int MT, int NTW>
 int launch_conv(const ConvParams& cp, hipStream_t st)
 {
-    const int grid = ((cp.Ho + Tile<MT>::TH - 1) / Tile<MT>::TH) * ((cp.Wo + Tile<MT>::TW - 1) / Tile<MT>::TW);
+    const int grid = tile_grid(cp.Ho, cp.Wo, Tile<MT>::TH, Tile<MT>::TW);
     const size_t row = (size_t)(cp.src.c0 + cp.src.c1 + Traits<T>::kPad) * sizeof(T);
     size_t lds = (size_t)Tile<MT>::M * row;
     ConvParams p = cp;
@@ -1598,7 +1569,7 @@ static ConvPlan plan_conv(const dcvc_conv* h, const ConvParams& cp)
     } else if (h->dtype == DCVC_F16 && h->w_c128[0].p != nullptr && sw.c128 && cp.src.c1 == 0 && cp.in_q == nullptr) {
         // 3x3 s1 convs: conv3x3_t128_kernel, 256-channel slices at one workgroup per CU if that grid runs in one round,
         // else 128-channel slices at two per CU
-        const int tiles = ((cp.H + t128::TH - 1) / t128::TH) * ((cp.W + t128::TW - 1) / t128::TW);
+        const int tiles = tile_grid(cp.H, cp.W, t128::TH, t128::TW);
         pl.kind = ConvPlan::Kind::c3_t128;
         pl.ntw = tiles * (cp.N / 256) <= 256 ? 2 : 1;
     } else {
@@ -1635,7 +1606,7 @@ static int run_conv(const dcvc_conv* h, const ConvParams& cp, hipStream_t st)
         p.out = cp.out;
         p.ldo = cp.ldo;
         const size_t lds = t128::conv_s2_lds(p.kin, p.k, pl.ntw);
-        const dim3 g(((cp.Ho + t128::S2_TH - 1) / t128::S2_TH) * ((cp.Wo + t128::S2_TW - 1) / t128::S2_TW));
+        const dim3 g(tile_grid(cp.Ho, cp.Wo, t128::S2_TH, t128::S2_TW));
         rc = pl.ntw == 2 ? launch_kernel(t128::conv_s2_t32_kernel<2>, g, 256, lds, st, p)
                          : launch_kernel(t128::conv_s2_t32_kernel<1>, g, 256, lds, st, p);
         break;
@@ -1654,7 +1625,7 @@ static int run_conv(const dcvc_conv* h, const ConvParams& cp, hipStream_t st)
         p.shuffle = cp.epi == DCVC_EPI_SHUFFLE2;
         p.cs_p = cp.cs_p;
         const size_t lds = t128::conv128_lds(p.kin, pl.ntw);
-        const dim3 g(((cp.H + t128::TH - 1) / t128::TH) * ((cp.W + t128::TW - 1) / t128::TW), cp.N / (128 * pl.ntw));
+        const dim3 g(tile_grid(cp.H, cp.W, t128::TH, t128::TW), cp.N / (128 * pl.ntw));
         rc = pl.ntw == 2 ? launch_kernel(t128::conv3x3_t128_kernel<2>, g, t128::NTHR, lds, st, p)
                          : launch_kernel(t128::conv3x3_t128_kernel<1>, g, t128::NTHR, lds, st, p);
         break;
@@ -1668,6 +1639,24 @@ static int run_conv(const dcvc_conv* h, const ConvParams& cp, hipStream_t st)
     }
     if (rc) return rc;
     DCVC_LAUNCH_CHECK();
+    return 0;
+}
+
+// What every forward entry point (`who`) requires of its sources.  two_ok: the layer takes a concat of two sources (a conv,
+// a block with adaptor); head_done: the caller says the block's head was computed by its predecessor's tail
+static int check_src(const char* who, const SrcPair& s, int cin_p, bool two_ok, int dtype, int H, int W, bool head_done = false)
+{
+    DCVC_REQUIRE(H > 0 && W > 0, "%s: empty input %dx%d", who, H, W);
+    DCVC_REQUIRE(s.c0 % 32 == 0 && s.c1 % 32 == 0 && s.c0 + s.c1 == cin_p,
+                 "%s: input channels %d+%d do not match the layer (%d physical)", who, s.c0, s.c1, cin_p);
+    DCVC_REQUIRE((s.x1 != nullptr) == (s.c1 > 0), "%s: x1/c1 mismatch", who);
+    DCVC_REQUIRE(two_ok || s.c1 == 0, "%s: a block without adaptor takes a single source", who);
+    DCVC_REQUIRE(!head_done || !two_ok, "%s: a block with adaptor computes its own head", who);
+    DCVC_REQUIRE(s.ld0 >= s.c0 && (s.c1 == 0 || s.ld1 >= s.c1), "%s: input row stride too small", who);
+    const size_t es = dcvc::elem_size(dtype);
+    DCVC_REQUIRE(((uintptr_t)s.x0 % 16) == 0 && (s.ld0 * es) % 16 == 0 &&
+                     (s.c1 == 0 || (((uintptr_t)s.x1 % 16) == 0 && (s.ld1 * es) % 16 == 0)),
+                 "%s: inputs must be 16-byte aligned", who);
     return 0;
 }
 
@@ -1692,38 +1681,37 @@ int dcvc_dcb_create(int dtype, int cin, int c, int shortcut, const float* adapto
     const int Cp = h->c_p = round_up(c, 64);
     const int Kp = h->cin_p = h->adapt ? round_up(cin, 32) : Cp;
     const int C = c;
-    int rc = 0;
-    if (h->adapt) {
-        rc |= pack_any(dtype, h->wa, Cp, Kp, [&](int n, int k) { return (n < C && k < cin) ? adaptor_w[(size_t)n * cin + k] : 0.f; });
-        rc |= upload_f32(h->ba, Cp, [&](int n) { return n < C ? adaptor_b[n] : 0.f; });
-    }
     // fp16 mode evaluates both activations on pre-scaled pre-activations (Traits<half_t>::gate / gate2):
     // dc.0 and ffn.0 are packed multiplied by kAct, their consumers (depthwise taps, ffn.2) divided by
     // it; exact mode packs everything unchanged (ka == 1)
     const float ka = dtype == DCVC_F16 ? Traits<half_t>::kAct : 1.0f;
-    rc |= pack_any(dtype, h->w1, Cp, Cp, [&](int n, int k) { return (n < C && k < C) ? ka * w1[(size_t)n * C + k] : 0.f; });
+    // ffn.0: logical rows [0,2C) pair with rows [2C,4C) (WSiLUChunkAdd); physical halves are 2*Cp wide
+    auto u_row = [&](int n) { const int half = n / (2 * Cp), cc = n % (2 * Cp); return cc < 2 * C ? half * 2 * C + cc : -1; };
+    // every matrix's logical view, once: the classic kernels' packing and the fragment streams read the same one
+    const Mat WA = [&](int n, int k) { return (n < C && k < cin) ? adaptor_w[(size_t)n * cin + k] : 0.f; };
+    const Mat W1 = [&](int n, int k) { return (n < C && k < C) ? ka * w1[(size_t)n * C + k] : 0.f; };
+    const Mat W2 = [&](int n, int k) { return (n < C && k < C) ? w2[(size_t)n * C + k] : 0.f; };
+    const Mat W3 = [&](int n, int k) { const int rr = u_row(n); return (rr >= 0 && k < C) ? ka * w3[(size_t)rr * C + k] : 0.f; };
+    const Mat W4 = [&](int n, int k) { return (n < C && k < 2 * C) ? w4[(size_t)n * 2 * C + k] / ka : 0.f; };
+    int rc = 0;
+    if (h->adapt) {
+        rc |= pack_any(dtype, h->wa, Cp, Kp, WA);
+        rc |= upload_f32(h->ba, Cp, [&](int n) { return n < C ? adaptor_b[n] : 0.f; });
+    }
+    rc |= pack_any(dtype, h->w1, Cp, Cp, W1);
     rc |= upload_f32(h->b1, Cp, [&](int n) { return n < C ? ka * b1[n] : 0.f; });
     auto dwget = [&](int i) { const int t = i / Cp, ch = i % Cp; return ch < C ? wd[(size_t)ch * 9 + t] / ka : 0.f; };
     rc |= dtype == DCVC_F16 ? upload_T<half_t>(h->wd, 9 * Cp, dwget) : upload_T<float>(h->wd, 9 * Cp, dwget);
     rc |= upload_f32(h->bd, Cp, [&](int n) { return n < C ? bd[n] : 0.f; });
-    rc |= pack_any(dtype, h->w2, Cp, Cp, [&](int n, int k) { return (n < C && k < C) ? w2[(size_t)n * C + k] : 0.f; });
+    rc |= pack_any(dtype, h->w2, Cp, Cp, W2);
     rc |= upload_f32(h->b2, Cp, [&](int n) { return n < C ? b2[n] : 0.f; });
-    // ffn.0: logical rows [0,2C) pair with rows [2C,4C) (WSiLUChunkAdd); physical halves are 2*Cp wide
-    auto u_row = [&](int n) { const int half = n / (2 * Cp), cc = n % (2 * Cp); return cc < 2 * C ? half * 2 * C + cc : -1; };
-    rc |= pack_any(dtype, h->w3, 4 * Cp, Cp, [&](int n, int k) { const int rr = u_row(n); return (rr >= 0 && k < C) ? ka * w3[(size_t)rr * C + k] : 0.f; });
+    rc |= pack_any(dtype, h->w3, 4 * Cp, Cp, W3);
     rc |= upload_f32(h->b3, 4 * Cp, [&](int n) { const int rr = u_row(n); return rr >= 0 ? ka * b3[rr] : 0.f; });
-    rc |= pack_any(dtype, h->w4, Cp, 2 * Cp, [&](int n, int k) { return (n < C && k < 2 * C) ? w4[(size_t)n * 2 * C + k] / ka : 0.f; });
+    rc |= pack_any(dtype, h->w4, Cp, 2 * Cp, W4);
     rc |= upload_f32(h->b4, Cp, [&](int n) { return n < C ? b4[n] : 0.f; });
-    if (rc == 0 && dtype == DCVC_F16 && t128_width_ok(Cp)) {
-        // the same (pre-scaled, fp16) tail weights once more, as the fragment streams of dcb_tail128_kernel
-        auto W2 = [&](int n, int k) { return (n < C && k < C) ? w2[(size_t)n * C + k] : 0.f; };
-        auto W3 = [&](int n, int k) { const int rr = u_row(n); return (rr >= 0 && k < C) ? ka * w3[(size_t)rr * C + k] : 0.f; };
-        auto W4 = [&](int n, int k) { return (n < C && k < 2 * C) ? w4[(size_t)n * 2 * C + k] / ka : 0.f; };
-        if (h->adapt && Kp % 64 == 0) {
-            auto WA = [&](int n, int k) { return (n < C && k < cin) ? adaptor_w[(size_t)n * cin + k] : 0.f; };
-            rc |= visit_t128_width(Cp, [&](auto w) { return pack_t128_rect<decltype(w)::value>(h->wa_t128, Kp, WA); });
-        }
-        rc |= pack_t128_square_any(Cp, h->w1_t128, [&](int n, int k) { return (n < C && k < C) ? ka * w1[(size_t)n * C + k] : 0.f; });
+    if (rc == 0 && dtype == DCVC_F16 && t128_width_ok(Cp)) {   // the same weights once more, as fragment streams
+        if (h->adapt && Kp % 64 == 0) rc |= pack_t128_matrix(h->wa_t128, Cp, Kp, WA);
+        rc |= pack_t128_matrix(h->w1_t128, Cp, Cp, W1);
         rc |= visit_t128_width(Cp, [&](auto w) { return pack_t128<decltype(w)::value>(h->wt128, W2, W3, W4); });
     }
     if (rc) return rc < 0 ? rc : dcvc::E_MEM;
@@ -1750,21 +1738,13 @@ int dcvc_dcb_forward_chained(const dcvc_dcb* h, const void* x0, int64_t ld0, int
                              int head_done, int a_slot, const dcvc_dcb* next)
 {
     DCVC_REQUIRE(h && x0 && out && scratch, "dcvc_dcb_forward: null pointer");
-    DCVC_REQUIRE(!head_done || !h->adapt, "dcvc_dcb_forward_chained: a block with adaptor computes its own head");
     if (next)
         DCVC_REQUIRE(!next->adapt && next->c_p == h->c_p && next->dtype == h->dtype && !quant && !h->shortcut,
                      "dcvc_dcb_forward_chained: cannot fuse the next block's head (needs same width and type, no "
                      "adaptor there, no shortcut / quant step here)");
-    DCVC_REQUIRE(H > 0 && W > 0, "dcvc_dcb_forward: empty input %dx%d", H, W);
-    DCVC_REQUIRE(c0 % 32 == 0 && c1 % 32 == 0 && c0 + c1 == h->cin_p,
-                 "dcvc_dcb_forward: input channels %d+%d do not match the block (%d physical)", c0, c1, h->cin_p);
-    DCVC_REQUIRE((x1 != nullptr) == (c1 > 0), "dcvc_dcb_forward: x1/c1 mismatch");
-    DCVC_REQUIRE(h->adapt || c1 == 0, "dcvc_dcb_forward: a block without adaptor takes a single source");
-    DCVC_REQUIRE(ld0 >= c0 && ldo >= h->c_p && (c1 == 0 || ld1 >= c1), "dcvc_dcb_forward: row stride too small");
-    const size_t es = dcvc::elem_size(h->dtype);
-    DCVC_REQUIRE(((uintptr_t)x0 % 16) == 0 && (ld0 * es) % 16 == 0 && (c1 == 0 || (((uintptr_t)x1 % 16) == 0 && (ld1 * es) % 16 == 0)),
-                 "dcvc_dcb_forward: inputs must be 16-byte aligned");
-    SrcPair src{x0, (long)ld0, c0, x1, (long)ld1, c1};
+    const SrcPair src{x0, (long)ld0, c0, x1, (long)ld1, c1};
+    if (int rc = check_src("dcvc_dcb_forward", src, h->cin_p, h->adapt != 0, h->dtype, H, W, head_done != 0)) return rc;
+    DCVC_REQUIRE(ldo >= h->c_p, "dcvc_dcb_forward: output row stride too small");
     hipStream_t st = (hipStream_t)stream;
     ChainArgs ch;
     ch.head_done = head_done;
@@ -1778,7 +1758,6 @@ int dcvc_dcb_forward_then_conv(const dcvc_dcb* h, const void* x0, int64_t ld0, i
                                const dcvc_conv* conv, const float* conv_quant, void* conv_out, int64_t ldco)
 {
     DCVC_REQUIRE(h && x0 && scratch && conv && conv_out, "dcvc_dcb_forward_then_conv: null pointer");
-    DCVC_REQUIRE(!head_done || !h->adapt, "dcvc_dcb_forward_then_conv: a block with adaptor computes its own head");
     DCVC_REQUIRE(!h->shortcut, "dcvc_dcb_forward_then_conv: a block with shortcut cannot feed a fused conv");
     DCVC_REQUIRE(conv->dtype == h->dtype && conv->kh == 1 && conv->kw == 1 && conv->stride == 1 && conv->pad == 0 &&
                      conv->cin_p == h->c_p && conv->n_p == h->c_p && conv->cin == h->c &&
@@ -1786,17 +1765,10 @@ int dcvc_dcb_forward_then_conv(const dcvc_dcb* h, const void* x0, int64_t ld0, i
                  "dcvc_dcb_forward_then_conv: the conv must be 1x1, stride 1, of the block's width (%d -> %d given, block %d), "
                  "epilogue bias or bias*quant", conv->cin, conv->cout, h->c);
     DCVC_REQUIRE((conv->epi == DCVC_EPI_BIAS_QUANT) == (conv_quant != nullptr), "dcvc_dcb_forward_then_conv: quant vector / epilogue mismatch");
-    DCVC_REQUIRE(H > 0 && W > 0, "dcvc_dcb_forward_then_conv: empty input %dx%d", H, W);
-    DCVC_REQUIRE(c0 % 32 == 0 && c1 % 32 == 0 && c0 + c1 == h->cin_p,
-                 "dcvc_dcb_forward_then_conv: input channels %d+%d do not match the block (%d physical)", c0, c1, h->cin_p);
-    DCVC_REQUIRE((x1 != nullptr) == (c1 > 0), "dcvc_dcb_forward_then_conv: x1/c1 mismatch");
-    DCVC_REQUIRE(h->adapt || c1 == 0, "dcvc_dcb_forward_then_conv: a block without adaptor takes a single source");
-    DCVC_REQUIRE(ld0 >= c0 && ldco >= h->c_p && (c1 == 0 || ld1 >= c1), "dcvc_dcb_forward_then_conv: row stride too small");
-    const size_t es = dcvc::elem_size(h->dtype);
-    DCVC_REQUIRE(((uintptr_t)x0 % 16) == 0 && (ld0 * es) % 16 == 0 && ((uintptr_t)conv_out % 16) == 0 && (ldco * es) % 16 == 0 &&
-                     (c1 == 0 || (((uintptr_t)x1 % 16) == 0 && (ld1 * es) % 16 == 0)),
-                 "dcvc_dcb_forward_then_conv: buffers must be 16-byte aligned");
-    SrcPair src{x0, (long)ld0, c0, x1, (long)ld1, c1};
+    const SrcPair src{x0, (long)ld0, c0, x1, (long)ld1, c1};
+    if (int rc = check_src("dcvc_dcb_forward_then_conv", src, h->cin_p, h->adapt != 0, h->dtype, H, W, head_done != 0)) return rc;
+    DCVC_REQUIRE(ldco >= h->c_p && ((uintptr_t)conv_out % 16) == 0 && (ldco * dcvc::elem_size(h->dtype)) % 16 == 0,
+                 "dcvc_dcb_forward_then_conv: output row stride too small or not 16-byte aligned");
     ChainArgs ch;
     ch.head_done = head_done;
     ch.a_slot = a_slot;
@@ -1897,28 +1869,24 @@ int dcvc_conv_create(int dtype, int cin, int cout, int kh, int kw, int stride, i
         to_log = [=](int n) { return n < cout ? n : -1; };
     }
     h->n_p = Np;
-    int rc = pack_any(dtype, h->w, Np, taps * Kp, [&](int n, int k) {
-        const int nl = to_log(n), t = k / Kp, ci = k % Kp;
+    // the conv's logical view, once; the classic kernel reads it as a matrix with k = tap * Kp + ci
+    const Taps WC = [&](int n, int t, int ci) {
+        const int nl = to_log(n);
         return (nl >= 0 && ci < cin) ? w[((size_t)nl * cin + ci) * taps + t] : 0.f;
-    });
+    };
+    int rc = pack_any(dtype, h->w, Np, taps * Kp, [&](int n, int k) { return WC(n, k / Kp, k % Kp); });
     rc |= upload_f32(h->b, Np, [&](int n) { const int nl = to_log(n); return nl >= 0 ? b[nl] : 0.f; });
-    if (rc == 0 && dtype == DCVC_F16 && taps == 1 && epilogue != DCVC_EPI_SHUFFLE2 && Np == Kp && Np == round_up(cout, 64) && t128_width_ok(Np))
-        rc |= pack_t128_square_any(Np, h->w_t128, [&](int n, int k) { return (n < cout && k < cin) ? w[(size_t)n * cin + k] : 0.f; });
-    if (rc == 0 && dtype == DCVC_F16 && kh == 3 && kw == 3 && stride == 1 && pad == 1 && Kp % 64 == 0 && Kp <= 256 && Np % 256 == 0 &&
+    const bool f16 = rc == 0 && dtype == DCVC_F16;   // the fragment-stream forms (at most one of the three applies)
+    if (f16 && taps == 1 && epilogue != DCVC_EPI_SHUFFLE2 && Np == Kp && Np == round_up(cout, 64) && t128_width_ok(Np))
+        rc |= pack_t128_matrix(h->w_t128, Np, Kp, [&](int n, int k) { return WC(n, 0, k); });
+    if (f16 && kh == 3 && kw == 3 && stride == 1 && pad == 1 && Kp % 64 == 0 && Kp <= 256 && Np % 256 == 0 &&
         (epilogue == DCVC_EPI_BIAS || (epilogue == DCVC_EPI_SHUFFLE2 && h->cs_p % 256 == 0))) {
-        auto WC = [&](int n, int t, int ci) {
-            const int nl = to_log(n);
-            return (nl >= 0 && ci < cin) ? w[((size_t)nl * cin + ci) * taps + t] : 0.f;
-        };
-        rc |= pack_t128_conv(h->w_c128[0], 1, 9, 4, Np, Kp, WC);
-        rc |= pack_t128_conv(h->w_c128[1], 2, 9, 8, Np, Kp, WC);
+        rc |= pack_quarters(h->w_c128[0], Np / 128, 1, 9, Kp / 16, 4, WC);
+        rc |= pack_quarters(h->w_c128[1], Np / 256, 2, 9, Kp / 16, 8, WC);
     }
-    if (rc == 0 && dtype == DCVC_F16 && stride == 2 && ((kh == 2 && kw == 2 && pad == 0) || (kh == 3 && kw == 3 && pad == 1)) &&
+    if (f16 && stride == 2 && ((kh == 2 && kw == 2 && pad == 0) || (kh == 3 && kw == 3 && pad == 1)) &&
         Kp % 128 == 0 && Kp <= 384 && (Np == 128 || Np == 256) && epilogue == DCVC_EPI_BIAS)
-        rc |= pack_t128_conv(h->w_s2, Np / 128, taps, 8 * (Np / 128), Np, Kp, [&](int n, int t, int ci) {
-            const int nl = to_log(n);
-            return (nl >= 0 && ci < cin) ? w[((size_t)nl * cin + ci) * taps + t] : 0.f;
-        });
+        rc |= pack_quarters(h->w_s2, 1, Np / 128, taps, Kp / 16, 8 * (Np / 128), WC);
     if (rc) return rc < 0 ? rc : dcvc::E_MEM;
     *out = h.release();
     return 0;
@@ -1936,16 +1904,10 @@ int dcvc_conv_forward_scaled(const dcvc_conv* h, const void* x0, int64_t ld0, in
                              int H, int W, const float* in_scale, const float* quant, void* out, int64_t ldo, void* stream)
 {
     DCVC_REQUIRE(h && x0 && out, "dcvc_conv_forward: null pointer");
-    DCVC_REQUIRE(H > 0 && W > 0, "dcvc_conv_forward: empty input %dx%d", H, W);
-    DCVC_REQUIRE(c0 % 32 == 0 && c1 % 32 == 0 && c0 + c1 == h->cin_p,
-                 "dcvc_conv_forward: input channels %d+%d do not match the layer (%d physical)", c0, c1, h->cin_p);
-    DCVC_REQUIRE((x1 != nullptr) == (c1 > 0), "dcvc_conv_forward: x1/c1 mismatch");
     DCVC_REQUIRE(h->epi != DCVC_EPI_BIAS_QUANT || quant != nullptr, "dcvc_conv_forward: quant vector required");
-    const size_t es = dcvc::elem_size(h->dtype);
-    DCVC_REQUIRE(((uintptr_t)x0 % 16) == 0 && (ld0 * es) % 16 == 0 && (c1 == 0 || (((uintptr_t)x1 % 16) == 0 && (ld1 * es) % 16 == 0)),
-                 "dcvc_conv_forward: inputs must be 16-byte aligned");
     ConvParams cp{};
     cp.src = SrcPair{x0, (long)ld0, c0, x1, (long)ld1, c1};
+    if (int rc = check_src("dcvc_conv_forward", cp.src, h->cin_p, true, h->dtype, H, W)) return rc;
     cp.H = H;
     cp.W = W;
     cp.Ho = (H + 2 * h->pad - h->kh) / h->stride + 1;

@@ -54,6 +54,27 @@ def _geom(x):
     return x.shape[0], x.shape[1], x.shape[2], x.stride(1)
 
 
+def _io(x0, x1, out, out_shape, dtype):
+    """The source and output arguments of a forward call: ((x0, ld0, c0, x1, ld1, c1, H, W), out, ldo) of the concat
+    sources x0, x1 (or None) and of `out`, allocated here if None.  out_shape(H, W): the HWC shape the layer writes."""
+    for name, t in (("x0", x0), ("x1", x1), ("out", out)):
+        if t is not None and t.dtype != dtype:
+            raise DcvcError(f"{name} is {t.dtype}, the layer computes in {dtype}")
+    H, W, c0, ld0 = _geom(x0)
+    c1, ld1 = 0, 0
+    if x1 is not None:
+        H1, W1, c1, ld1 = _geom(x1)
+        if (H1, W1) != (H, W):
+            raise DcvcError(f"concat inputs differ in size: {(H, W)} and {(H1, W1)}")
+    Ho, Wo, co = out_shape(H, W)
+    if out is None:
+        out = torch.empty((Ho, Wo, co), dtype=dtype, device=x0.device)
+    H2, W2, c2, ldo = _geom(out)
+    if (H2, W2) != (Ho, Wo) or c2 < co:
+        raise DcvcError(f"output view {tuple(out.shape)} does not fit the layer's output {(Ho, Wo, co)}")
+    return (_p(x0), ld0, c0, _p(x1), ld1, c1, H, W), out, ldo
+
+
 class Scratch:
     """Grow-only device scratch per (device, stream): no allocation in the steady state.  A buffer that has been
     handed out is never freed: captured HIP graphs (models.GraphCache) keep its raw address in their kernel
@@ -109,45 +130,20 @@ class DepthConvBlock:
         out: optional HWC view to write into (e.g. a slice of a concat buffer).
         head_done / a_slot / next_block: see dcb_chain() (dcvc_dcb_forward_chained)."""
         L = _lib.lib()
-        H, W, c0, ld0 = _geom(x0)
-        c1, ld1 = 0, 0
-        if x1 is not None:
-            H1, W1, c1, ld1 = _geom(x1)
-            if (H1, W1) != (H, W):
-                raise DcvcError("concat inputs differ in size")
-        if out is None:
-            out = torch.empty((H, W, self.c_p), dtype=self.dtype, device=x0.device)
-        Ho, Wo, co, ldo = _geom(out)
-        if (Ho, Wo) != (H, W) or co < self.c_p:
-            raise DcvcError(f"output view {tuple(out.shape)} does not fit a {self.c_p}-channel block output")
-        if x0.dtype != self.dtype or out.dtype != self.dtype:
-            raise DcvcError("dtype mismatch between block and tensors")
-        nbytes = L.dcvc_dcb_scratch_bytes(self.h, H, W)
-        scratch = Scratch.get(nbytes, x0.device)
-        check(L.dcvc_dcb_forward_chained(self.h, _p(x0), ld0, c0, _p(x1), ld1, c1, H, W, _p(quant), _p(out), ldo,
-                                         _p(scratch), _stream(), int(head_done), int(a_slot),
-                                         next_block.h if next_block is not None else None), "dcvc_dcb_forward")
+        src, out, ldo = _io(x0, x1, out, lambda H, W: (H, W, self.c_p), self.dtype)
+        scratch = Scratch.get(L.dcvc_dcb_scratch_bytes(self.h, *src[6:]), x0.device)
+        check(L.dcvc_dcb_forward_chained(self.h, *src, _p(quant), _p(out), ldo, _p(scratch), _stream(), int(head_done),
+                                         int(a_slot), next_block.h if next_block is not None else None), "dcvc_dcb_forward")
         return out
 
     def then_conv(self, x0, x1, conv, conv_quant=None, out=None, head_done=False, a_slot=0):
         """This block followed by a 1x1 conv of the same width (dcvc_dcb_forward_then_conv): only the conv's output
         is written.  conv.fusable_after(self) must hold."""
         L = _lib.lib()
-        H, W, c0, ld0 = _geom(x0)
-        c1, ld1 = 0, 0
-        if x1 is not None:
-            H1, W1, c1, ld1 = _geom(x1)
-            if (H1, W1) != (H, W):
-                raise DcvcError("concat inputs differ in size")
-        if out is None:
-            out = torch.empty((H, W, conv.cout_p), dtype=self.dtype, device=x0.device)
-        Ho, Wo, co, ldo = _geom(out)
-        if (Ho, Wo) != (H, W) or co < conv.cout_p or out.dtype != self.dtype or x0.dtype != self.dtype:
-            raise DcvcError(f"output view {tuple(out.shape)} does not fit the fused conv's output")
-        scratch = Scratch.get(L.dcvc_dcb_scratch_bytes(self.h, H, W), x0.device)
-        check(L.dcvc_dcb_forward_then_conv(self.h, _p(x0), ld0, c0, _p(x1), ld1, c1, H, W, _p(scratch), _stream(),
-                                           int(head_done), int(a_slot), conv.h, _p(conv_quant), _p(out), ldo),
-              "dcvc_dcb_forward_then_conv")
+        src, out, ldo = _io(x0, x1, out, lambda H, W: (H, W, conv.cout_p), self.dtype)
+        scratch = Scratch.get(L.dcvc_dcb_scratch_bytes(self.h, *src[6:]), x0.device)
+        check(L.dcvc_dcb_forward_then_conv(self.h, *src, _p(scratch), _stream(), int(head_done), int(a_slot), conv.h,
+                                           _p(conv_quant), _p(out), ldo), "dcvc_dcb_forward_then_conv")
         return out
 
     def can_follow(self, prev, prev_quant):
@@ -227,20 +223,10 @@ class Conv2d:
         """in_scale: float32 device vector [cin]: the conv of x * in_scale[c] (the product rounded to the element type,
         = scale_channels followed by the conv, without the intermediate tensor)"""
         L = _lib.lib()
-        H, W, c0, ld0 = _geom(x0)
-        c1, ld1 = 0, 0
-        if x1 is not None:
-            _, _, c1, ld1 = _geom(x1)
         if in_scale is not None and (in_scale.dtype != torch.float32 or in_scale.numel() < self.cin):
             raise DcvcError(f"in_scale must be a float32 vector of at least {self.cin} entries")
-        Ho, Wo = self.out_hw(H, W)
-        if out is None:
-            out = torch.empty((Ho, Wo, self.cout_p), dtype=self.dtype, device=x0.device)
-        H2, W2, co, ldo = _geom(out)
-        if (H2, W2) != (Ho, Wo) or co < self.cout_p:
-            raise DcvcError(f"output view {tuple(out.shape)} does not fit conv output {(Ho, Wo, self.cout_p)}")
-        check(L.dcvc_conv_forward_scaled(self.h, _p(x0), ld0, c0, _p(x1), ld1, c1, H, W, _p(in_scale), _p(quant), _p(out),
-                                         ldo, _stream()), "dcvc_conv_forward")
+        src, out, ldo = _io(x0, x1, out, lambda H, W: (*self.out_hw(H, W), self.cout_p), self.dtype)
+        check(L.dcvc_conv_forward_scaled(self.h, *src, _p(in_scale), _p(quant), _p(out), ldo, _stream()), "dcvc_conv_forward")
         return out
 
 

@@ -454,3 +454,16 @@ def test_bad_arguments_fail_loudly():
     blk = nn.DepthConvBlock(sd, "m", torch.float32)
     with pytest.raises(DcvcError):
         blk(torch.zeros((4, 4, 128), device="cuda"))
+    # rejected on the host, before anything is launched
+    sd = {"m.weight": (rng.standard_normal((64, 256, 1, 1)) / 16).astype(np.float32),
+          "m.bias": rng.standard_normal(64).astype(np.float32)}
+    conv = nn.Conv2d(sd, "m", torch.float32)
+    half = lambda h, dt=torch.float32: torch.zeros((h, 4, 128), dtype=dt, device="cuda")
+    with pytest.raises(DcvcError):
+        conv(half(4), half(5))                          # two sources of different height
+    with pytest.raises(DcvcError):
+        conv(torch.zeros((4, 4, 256), dtype=torch.float16, device="cuda"))   # a source of the wrong dtype
+    sd = make_dcb_weights(rng, "a", 256, 128, True)
+    blk = nn.DepthConvBlock(sd, "a", torch.float32)
+    with pytest.raises(DcvcError):
+        blk(half(4), half(4, torch.float16))            # a second source of the wrong dtype
