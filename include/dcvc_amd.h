@@ -494,6 +494,26 @@ int64_t dcvc_rate_estimate_ws_bytes(int nsym, int parts, int nz);
 int dcvc_rate_estimate(const int16_t* packed, int nsym, int parts, const uint32_t* gcost, int g_n, int g_stride,
                        const int8_t* z8, int nz, int zhw, const uint32_t* zcost, int z_n, int z_stride, int z_start,
                        void* workspace, uint64_t* out_host, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Decoder-state digest (csrc/dcvc_digest.hip, docs/state_digest.md; no reference counterpart).  data: nbytes = 8 m bytes
+ * of device memory, read where they lie as m little-endian uint64 words w_0 .. w_{m-1}; all arithmetic mod 2^64:
+ *   G = 0x9E3779B97F4A7C15
+ *   mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *   digest = sum over j of mix(w_j + (j + 1) * G)  +  mix(nbytes * G)
+ * The sum is commutative, so the result does not depend on the reduction order (no atomics).  mix is a bijection and the
+ * position term is fixed per word: a change confined to one word always changes the digest.  A drift and damage check,
+ * not a cryptographic hash.
+ * out_host (dcvc_host_alloc memory, 2 words): the digest and a status - 0 not compared (have_expected == 0), 1 equal to
+ * `expected`, 2 differs - written by the second of two kernels, valid for the host once the stream has passed that point;
+ * the call does not wait for the device.  nbytes <= 0, nbytes % 8 != 0 and a data pointer that is not 8-byte aligned are
+ * argument errors and launch nothing (all argument checks need no device).  The buffer is read 16 bytes per access; a base
+ * that is 8- but not 16-byte aligned and an odd word count are handled by the same kernel.  One grid-stride pass of the
+ * full grid covers DCVC_DIGEST_PASS_WORDS words.  workspace: device, 8-byte aligned,
+ * dcvc_state_digest_ws_bytes(nbytes) bytes (< 0: bad size; never more than 8 * DCVC_DIGEST_PASS_WORDS / 512). */
+#define DCVC_DIGEST_PASS_WORDS 1048576
+int64_t dcvc_state_digest_ws_bytes(int64_t nbytes);
+int dcvc_state_digest(const void* data, int64_t nbytes, void* workspace, uint64_t expected, int have_expected,
+                      uint64_t* out_host, void* stream);
 /* dst[0..n) = src[0..n) on the device by a kernel (the per-frame row of the quantisation tables: src/models/video_model.py:303-305
  * slices them per call; a runtime copy command costs an order of magnitude more than the kernel) */
 int dcvc_copy_f32(float* dst, const float* src, int n, void* stream);

@@ -8,7 +8,7 @@ import ctypes
 import os
 import subprocess
 from ctypes import (POINTER, c_char_p, c_double, c_float, c_int, c_int8, c_int16, c_int32, c_int64, c_size_t,
-                    c_uint8, c_uint32, c_void_p)
+                    c_uint8, c_uint32, c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DCVC_AMD_DIAG=1 selects the developer build with in-kernel diagnostics (make -C opendcvc_amd/csrc diag)
@@ -20,11 +20,23 @@ F16, F32 = 0, 1
 U8 = 2                    # uint8 planes: the metric entries only (dcvc_sse, dcvc_msssim_stats)
 U16 = 3                   # uint16 planes (low-bit-aligned samples above 8 bits): the same entries only
 SSE_BLOCKS = 1024         # DCVC_SSE_BLOCKS
+DIGEST_PASS_WORDS = 1 << 20          # DCVC_DIGEST_PASS_WORDS: the words one grid-stride pass of dcvc_state_digest covers
 EPI_BIAS, EPI_BIAS_QUANT, EPI_SHUFFLE2, EPI_WSILU = 0, 1, 2, 3
 
 
 class DcvcError(RuntimeError):
     pass
+
+
+class DigestMismatch(DcvcError):
+    """The entry a decoded frame put into the DPB does not have the digest the stream carries for it (docs/state_digest.md):
+    the decoder has left the encoder's state at this frame, or the digest unit is damaged.  index: the frame's position in
+    decode order; is_i; expected: the stream's digest; got: the decoder's.  Resume at the next I frame."""
+
+    def __init__(self, index, is_i, expected, got):
+        super().__init__(f"frame {index} ({'I' if is_i else 'P'}): the decoder's reference state has digest {got:#018x}, "
+                         f"the stream carries {expected:#018x}")
+        self.index, self.is_i, self.expected, self.got = index, is_i, expected, got
 
 
 def build(force=False):
@@ -142,6 +154,8 @@ _SIGS = {
     "dcvc_frame_analyze": (_I, [_I, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
     "dcvc_rate_estimate_ws_bytes": (_L, [_I, _I, _I]),
     "dcvc_rate_estimate": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "dcvc_state_digest_ws_bytes": (_L, [_L]),
+    "dcvc_state_digest": (_I, [_P, _L, _P, c_uint64, _I, _P, _P]),
     "dcvc_copy_f32": (_I, [_P, _P, _I, _P]),
     "dcvc_memcpy_d2h": (_I, [_P, _P, c_size_t, _P]),
     "dcvc_memcpy_h2d": (_I, [_P, _P, c_size_t, _P]),

@@ -9,6 +9,9 @@ Layout:  NAL header byte = type(4 bits) | sps_id(4 bits)
   SPS :  header, height (varint), width (varint), flags = ec_part << 2 | use_ada_i
   I/P :  header, qp (1 byte), payload length (varint), payload (the rANS stream of the frame)
          (types 3 / 4 = I / P with a chunked payload: this project's extension, docs/chunked_stream.md)
+  DIGEST: header (type 5), 8 bytes: the digest, little endian, of the entry the NEXT unit's frame puts into the DPB - that
+         unit must be an I or P unit.  This project's extension (docs/state_digest.md): the reference's reader rejects
+         type 5, streams written without digests are unchanged.
 varint:  0xxxxxxx                      value < 2**7
          10xxxxxx xxxxxxxx             value < 2**14   (big endian)
          11xxxxxx + 3 bytes            value < 2**30   (big endian)
@@ -24,6 +27,9 @@ class NalType(enum.IntEnum):
     # the y symbols in independent chunks that the GPU entropy-codes
     NAL_I_CHUNKED = 3
     NAL_P_CHUNKED = 4
+    # this project's extension (docs/state_digest.md), not readable by the reference: the digest of the decoder state behind
+    # the frame unit that follows
+    NAL_DIGEST = 5
 
 
 def write_uint_adaptive(f, value):
@@ -127,6 +133,23 @@ def write_ip(f, is_i_frame, sps_id, qp, bit_stream, chunked=False):
     return n + len(bit_stream)
 
 
+DIGEST_UNIT_BYTES = 9        # header + 8
+
+
+def write_digest(f, sps_id, digest):
+    if not 0 <= digest < (1 << 64):
+        raise ValueError(f"digest {digest} is not a 64-bit word")
+    f.write(bytes(((int(NalType.NAL_DIGEST) << 4) | sps_id,)) + int(digest).to_bytes(8, "little"))
+    return DIGEST_UNIT_BYTES
+
+
+def read_digest_remaining(f):
+    data = f.read(8)
+    if len(data) != 8:
+        raise EOFError("truncated DCVC-RT digest unit")
+    return int.from_bytes(data, "little")
+
+
 def frame_overhead_bytes(payload_len):
     """bytes write_ip puts in front of a payload of that length: NAL header, qp, the varint of the length (an SPS, written
     when a frame's parameters are new to the stream - twice in a typical one - is not counted)"""
@@ -155,26 +178,37 @@ class StreamWriter:
         sps_id, is_new = self.sps_helper.get_sps_id(sps)
         sps["sps_id"] = sps_id
         n = write_sps(self.f, sps) if is_new else 0
+        if getattr(pkt, "digest", None) is not None:
+            n += write_digest(self.f, sps_id, pkt.digest)
         return n + write_ip(self.f, pkt.is_i, sps_id, pkt.qp, pkt.bit_stream, chunked=getattr(pkt, "chunked", False))
 
 
 class StreamReader:
     """test_video.py:265-276: yields (sps, is_i_frame, qp, payload) per frame; `chunked` tells whether the frame returned
-    last carries a chunked payload (NAL_I_CHUNKED / NAL_P_CHUNKED)."""
+    last carries a chunked payload (NAL_I_CHUNKED / NAL_P_CHUNKED), `digest` the digest unit in front of it (an int; None:
+    the frame came without one)."""
 
     def __init__(self, f):
         self.f = f
         self.sps_helper = SPSHelper()
         self.chunked = False
+        self.digest = None
 
     def read_frame(self):
         header = read_header(self.f)
-        while header["nal_type"] == NalType.NAL_SPS:
-            self.sps_helper.add_sps_by_id(read_sps_remaining(self.f, header["sps_id"]))
+        digest = None
+        while header["nal_type"] in (NalType.NAL_SPS, NalType.NAL_DIGEST):
+            if digest is not None:
+                raise ValueError(f"a digest unit is followed by {header['nal_type'].name}, not by the frame it describes")
+            if header["nal_type"] == NalType.NAL_SPS:
+                self.sps_helper.add_sps_by_id(read_sps_remaining(self.f, header["sps_id"]))
+            else:
+                digest = read_digest_remaining(self.f)
             header = read_header(self.f)
         sps = self.sps_helper.get_sps_by_id(header["sps_id"])
         if sps is None:
             raise ValueError(f"frame refers to unknown SPS {header['sps_id']}")
         qp, payload = read_ip_remaining(self.f)
+        self.digest = digest
         self.chunked = header["nal_type"] in (NalType.NAL_I_CHUNKED, NalType.NAL_P_CHUNKED)
         return sps, header["nal_type"] in (NalType.NAL_I, NalType.NAL_I_CHUNKED), qp, payload

@@ -351,7 +351,7 @@ def _to_device(planes, device):
 def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=None, intra_period=-1,
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
                   src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
-                  target_bpp=None):
+                  target_bpp=None, digest=False):
     """Encodes `frame_num` frames of a YUV 4:2:0 file (src_type "yuv420"), of a raw file in another pixel format
     (pipeline.PIXEL_FORMATS: "yuv420p10le", "yuv444p", "nv12", "p010le", ...; metrics with data_range = max_val, rec_path in
     the source's format) or of a directory of PNGs ("png": RGB, converted to YCbCr around the codec) into the reference's
@@ -367,7 +367,10 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     off: the fixed qp of the reference's RD sweep): target-bitrate control (ratecontrol.RateController fed by the device's
     size estimate); qp_i / qp_p are then the starting qp and the log carries target_bpp, rc_qp (the mean qp of the packets)
     and rc_est_bpp (the mean of what the controller was fed, to hold against ave_all_frame_bpp) - with verbose_json also
-    the per-frame lists frame_rc_qp and frame_rc_est_bpp."""
+    the per-frame lists frame_rc_qp and frame_rc_est_bpp.  digest: the encoder writes a digest unit in front of every frame
+    (docs/state_digest.md: this project's extension, NOT readable by the reference; 9 bytes per frame, counted in the bits)
+    and the decode loop checks its own reference state against it - a difference raises _lib.DigestMismatch; the log then
+    carries one extra key, digests_checked."""
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics {metrics!r}: 'host' or 'device'")
     if entropy not in ("host", "device"):
@@ -401,6 +404,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         adaptive["rate"] = RateController(float(target_bpp) * height * width, qp_i if qp_p is None else qp_p, qp_i_init=qp_i)
     else:
         i_net.rate_estimate = p_net.rate_estimate = False       # (one pair codes every point)
+    if digest:
+        adaptive["digest"] = True
     enc = SequenceEncoder(i_net, p_net, qp_i, qp_p, intra_period, reset_interval, **adaptive)
     out = io.BytesIO()
     writer = StreamWriter(out)
@@ -439,8 +444,10 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         t0 = time.time()
         sps, is_i, qp, payload = stream_reader.read_frame()
         dec.h, dec.w, dec.two = sps["height"], sps["width"], bool(sps["ec_part"])
-        x_hat = dec.decode(FramePacket(is_i, qp, sps["use_ada_i"], payload, chunked=stream_reader.chunked))
+        x_hat = dec.decode(FramePacket(is_i, qp, sps["use_ada_i"], payload, chunked=stream_reader.chunked,
+                                       digest=stream_reader.digest))
         torch.cuda.synchronize(dev)
+        dec.check_digests()
         dec_time.append(time.time() - t0)
         if png:
             # (the PNG reader's planes are a transposed view: the kernels read them planar, as load_rgb_frame does)
@@ -490,6 +497,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         if verbose_json:
             log["frame_rc_qp"] = [int(q) for q in enc.rc_qp]
             log["frame_rc_est_bpp"] = [8 * b / (height * width) for b in enc.rc_est_bytes]
+    if digest:
+        log["digests_checked"] = dec.digests_checked
     return log
 
 
@@ -689,7 +698,8 @@ def run_job(nets, job, opts):
                         verbose_json=opts.get("verbose_json", False), device="cuda:0", src_type=job.get("src_type", "yuv420"),
                         calc_ssim=bool(opts.get("calc_ssim")), metrics=opts.get("metrics") or "host",
                         entropy=opts.get("entropy") or "host", scenecut=opts.get("scenecut") or 0,
-                        min_keyint=opts.get("min_keyint") or 4, target_bpp=target_bpp(opts, job["src_width"], job["src_height"]))
+                        min_keyint=opts.get("min_keyint") or 4, target_bpp=target_bpp(opts, job["src_width"], job["src_height"]),
+                        digest=bool(opts.get("digest")))
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -813,6 +823,9 @@ def build_parser():
     ap.add_argument("--target-kbps", "--target_kbps", type=float, default=None, metavar="K",
                     help="the same as a bitrate: K * 1000 / (--fps * width * height) bits per pixel, per sequence")
     ap.add_argument("--fps", type=float, default=None, metavar="F", help="frame rate of the source, for --target-kbps")
+    ap.add_argument("--digest", **flag,
+                    help="write a digest of the decoder's reference state in front of every frame and check it while decoding "
+                         "(docs/state_digest.md) - this project's extension, not readable by the reference")
     ap.add_argument("--model-i", "--model_path_i", help="DMCI checkpoint (.pth.tar); synthetic weights if omitted")
     ap.add_argument("--model-p", "--model_path_p", help="DMC checkpoint")
     ap.add_argument("--force-zero-thres", "--force_zero_thres", type=float, default=0.12)
@@ -839,7 +852,7 @@ def manifest_options(args, ap):
                 force_zero_thres=args.force_zero_thres, fp32=args.fp32, stream_path=stream_path,
                 verbose=args.verbose, verbose_json=args.verbose_json, calc_ssim=args.calc_ssim, metrics=args.metrics,
                 entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint, target_bpp=args.target_bpp,
-                target_kbps=args.target_kbps, fps=args.fps, force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
+                target_kbps=args.target_kbps, fps=args.fps, digest=args.digest, force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
     return opts, gpus
 
 
@@ -894,7 +907,7 @@ def main(argv=None):
                     intra_period=args.intra_period, reset_interval=args.reset_interval, verbose=args.verbose,
                     verbose_json=args.verbose_json, src_type=args.src_type, calc_ssim=args.calc_ssim, metrics=args.metrics,
                     entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint,
-                    target_bpp=target_bpp(vars(args), args.width, args.height))
+                    target_bpp=target_bpp(vars(args), args.width, args.height), digest=args.digest)
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:

@@ -4,6 +4,7 @@ small state machines, so bench.py / smoke() / the tests all drive the codecs the
 reference's run_one_point_with_stream does.
 """
 from dataclasses import dataclass
+from typing import Optional
 
 INDEX_MAP = (0, 1, 0, 2, 0, 2, 0, 2)          # test_video.py:164
 
@@ -15,6 +16,13 @@ class FramePacket:
     use_ada_i: int
     bit_stream: bytes
     chunked: bool = False        # chunked payload (the models' entropy="device" mode): written as NAL_I_CHUNKED / NAL_P_CHUNKED
+    digest: Optional[int] = None     # digest of the entry the frame puts into the DPB (docs/state_digest.md): a NAL_DIGEST unit
+
+
+def _dpb_entry(p_net):
+    """what a frame has just put into the DPB, the object both sides hold: an I frame's picture, a P frame's feature buffer"""
+    ref = p_net.dpb[0]
+    return ref.frame if ref.feature is None else ref.feature
 
 
 class SequenceEncoder:
@@ -39,13 +47,22 @@ class SequenceEncoder:
     frame's qp is chosen the controller is fed the previous frame's estimate plus the container's bytes - the same number
     with and without defer_stream, since it never waits for the exact stream - and gives the base qp: a P frame is coded at
     shift_qp(base, INDEX_MAP[g % 8]), an I frame at rate.i_qp(base).  Per frame: rc_qp (the qp in the packet), rc_est_bytes
-    (what the controller was fed) and rc_bytes (payload + container bytes, filled in when the packet comes out)."""
+    (what the controller was fed) and rc_bytes (payload + container bytes, filled in when the packet comes out).
+
+    digest (False = off: nothing launched, the packets of today): every packet carries the digest of the entry its frame put
+    into the DPB (digest.StateDigest on the encode stream, right behind the call that made the entry; the P frame's feature
+    buffer is overwritten by the next frame, which stream order puts behind the read).  Without defer_stream encode() waits
+    for the digest's event - the tail of the frame's kernels it otherwise leaves in flight - before it returns the packet;
+    with it the value is read when the packet comes out, one call later.  With rate control the unit's 9 bytes count in what
+    the controller is fed and in rc_bytes."""
 
     def __init__(self, i_net, p_net, qp_i, qp_p=None, intra_period=-1, reset_interval=32, defer_stream=False,
-                 scenecut=None, min_keyint=4, analyzer=None, rate=None):
+                 scenecut=None, min_keyint=4, analyzer=None, rate=None, digest=False):
         self.i_net, self.p_net = i_net, p_net
         self.defer = defer_stream
-        self._held = None            # (qp, use_ada_i, chunked) of the P frame whose stream is still pending
+        self._held = None            # (qp, use_ada_i, chunked, digest handle) of the P frame whose stream is still pending
+        self.digest = bool(digest)
+        self._digester = None        # (made at the first frame, on the frame's device)
         self.qp_i = qp_i
         self.qp_p = qp_i if qp_p is None else qp_p
         self.intra_period = intra_period
@@ -80,7 +97,7 @@ class SequenceEncoder:
             from .bitstream import frame_overhead_bytes
             for pkt in (pkts if isinstance(pkts, list) else [pkts]):
                 n = len(pkt.bit_stream)
-                self.rc_bytes.append(n + frame_overhead_bytes(n))
+                self.rc_bytes.append(n + frame_overhead_bytes(n) + self._unit_bytes())
                 self.rate.record_exact(self._rc_out, n)
                 self._rc_out += 1
         return pkts
@@ -96,15 +113,31 @@ class SequenceEncoder:
     def _rc_note(self, klass, base, qp, enc):
         from .bitstream import frame_overhead_bytes
         est = int(enc["est_bytes"])          # (compress() has waited for the hand-off's event, not for the host coder)
-        est += frame_overhead_bytes(est)
+        est += frame_overhead_bytes(est) + self._unit_bytes()
         self._rc_pending = (klass, base, est)
         self.rc_qp.append(qp)
         self.rc_est_bytes.append(est)
 
+    def _unit_bytes(self):
+        from .bitstream import DIGEST_UNIT_BYTES
+        return DIGEST_UNIT_BYTES if self.digest else 0
+
+    def _enqueue_digest(self):
+        """digest on: the handle of the newest DPB entry's digest, enqueued on the current stream"""
+        if not self.digest:
+            return None
+        entry = _dpb_entry(self.p_net)
+        if self._digester is None:
+            from .digest import StateDigest
+            self._digester = StateDigest(entry.device)
+        return self._digester.enqueue(entry)
+
     def _take_held(self, stream):
         out = []
         if self._held is not None and stream is not None:
-            out.append(FramePacket(False, self._held[0], self._held[1], stream, chunked=self._held[2]))
+            qp, use_ada_i, chunked, handle = self._held
+            out.append(FramePacket(False, qp, use_ada_i, stream, chunked=chunked,
+                                   digest=None if handle is None else handle.value()))
             self._held = None
         return out
 
@@ -141,7 +174,9 @@ class SequenceEncoder:
                 self._rc_note(I_CLASS, base, qp_i, enc)
             self.p_net.clear_dpb()
             self.p_net.add_ref_frame(None, enc["x_hat"])
-            pkt = FramePacket(True, qp_i, 0, enc["bit_stream"], chunked=bool(enc.get("chunked", False)))
+            handle = self._enqueue_digest()
+            pkt = FramePacket(True, qp_i, 0, enc["bit_stream"], chunked=bool(enc.get("chunked", False)),
+                              digest=None if handle is None else handle.value())
             return done + [pkt] if self.defer else pkt
         use_ada_i = 0
         if self.reset_interval > 0 and pos % self.reset_interval == 1:
@@ -153,11 +188,13 @@ class SequenceEncoder:
         if self.rate is not None:
             self._rc_note(INDEX_MAP[pos % 8], base, qp, enc)
         self.last_qp = qp
+        handle = self._enqueue_digest()
         chunked = bool(enc.get("chunked", False))         # (the models' entropy="device" mode: NAL_*_CHUNKED)
         if not self.defer:
-            return FramePacket(False, qp, use_ada_i, enc["bit_stream"], chunked=chunked)
+            return FramePacket(False, qp, use_ada_i, enc["bit_stream"], chunked=chunked,
+                               digest=None if handle is None else handle.value())
         done = self._take_held(enc.get("bit_stream_prev"))
-        self._held = (qp, use_ada_i, chunked)
+        self._held = (qp, use_ada_i, chunked, handle)
         return done
 
     def flush(self):
@@ -171,18 +208,53 @@ class SequenceDecoder:
     """defer_output=False: decode(pkt) returns the packet's picture (the reference's loop).
     defer_output=True: P pictures come out one call late - decode(pkt) returns a LIST of the pictures completed
     by the call, in order (usually one: the previous frame), flush() the rest; the reconstruction network of a
-    P frame then runs inside the host entropy-decoding gaps of the next frame (DMC.decompress)."""
+    P frame then runs inside the host entropy-decoding gaps of the next frame (DMC.decompress).
+
+    A packet that carries a digest (docs/state_digest.md) is checked, one without is not: behind the frame's entry into the
+    DPB the device forms the entry's digest and compares it with the packet's.  The result is read lazily - at the start of
+    the next decode(), in flush() (so call it at the end of a stream, deferring or not) and in check_digests() for callers
+    that have synchronised anyway - and a difference raises _lib.DigestMismatch naming the frame's index in decode order;
+    digests_checked counts the frames that passed.  After a mismatch resume at the next I frame, as after DcvcError."""
 
     def __init__(self, i_net, p_net, height, width, use_two, defer_output=False):
         self.i_net, self.p_net = i_net, p_net
         self.h, self.w, self.two = height, width, use_two
         self.defer = defer_output
+        self.frame_idx = 0           # packets handed to decode() so far
+        self.digests_checked = 0
+        self._digester = None        # (made at the first packet with a digest, on the entry's device)
+        self._unchecked = []         # (index, is_i, expected, handle) of the digests enqueued and not yet read
         p_net.set_curr_poc(0)
 
     def decode(self, pkt):
         from .models import CAPTURE_GUARD
         with CAPTURE_GUARD.frame():
-            return self._decode(pkt)
+            self._check_digests()
+            index, self.frame_idx = self.frame_idx, self.frame_idx + 1
+            out = self._decode(pkt)
+            expected = getattr(pkt, "digest", None)
+            if expected is not None:
+                entry = _dpb_entry(self.p_net)
+                if self._digester is None:
+                    from .digest import StateDigest
+                    self._digester = StateDigest(entry.device)
+                self._unchecked.append((index, pkt.is_i, expected, self._digester.enqueue(entry, expected)))
+            return out
+
+    def _check_digests(self):
+        from ._lib import DigestMismatch
+        from .digest import EQUAL
+        while self._unchecked:
+            index, is_i, expected, handle = self._unchecked.pop(0)
+            if handle.status() != EQUAL:
+                raise DigestMismatch(index, is_i, expected, handle.value())
+            self.digests_checked += 1
+
+    def check_digests(self):
+        """reads the digests enqueued so far (waits for the newest one's event: free behind a synchronisation)"""
+        from .models import CAPTURE_GUARD
+        with CAPTURE_GUARD.frame():
+            self._check_digests()
 
     def _decode(self, pkt):
         sps = dict(height=self.h, width=self.w, ec_part=1 if self.two else 0, use_ada_i=pkt.use_ada_i)
@@ -211,6 +283,7 @@ class SequenceDecoder:
         from .models import CAPTURE_GUARD
         with CAPTURE_GUARD.frame():
             last = self.p_net.finish_output() if self.defer else None
+            self._check_digests()
         return [] if last is None else [last]
 
 
