@@ -457,6 +457,27 @@ int dcvc_frame_to_planes(int dtype, int chroma, int bit_depth, int semi_planar, 
 int dcvc_frame_to_metric_planes(int dtype, int chroma, int max_val, const void* x_nchw, int Hp, int Wp, int H, int W,
                                 float* y, float* u, float* v, void* stream);
 /* ------------------------------------------------------------------------------------------
+ * Separable polyphase resampler on model frames (csrc/dcvc_resize.hip, docs/reduced_resolution.md; no reference
+ * counterpart): the scaler of a reduced-resolution run.  x_nchw [3][Hp][Wp] with the valid region H x W at its top left ->
+ * out_nchw [3][HOp][WOp] with the valid region HO x WO, one launch for the three planes.  The tables are device memory made
+ * by the caller (opendcvc_amd/resize.py): first_h [WO] / coef_h [WO][taps_h] give, per output column, the first source
+ * column of its window and the window's weights; first_v [HO] / coef_v [HO][taps_v] the same per output row.  The kernel
+ * knows no filter.  fp32 multiply and add in tap order, no fused multiply-add:
+ *   t[y][j]   = coef_h[j][0] * x[y][i_0],  then for k = 1 .. taps_h - 1:  t = t + coef_h[j][k] * x[y][i_k]
+ *   out[i][j] = coef_v[i][0] * t[y_0][j],  then for k = 1 .. taps_v - 1:  o = o + coef_v[i][k] * t[y_k][j]
+ *   i_k = min(max(first_h[j] + k, 0), W - 1),  y_k = min(max(first_v[i] + k, 0), H - 1)
+ * x is read in its storage type and widened; t stays fp32 (in LDS, never in memory); ONE rounding to the storage type at
+ * the end, no clamp to [0, 1].  Rows and columns of the output past HO x WO are the replicate pad of the valid region.
+ * The index clamps are part of the contract: whatever the tables hold, nothing outside the valid H x W region of the
+ * source is read - its padding may hold anything.
+ * Argument errors (checked before any device work; nothing is launched and out stays untouched): dtype; a size that is
+ * not positive, Hp < H, Wp < W, HOp < HO, WOp < WO; taps outside 1 .. 64; a NULL pointer; x not aligned to its element,
+ * out not 16-byte aligned or WOp no multiple of 8 (the output is stored 16 bytes per access; the source is gathered
+ * element by element), a table not 4-byte aligned. */
+int dcvc_resize_frame(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, void* out_nchw, int HOp, int WOp, int HO,
+                      int WO, const int32_t* first_h, const float* coef_h, int taps_h, const int32_t* first_v,
+                      const float* coef_v, int taps_v, void* stream);
+/* ------------------------------------------------------------------------------------------
  * Frame analysis for the encoder's scene-cut decision (csrc/dcvc_analysis.hip; no reference counterpart: the reference
  * harness places I frames by fi % intra_period only).  luma: H x W samples of the model input (DCVC_F16 / DCVC_F32), row
  * stride ld elements, read in place.  Per sample q = (int)fminf(fmaxf(rintf(v * 1023.0f), 0.0f), 1023.0f) (one fp32

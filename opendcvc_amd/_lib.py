@@ -150,6 +150,7 @@ _SIGS = {
     "dcvc_planes_to_frame": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _I, _I, _I, _I, _P, _P]),
     "dcvc_frame_to_planes": (_I, [_I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _L, _P]),
     "dcvc_frame_to_metric_planes": (_I, [_I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dcvc_resize_frame": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "dcvc_frame_analysis_ws_bytes": (_L, [_I, _I]),
     "dcvc_frame_analyze": (_I, [_I, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
     "dcvc_rate_estimate_ws_bytes": (_L, [_I, _I, _I]),

@@ -12,6 +12,10 @@ Layout:  NAL header byte = type(4 bits) | sps_id(4 bits)
   DIGEST: header (type 5), 8 bytes: the digest, little endian, of the entry the NEXT unit's frame puts into the DPB - that
          unit must be an I or P unit.  This project's extension (docs/state_digest.md): the reference's reader rejects
          type 5, streams written without digests are unchanged.
+  DISPLAY: header (type 6), display height (varint), display width (varint), filter id (1 byte: 0 bilinear, 1 bicubic,
+         2 lanczos3): the pictures of this SPS are to be resampled to that size after decoding.  Written directly behind
+         an SPS.  This project's extension (docs/reduced_resolution.md): the reference's reader rejects type 6, streams
+         written without it are unchanged.
 varint:  0xxxxxxx                      value < 2**7
          10xxxxxx xxxxxxxx             value < 2**14   (big endian)
          11xxxxxx + 3 bytes            value < 2**30   (big endian)
@@ -30,6 +34,12 @@ class NalType(enum.IntEnum):
     # this project's extension (docs/state_digest.md), not readable by the reference: the digest of the decoder state behind
     # the frame unit that follows
     NAL_DIGEST = 5
+    # this project's extension (docs/reduced_resolution.md), not readable by the reference: the size the pictures of an SPS
+    # are shown at, and the filter that takes them there
+    NAL_DISPLAY = 6
+
+
+DISPLAY_FILTERS = ("bilinear", "bicubic", "lanczos3")       # filter id = position (resize.FILTERS)
 
 
 def write_uint_adaptive(f, value):
@@ -150,6 +160,27 @@ def read_digest_remaining(f):
     return int.from_bytes(data, "little")
 
 
+def write_display(f, sps_id, height, width, filter_name):
+    if filter_name not in DISPLAY_FILTERS:
+        raise ValueError(f"display filter {filter_name!r}: one of {', '.join(DISPLAY_FILTERS)}")
+    if not 0 <= sps_id < 16:
+        raise ValueError(f"bad sps_id {sps_id}")
+    f.write(bytes(((int(NalType.NAL_DISPLAY) << 4) | sps_id,)))
+    n = 1 + write_uint_adaptive(f, height) + write_uint_adaptive(f, width)
+    f.write(bytes((DISPLAY_FILTERS.index(filter_name),)))
+    return n + 1
+
+
+def read_display_remaining(f):
+    """-> (height, width, filter_name)"""
+    height = read_uint_adaptive(f)
+    width = read_uint_adaptive(f)
+    fid = _byte(f)
+    if fid >= len(DISPLAY_FILTERS):
+        raise ValueError(f"display unit with unknown filter id {fid}")
+    return height, width, DISPLAY_FILTERS[fid]
+
+
 def frame_overhead_bytes(payload_len):
     """bytes write_ip puts in front of a payload of that length: NAL header, qp, the varint of the length (an SPS, written
     when a frame's parameters are new to the stream - twice in a typical one - is not counted)"""
@@ -166,18 +197,30 @@ def read_ip_remaining(f):
 
 
 class StreamWriter:
-    """What test_video.py:166,216-224 does per frame: SPS dedup + NAL writing; returns bytes written."""
+    """What test_video.py:166,216-224 does per frame: SPS dedup + NAL writing; returns bytes written.  display =
+    (height, width, filter_name): the size the decoded pictures are to be resampled to; where it differs from a frame's
+    size a display unit follows every SPS the writer emits (None, or equal sizes: the stream of the reference)."""
 
-    def __init__(self, f):
+    def __init__(self, f, display=None):
         self.f = f
         self.sps_helper = SPSHelper()
+        if display is not None:
+            display = (int(display[0]), int(display[1]), display[2])
+            if display[2] not in DISPLAY_FILTERS:
+                raise ValueError(f"display filter {display[2]!r}: one of {', '.join(DISPLAY_FILTERS)}")
+        self.display = display
 
     def write_frame(self, height, width, use_two_entropy_coders, pkt):
         sps = {"sps_id": -1, "height": height, "width": width, "ec_part": 1 if use_two_entropy_coders else 0,
                "use_ada_i": pkt.use_ada_i}
+        scaled = self.display is not None and self.display[:2] != (height, width)
+        if scaled and (self.display[0] < height or self.display[1] < width):
+            raise ValueError(f"display {self.display[1]}x{self.display[0]} below the coded size {width}x{height}")
         sps_id, is_new = self.sps_helper.get_sps_id(sps)
         sps["sps_id"] = sps_id
         n = write_sps(self.f, sps) if is_new else 0
+        if is_new and scaled:
+            n += write_display(self.f, sps_id, *self.display)
         if getattr(pkt, "digest", None) is not None:
             n += write_digest(self.f, sps_id, pkt.digest)
         return n + write_ip(self.f, pkt.is_i, sps_id, pkt.qp, pkt.bit_stream, chunked=getattr(pkt, "chunked", False))
@@ -186,22 +229,36 @@ class StreamWriter:
 class StreamReader:
     """test_video.py:265-276: yields (sps, is_i_frame, qp, payload) per frame; `chunked` tells whether the frame returned
     last carries a chunked payload (NAL_I_CHUNKED / NAL_P_CHUNKED), `digest` the digest unit in front of it (an int; None:
-    the frame came without one)."""
+    the frame came without one), `display` the (height, width, filter_name) of the display unit that belongs to that
+    frame's SPS (None until a display unit was read)."""
 
     def __init__(self, f):
         self.f = f
         self.sps_helper = SPSHelper()
         self.chunked = False
         self.digest = None
+        self.display = None
+        self._displays = {}          # sps_id -> the display unit behind that SPS
+        self._display_seen = False
 
     def read_frame(self):
         header = read_header(self.f)
         digest = None
-        while header["nal_type"] in (NalType.NAL_SPS, NalType.NAL_DIGEST):
+        while header["nal_type"] in (NalType.NAL_SPS, NalType.NAL_DIGEST, NalType.NAL_DISPLAY):
             if digest is not None:
                 raise ValueError(f"a digest unit is followed by {header['nal_type'].name}, not by the frame it describes")
             if header["nal_type"] == NalType.NAL_SPS:
                 self.sps_helper.add_sps_by_id(read_sps_remaining(self.f, header["sps_id"]))
+                self._displays.pop(header["sps_id"], None)          # (a new SPS under this id: its display unit follows, if any)
+            elif header["nal_type"] == NalType.NAL_DISPLAY:
+                display = read_display_remaining(self.f)
+                sps = self.sps_helper.get_sps_by_id(header["sps_id"])
+                if sps is None:
+                    raise ValueError(f"display unit refers to unknown SPS {header['sps_id']}")
+                if display[0] < sps["height"] or display[1] < sps["width"]:
+                    raise ValueError(f"display {display[1]}x{display[0]} below the coded size {sps['width']}x{sps['height']}")
+                self._displays[header["sps_id"]] = display
+                self._display_seen = True
             else:
                 digest = read_digest_remaining(self.f)
             header = read_header(self.f)
@@ -210,5 +267,7 @@ class StreamReader:
             raise ValueError(f"frame refers to unknown SPS {header['sps_id']}")
         qp, payload = read_ip_remaining(self.f)
         self.digest = digest
+        if self._display_seen:
+            self.display = self._displays.get(header["sps_id"])
         self.chunked = header["nal_type"] in (NalType.NAL_I_CHUNKED, NalType.NAL_P_CHUNKED)
         return sps, header["nal_type"] in (NalType.NAL_I, NalType.NAL_I_CHUNKED), qp, payload

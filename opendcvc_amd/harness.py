@@ -351,7 +351,7 @@ def _to_device(planes, device):
 def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=None, intra_period=-1,
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
                   src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
-                  target_bpp=None, digest=False):
+                  target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3"):
     """Encodes `frame_num` frames of a YUV 4:2:0 file (src_type "yuv420"), of a raw file in another pixel format
     (pipeline.PIXEL_FORMATS: "yuv420p10le", "yuv444p", "nv12", "p010le", ...; metrics with data_range = max_val, rec_path in
     the source's format) or of a directory of PNGs ("png": RGB, converted to YCbCr around the codec) into the reference's
@@ -370,13 +370,24 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     the per-frame lists frame_rc_qp and frame_rc_est_bpp.  digest: the encoder writes a digest unit in front of every frame
     (docs/state_digest.md: this project's extension, NOT readable by the reference; 9 bytes per frame, counted in the bits)
     and the decode loop checks its own reference state against it - a difference raises _lib.DigestMismatch; the log then
-    carries one extra key, digests_checked."""
+    carries one extra key, digests_checked.  coded_size = (height, width), at most the source's size and at least 16 x 16 (None
+    or the source's size: off): reduced-resolution coding (docs/reduced_resolution.md: this project's extension, NOT readable
+    by the reference) - every frame is resampled down to that size on the device (resize.Resampler, scale_filter: bilinear,
+    bicubic or lanczos3) before the encoder sees it, the stream's SPS carries the coded size and a display unit the source's
+    size and the filter, and the decode loop resamples every decoded frame up to what the display unit says before metrics
+    and rec_path, which stay those of the source; bpp and target_bpp stay per SOURCE pixel.  The log then ends in coded_height,
+    coded_width and scale_filter."""
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics {metrics!r}: 'host' or 'device'")
     if entropy not in ("host", "device"):
         raise ValueError(f"entropy {entropy!r}: 'host' or 'device'")
     if src_type not in SRC_TYPES:
         raise ValueError(f"src_type {src_type!r}: one of {', '.join(SRC_TYPES)}")
+    from .resize import FILTERS, Resampler, check_coded_size
+    if scale_filter not in FILTERS:
+        raise ValueError(f"scale_filter {scale_filter!r}: one of {', '.join(FILTERS)}")
+    coded_size = check_coded_size(coded_size, height, width)
+    ch, cw = coded_size or (height, width)          # what the SPS and the models see
     png = src_type == "png"
     fmt = PIXEL_FORMATS.get(src_type)          # None: the reference harness's own two source types
     if fmt is not None:
@@ -392,7 +403,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     import torch
     dev = torch.device(device)
     dtype = next(p_net.parameters()).dtype
-    two = use_two_entropy_coders(height, width)
+    two = use_two_entropy_coders(ch, cw)
+    scaler = Resampler(dev) if coded_size else None
     for m in (i_net, p_net):
         m.set_use_two_entropy_coders(two)
         m.entropy = entropy
@@ -408,14 +420,17 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         adaptive["digest"] = True
     enc = SequenceEncoder(i_net, p_net, qp_i, qp_p, intra_period, reset_interval, **adaptive)
     out = io.BytesIO()
-    writer = StreamWriter(out)
+    writer = StreamWriter(out, display=(height, width, scale_filter) if coded_size else None)
     frame_types, bits, enc_time, dec_time, psnrs, ssims = [], [], [], [], [], []
     for _ in range(frame_num):
         planes = _to_device(reader.read(), dev)
         torch.cuda.synchronize(dev)
         t0 = time.time()
-        pkt = enc.encode(to_input(planes, dtype))
-        bits.append(8 * writer.write_frame(height, width, two, pkt))
+        x = to_input(planes, dtype)
+        if scaler:
+            x = scaler.resample(x, (height, width), (ch, cw), scale_filter)
+        pkt = enc.encode(x)
+        bits.append(8 * writer.write_frame(ch, cw, two, pkt))
         torch.cuda.synchronize(dev)
         enc_time.append(time.time() - t0)
         frame_types.append(0 if pkt.is_i else 1)
@@ -433,7 +448,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     elif rec_path:
         rec = open(rec_path, "wb")
     from .pipeline import FramePacket
-    dec = SequenceDecoder(i_net, p_net, height, width, two)
+    dec = SequenceDecoder(i_net, p_net, ch, cw, two)
     dm = None
     if metrics == "device":
         from .metrics import DeviceMetrics
@@ -446,6 +461,12 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         dec.h, dec.w, dec.two = sps["height"], sps["width"], bool(sps["ec_part"])
         x_hat = dec.decode(FramePacket(is_i, qp, sps["use_ada_i"], payload, chunked=stream_reader.chunked,
                                        digest=stream_reader.digest))
+        if stream_reader.display is not None:       # the stream's word, not the arguments'
+            dh, dw, dfilter = stream_reader.display
+            if (dh, dw) != (height, width):
+                raise ValueError(f"the stream's display size {dw}x{dh} is not the source's {width}x{height}")
+            scaler = scaler or Resampler(dev)
+            x_hat = scaler.resample(x_hat, (sps["height"], sps["width"]), (dh, dw), dfilter)
         torch.cuda.synchronize(dev)
         dec.check_digests()
         dec_time.append(time.time() - t0)
@@ -499,6 +520,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
             log["frame_rc_est_bpp"] = [8 * b / (height * width) for b in enc.rc_est_bytes]
     if digest:
         log["digests_checked"] = dec.digests_checked
+    if coded_size:
+        log["coded_height"], log["coded_width"], log["scale_filter"] = ch, cw, scale_filter
     return log
 
 
@@ -699,7 +722,8 @@ def run_job(nets, job, opts):
                         calc_ssim=bool(opts.get("calc_ssim")), metrics=opts.get("metrics") or "host",
                         entropy=opts.get("entropy") or "host", scenecut=opts.get("scenecut") or 0,
                         min_keyint=opts.get("min_keyint") or 4, target_bpp=target_bpp(opts, job["src_width"], job["src_height"]),
-                        digest=bool(opts.get("digest")))
+                        digest=bool(opts.get("digest")), coded_size=opts.get("coded_size"),
+                        scale_filter=opts.get("scale_filter") or "lanczos3")
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -765,6 +789,12 @@ def _str2bool(v):
     raise ValueError("boolean value expected, got %r" % (v,))
 
 
+def _coded_size(text):
+    """--coded-size WxH -> (height, width); argparse turns the ValueError of a malformed size into a usage error"""
+    from .resize import parse_size
+    return parse_size(text)
+
+
 def build_parser():
     """The command line.  Every option of the reference's test_video.py (parse_args, test_video.py:30-56) is accepted under
     its own spelling and value convention too (`--test_config`, `--model_path_i`, `--write_stream 1`, `--cuda_idx 0 1`, ...):
@@ -826,6 +856,12 @@ def build_parser():
     ap.add_argument("--digest", **flag,
                     help="write a digest of the decoder's reference state in front of every frame and check it while decoding "
                          "(docs/state_digest.md) - this project's extension, not readable by the reference")
+    ap.add_argument("--coded-size", "--coded_size", type=_coded_size, default=None, metavar="WxH",
+                    help="reduced-resolution coding: resample every frame down to W x H on the device, code that, and resample "
+                         "the decoded frames back up; metrics, bpp and --target-bpp stay those of the source "
+                         "(docs/reduced_resolution.md) - this project's extension, not readable by the reference")
+    ap.add_argument("--scale-filter", "--scale_filter", choices=("bilinear", "bicubic", "lanczos3"), default="lanczos3",
+                    help="the resampling filter of --coded-size, down and up")
     ap.add_argument("--model-i", "--model_path_i", help="DMCI checkpoint (.pth.tar); synthetic weights if omitted")
     ap.add_argument("--model-p", "--model_path_p", help="DMC checkpoint")
     ap.add_argument("--force-zero-thres", "--force_zero_thres", type=float, default=0.12)
@@ -852,7 +888,8 @@ def manifest_options(args, ap):
                 force_zero_thres=args.force_zero_thres, fp32=args.fp32, stream_path=stream_path,
                 verbose=args.verbose, verbose_json=args.verbose_json, calc_ssim=args.calc_ssim, metrics=args.metrics,
                 entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint, target_bpp=args.target_bpp,
-                target_kbps=args.target_kbps, fps=args.fps, digest=args.digest, force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
+                target_kbps=args.target_kbps, fps=args.fps, digest=args.digest, coded_size=args.coded_size,
+                scale_filter=args.scale_filter, force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
     return opts, gpus
 
 
@@ -907,7 +944,8 @@ def main(argv=None):
                     intra_period=args.intra_period, reset_interval=args.reset_interval, verbose=args.verbose,
                     verbose_json=args.verbose_json, src_type=args.src_type, calc_ssim=args.calc_ssim, metrics=args.metrics,
                     entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint,
-                    target_bpp=target_bpp(vars(args), args.width, args.height), digest=args.digest)
+                    target_bpp=target_bpp(vars(args), args.width, args.height), digest=args.digest,
+                    coded_size=args.coded_size, scale_filter=args.scale_filter)
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:
