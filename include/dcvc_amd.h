@@ -478,6 +478,36 @@ int dcvc_resize_frame(int dtype, const void* x_nchw, int Hp, int Wp, int H, int 
                       int WO, const int32_t* first_h, const float* coef_h, int taps_h, const int32_t* first_v,
                       const float* coef_v, int taps_v, void* stream);
 /* ------------------------------------------------------------------------------------------
+ * Film-grain synthesis and estimation on model frames (csrc/dcvc_grain.hip; docs/film_grain.md is the normative text; no
+ * reference counterpart).  The parameters of a grain unit, passed by value: strengths are standard deviations in units of
+ * 2^-11 of full scale, scale_y[k] the luma strength at intensity band k (centred at (k + 0.5) / 8). */
+typedef struct dcvc_grain_params {
+    uint16_t seed;
+    uint8_t corr;               /* 0, 1, 2: white, 3 x 3 binomial, 5 x 5 binomial */
+    uint8_t scale_y[8];
+    uint8_t scale_cb;
+    uint8_t scale_cr;
+} dcvc_grain_params;
+/* x_nchw [3][Hp][Wp] with the picture H x W at its top left -> out_nchw, the same layout: inside the picture
+ *   out = v + float(g * gain * s) * 2^-30   (g: the shaped noise of (seed, t, plane, row, column), an integer; s: the strength
+ *   at the sample - luma: interpolated between the bands from the sample itself; ONE fp32 add, ONE rounding to the storage
+ *   type, no clamp; where the product is 0 or v is a NaN, out has the bits of v),
+ * outside it a bit copy.  One launch for the three planes; no sample's neighbours are read, so out_nchw may be x_nchw.  t:
+ * the frame's counter since the grain unit.  Nothing is allocated and nothing waited for.
+ * Argument errors (checked before any device work): dtype; a size that is not positive, Hp < H, Wp < W; a NULL pointer; a
+ * tensor not aligned to its element (16-byte alignment and rows of a multiple of 16 bytes are used where present, not
+ * required); corr above 2. */
+int dcvc_grain_apply(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, void* out_nchw, dcvc_grain_params params,
+                     uint32_t t, void* stream);
+/* The estimator's table of a (noisy, clean) pair of such frames: over every whole 16 x 16 block of the H x W picture whose
+ * clean luma is flat, table [12][2] int64 (device memory, 8-byte aligned; zeroed by the call) = (count, sum) per line - the
+ * eight luma bands' residual variance numerators, Cb's, Cr's, and the horizontal and vertical lag-1 sums.  Integer
+ * arithmetic behind the two roundings dq = rint((noisy - clean) * 4096), cq = rint(clean * 4096): the table does not
+ * depend on the order of summation.  A picture smaller than a block gives the zero table.  Argument errors as above, and a
+ * table that is NULL or misaligned. */
+int dcvc_grain_stats(int dtype, const void* noisy_nchw, const void* clean_nchw, int Hp, int Wp, int H, int W, int64_t* table,
+                     void* stream);
+/* ------------------------------------------------------------------------------------------
  * Frame analysis for the encoder's scene-cut decision (csrc/dcvc_analysis.hip; no reference counterpart: the reference
  * harness places I frames by fi % intra_period only).  luma: H x W samples of the model input (DCVC_F16 / DCVC_F32), row
  * stride ld elements, read in place.  Per sample q = (int)fminf(fmaxf(rintf(v * 1023.0f), 0.0f), 1023.0f) (one fp32

@@ -48,6 +48,12 @@ def build(force=False):
     return LIB_PATH
 
 
+class GrainParamsC(ctypes.Structure):
+    """dcvc_grain_params, passed by value (docs/film_grain.md)"""
+    _fields_ = [("seed", ctypes.c_uint16), ("corr", c_uint8), ("scale_y", c_uint8 * 8), ("scale_cb", c_uint8),
+                ("scale_cr", c_uint8)]
+
+
 _P = c_void_p
 _I = c_int
 _L = c_int64
@@ -151,6 +157,8 @@ _SIGS = {
     "dcvc_frame_to_planes": (_I, [_I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _L, _P]),
     "dcvc_frame_to_metric_planes": (_I, [_I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dcvc_resize_frame": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
+    "dcvc_grain_apply": (_I, [_I, _P, _I, _I, _I, _I, _P, GrainParamsC, c_uint32, _P]),
+    "dcvc_grain_stats": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "dcvc_frame_analysis_ws_bytes": (_L, [_I, _I]),
     "dcvc_frame_analyze": (_I, [_I, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
     "dcvc_rate_estimate_ws_bytes": (_L, [_I, _I, _I]),

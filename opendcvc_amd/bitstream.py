@@ -16,6 +16,11 @@ Layout:  NAL header byte = type(4 bits) | sps_id(4 bits)
          2 lanczos3): the pictures of this SPS are to be resampled to that size after decoding.  Written directly behind
          an SPS.  This project's extension (docs/reduced_resolution.md): the reference's reader rejects type 6, streams
          written without it are unchanged.
+  GRAIN: header (type 7), 13 bytes: seed (2 bytes, little endian), corr (0, 1, 2), the eight luma strengths, the Cb and the Cr
+         strength (grain.GrainParams): film grain to be put on the displayed pictures from the NEXT unit's frame on, until
+         the next grain unit; all strengths 0 switches it off.  Written in front of an I frame, in front of its digest unit
+         if it has one.  This project's extension (docs/film_grain.md): the reference's reader rejects type 7, streams
+         written without it are unchanged.
 varint:  0xxxxxxx                      value < 2**7
          10xxxxxx xxxxxxxx             value < 2**14   (big endian)
          11xxxxxx + 3 bytes            value < 2**30   (big endian)
@@ -37,6 +42,9 @@ class NalType(enum.IntEnum):
     # this project's extension (docs/reduced_resolution.md), not readable by the reference: the size the pictures of an SPS
     # are shown at, and the filter that takes them there
     NAL_DISPLAY = 6
+    # this project's extension (docs/film_grain.md), not readable by the reference: the film grain to synthesise on the
+    # displayed pictures from the next frame on
+    NAL_GRAIN = 7
 
 
 DISPLAY_FILTERS = ("bilinear", "bicubic", "lanczos3")       # filter id = position (resize.FILTERS)
@@ -160,6 +168,26 @@ def read_digest_remaining(f):
     return int.from_bytes(data, "little")
 
 
+GRAIN_UNIT_BYTES = 14        # header + grain.UNIT_BODY_BYTES
+
+
+def write_grain(f, sps_id, params):
+    """params: a grain.GrainParams"""
+    if not 0 <= sps_id < 16:
+        raise ValueError(f"bad sps_id {sps_id}")
+    f.write(bytes(((int(NalType.NAL_GRAIN) << 4) | sps_id,)) + params.to_bytes())
+    return GRAIN_UNIT_BYTES
+
+
+def read_grain_remaining(f):
+    """-> grain.GrainParams; ValueError for a corr above 2, EOFError for a unit cut short"""
+    from .grain import GrainParams
+    data = f.read(GRAIN_UNIT_BYTES - 1)
+    if len(data) != GRAIN_UNIT_BYTES - 1:
+        raise EOFError("truncated DCVC-RT grain unit")
+    return GrainParams.from_bytes(data)
+
+
 def write_display(f, sps_id, height, width, filter_name):
     if filter_name not in DISPLAY_FILTERS:
         raise ValueError(f"display filter {filter_name!r}: one of {', '.join(DISPLAY_FILTERS)}")
@@ -199,7 +227,8 @@ def read_ip_remaining(f):
 class StreamWriter:
     """What test_video.py:166,216-224 does per frame: SPS dedup + NAL writing; returns bytes written.  display =
     (height, width, filter_name): the size the decoded pictures are to be resampled to; where it differs from a frame's
-    size a display unit follows every SPS the writer emits (None, or equal sizes: the stream of the reference)."""
+    size a display unit follows every SPS the writer emits (None, or equal sizes: the stream of the reference).  A packet
+    whose `grain` is a grain.GrainParams gets a grain unit in front of its digest unit / its frame."""
 
     def __init__(self, f, display=None):
         self.f = f
@@ -221,6 +250,8 @@ class StreamWriter:
         n = write_sps(self.f, sps) if is_new else 0
         if is_new and scaled:
             n += write_display(self.f, sps_id, *self.display)
+        if getattr(pkt, "grain", None) is not None:
+            n += write_grain(self.f, sps_id, pkt.grain)
         if getattr(pkt, "digest", None) is not None:
             n += write_digest(self.f, sps_id, pkt.digest)
         return n + write_ip(self.f, pkt.is_i, sps_id, pkt.qp, pkt.bit_stream, chunked=getattr(pkt, "chunked", False))
@@ -230,7 +261,9 @@ class StreamReader:
     """test_video.py:265-276: yields (sps, is_i_frame, qp, payload) per frame; `chunked` tells whether the frame returned
     last carries a chunked payload (NAL_I_CHUNKED / NAL_P_CHUNKED), `digest` the digest unit in front of it (an int; None:
     the frame came without one), `display` the (height, width, filter_name) of the display unit that belongs to that
-    frame's SPS (None until a display unit was read)."""
+    frame's SPS (None until a display unit was read), `grain` the grain.GrainParams in force for that frame (None: no grain
+    unit so far, or the last one switched grain off) and `grain_t` the frame's counter since that unit (0 for the frame the
+    unit stands in front of)."""
 
     def __init__(self, f):
         self.f = f
@@ -240,11 +273,14 @@ class StreamReader:
         self.display = None
         self._displays = {}          # sps_id -> the display unit behind that SPS
         self._display_seen = False
+        self.grain = None
+        self.grain_t = 0
 
     def read_frame(self):
         header = read_header(self.f)
         digest = None
-        while header["nal_type"] in (NalType.NAL_SPS, NalType.NAL_DIGEST, NalType.NAL_DISPLAY):
+        grain = None
+        while header["nal_type"] in (NalType.NAL_SPS, NalType.NAL_DIGEST, NalType.NAL_DISPLAY, NalType.NAL_GRAIN):
             if digest is not None:
                 raise ValueError(f"a digest unit is followed by {header['nal_type'].name}, not by the frame it describes")
             if header["nal_type"] == NalType.NAL_SPS:
@@ -259,6 +295,8 @@ class StreamReader:
                     raise ValueError(f"display {display[1]}x{display[0]} below the coded size {sps['width']}x{sps['height']}")
                 self._displays[header["sps_id"]] = display
                 self._display_seen = True
+            elif header["nal_type"] == NalType.NAL_GRAIN:
+                grain = read_grain_remaining(self.f)
             else:
                 digest = read_digest_remaining(self.f)
             header = read_header(self.f)
@@ -267,6 +305,10 @@ class StreamReader:
             raise ValueError(f"frame refers to unknown SPS {header['sps_id']}")
         qp, payload = read_ip_remaining(self.f)
         self.digest = digest
+        if grain is not None:
+            self.grain, self.grain_t = (grain if grain.active else None), 0
+        else:
+            self.grain_t += 1
         if self._display_seen:
             self.display = self._displays.get(header["sps_id"])
         self.chunked = header["nal_type"] in (NalType.NAL_I_CHUNKED, NalType.NAL_P_CHUNKED)

@@ -351,7 +351,7 @@ def _to_device(planes, device):
 def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=None, intra_period=-1,
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
                   src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
-                  target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3"):
+                  target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3", film_grain=None):
     """Encodes `frame_num` frames of a YUV 4:2:0 file (src_type "yuv420"), of a raw file in another pixel format
     (pipeline.PIXEL_FORMATS: "yuv420p10le", "yuv444p", "nv12", "p010le", ...; metrics with data_range = max_val, rec_path in
     the source's format) or of a directory of PNGs ("png": RGB, converted to YCbCr around the codec) into the reference's
@@ -376,7 +376,15 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     bicubic or lanczos3) before the encoder sees it, the stream's SPS carries the coded size and a display unit the source's
     size and the filter, and the decode loop resamples every decoded frame up to what the display unit says before metrics
     and rec_path, which stay those of the source; bpp and target_bpp stay per SOURCE pixel.  The log then ends in coded_height,
-    coded_width and scale_filter."""
+    coded_width and scale_filter.  film_grain (None = off): film-grain synthesis (docs/film_grain.md: this project's extension,
+    NOT readable by the reference) - a grain.GrainParams, written as a grain unit in front of every I frame, or "auto": at every
+    I frame the grain the codec removed is estimated on the device (grain.FilmGrain.estimate of the source frame against the I
+    frame's reconstruction - with coded_size the reconstruction resampled up against the full-size source, so grain is measured
+    at the size it is applied at; the unit's seed is the frame's index) and written if there is any.  The decode loop needs
+    no switch: while the stream's grain unit is in force, the picture behind the display upscale goes through
+    grain.FilmGrain.apply inside the timed region.  Metrics are taken from the picture BEFORE synthesis - they do not depend
+    on the switch - and rec_path gets the picture after it.  A unit's 14 bytes count in its frame's bits.  The log then ends
+    in grain_units, grain_scale_y (the last unit's eight values) and grain_corr."""
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics {metrics!r}: 'host' or 'device'")
     if entropy not in ("host", "device"):
@@ -387,6 +395,9 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     if scale_filter not in FILTERS:
         raise ValueError(f"scale_filter {scale_filter!r}: one of {', '.join(FILTERS)}")
     coded_size = check_coded_size(coded_size, height, width)
+    from .grain import FilmGrain, GrainParams
+    if not (film_grain is None or film_grain == "auto" or isinstance(film_grain, GrainParams)):
+        raise ValueError(f"film_grain {film_grain!r}: None, 'auto' or a GrainParams")
     ch, cw = coded_size or (height, width)          # what the SPS and the models see
     png = src_type == "png"
     fmt = PIXEL_FORMATS.get(src_type)          # None: the reference harness's own two source types
@@ -418,6 +429,16 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         i_net.rate_estimate = p_net.rate_estimate = False       # (one pair codes every point)
     if digest:
         adaptive["digest"] = True
+    grainer = FilmGrain(dev) if film_grain is not None else None
+    source = []                                      # "auto": the full-size input of the frame being coded
+    if film_grain == "auto":
+        def estimate_grain(x_coded, x_hat):
+            if scaler:
+                x_hat = scaler.resample(x_hat, (ch, cw), (height, width), scale_filter)
+            return grainer.estimate(source[0], x_hat, (height, width), len(frame_types))
+        adaptive["grain"] = estimate_grain
+    elif film_grain is not None:
+        adaptive["grain"] = film_grain
     enc = SequenceEncoder(i_net, p_net, qp_i, qp_p, intra_period, reset_interval, **adaptive)
     out = io.BytesIO()
     writer = StreamWriter(out, display=(height, width, scale_filter) if coded_size else None)
@@ -427,6 +448,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         torch.cuda.synchronize(dev)
         t0 = time.time()
         x = to_input(planes, dtype)
+        source[:] = [x]
         if scaler:
             x = scaler.resample(x, (height, width), (ch, cw), scale_filter)
         pkt = enc.encode(x)
@@ -467,6 +489,10 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                 raise ValueError(f"the stream's display size {dw}x{dh} is not the source's {width}x{height}")
             scaler = scaler or Resampler(dev)
             x_hat = scaler.resample(x_hat, (sps["height"], sps["width"]), (dh, dw), dfilter)
+        shown = x_hat                               # what rec_path gets; the metrics below are x_hat's
+        if stream_reader.grain is not None:
+            grainer = grainer or FilmGrain(dev)
+            shown = grainer.apply(x_hat, (height, width), stream_reader.grain, stream_reader.grain_t)
         torch.cuda.synchronize(dev)
         dec.check_digests()
         dec_time.append(time.time() - t0)
@@ -477,7 +503,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
             ssims.append(s_)
             if rec_path:        # clamp * 255 rounded to uint8 (test_video.py:314-318), names like the source's
                 from PIL import Image
-                rgb8 = reconstruct_rgb(x_hat, height, width).float().round().to(torch.uint8).cpu().numpy()
+                rgb8 = reconstruct_rgb(shown, height, width).float().round().to(torch.uint8).cpu().numpy()
                 Image.fromarray(rgb8.transpose(1, 2, 0)).save(os.path.join(rec_path, "im%s.png" % str(fi + 1).zfill(reader.digits)))
             continue
         if fmt is not None:
@@ -485,7 +511,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
             psnrs.append(p_)
             ssims.append(s_)
             if rec is not None:     # the source's own format (pipeline.store_frame)
-                for plane in store_frame(x_hat, height, width, fmt):
+                for plane in store_frame(shown, height, width, fmt):
                     rec.write(plane.cpu().numpy().tobytes())
             continue
         y, u, v = planes
@@ -497,7 +523,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
             psnrs.append(yuv420_distortion(x_hat, y, u, v))
             ssims.append(yuv420_msssim(x_hat, y, u, v) if calc_ssim else [0.0, 0.0, 0.0, 0.0])
         if rec is not None:     # clamp * 255, Y rounded, chroma truncated (test_video.py:307-311)
-            for plane in store_yuv420_frame(x_hat, height, width):
+            for plane in store_yuv420_frame(shown, height, width):
                 rec.write(plane.cpu().numpy().tobytes())
     reader.close()
     if rec is not None:
@@ -522,6 +548,11 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         log["digests_checked"] = dec.digests_checked
     if coded_size:
         log["coded_height"], log["coded_width"], log["scale_filter"] = ch, cw, scale_filter
+    if film_grain is not None:
+        last = enc.grain_units[-1] if enc.grain_units else None
+        log["grain_units"] = len(enc.grain_units)
+        log["grain_scale_y"] = list(last.scale_y) if last else []
+        log["grain_corr"] = last.corr if last else 0
     return log
 
 
@@ -723,7 +754,7 @@ def run_job(nets, job, opts):
                         entropy=opts.get("entropy") or "host", scenecut=opts.get("scenecut") or 0,
                         min_keyint=opts.get("min_keyint") or 4, target_bpp=target_bpp(opts, job["src_width"], job["src_height"]),
                         digest=bool(opts.get("digest")), coded_size=opts.get("coded_size"),
-                        scale_filter=opts.get("scale_filter") or "lanczos3")
+                        scale_filter=opts.get("scale_filter") or "lanczos3", film_grain=opts.get("film_grain") or None)
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -862,6 +893,10 @@ def build_parser():
                          "(docs/reduced_resolution.md) - this project's extension, not readable by the reference")
     ap.add_argument("--scale-filter", "--scale_filter", choices=("bilinear", "bicubic", "lanczos3"), default="lanczos3",
                     help="the resampling filter of --coded-size, down and up")
+    ap.add_argument("--film-grain", "--film_grain", **flag,
+                    help="film-grain synthesis: at every I frame the grain the codec removed is estimated on the device and "
+                         "written as a 14-byte grain unit; the decode loop puts it back on the pictures it stores, not on "
+                         "the ones it measures (docs/film_grain.md) - this project's extension, not readable by the reference")
     ap.add_argument("--model-i", "--model_path_i", help="DMCI checkpoint (.pth.tar); synthetic weights if omitted")
     ap.add_argument("--model-p", "--model_path_p", help="DMC checkpoint")
     ap.add_argument("--force-zero-thres", "--force_zero_thres", type=float, default=0.12)
@@ -889,7 +924,7 @@ def manifest_options(args, ap):
                 verbose=args.verbose, verbose_json=args.verbose_json, calc_ssim=args.calc_ssim, metrics=args.metrics,
                 entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint, target_bpp=args.target_bpp,
                 target_kbps=args.target_kbps, fps=args.fps, digest=args.digest, coded_size=args.coded_size,
-                scale_filter=args.scale_filter, force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
+                scale_filter=args.scale_filter, film_grain="auto" if args.film_grain else None, force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
     return opts, gpus
 
 
@@ -945,7 +980,8 @@ def main(argv=None):
                     verbose_json=args.verbose_json, src_type=args.src_type, calc_ssim=args.calc_ssim, metrics=args.metrics,
                     entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint,
                     target_bpp=target_bpp(vars(args), args.width, args.height), digest=args.digest,
-                    coded_size=args.coded_size, scale_filter=args.scale_filter)
+                    coded_size=args.coded_size, scale_filter=args.scale_filter,
+                    film_grain="auto" if args.film_grain else None)
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:

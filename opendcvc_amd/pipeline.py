@@ -16,6 +16,8 @@ class FramePacket:
     use_ada_i: int
     bit_stream: bytes
     chunked: bool = False        # chunked payload (the models' entropy="device" mode): written as NAL_I_CHUNKED / NAL_P_CHUNKED
+    grain: Optional[object] = None   # grain.GrainParams in force from this frame on (docs/film_grain.md): a NAL_GRAIN unit,
+                                     # written in front of the digest unit as it stands in front of it here
     digest: Optional[int] = None     # digest of the entry the frame puts into the DPB (docs/state_digest.md): a NAL_DIGEST unit
 
 
@@ -54,15 +56,25 @@ class SequenceEncoder:
     buffer is overwritten by the next frame, which stream order puts behind the read).  Without defer_stream encode() waits
     for the digest's event - the tail of the frame's kernels it otherwise leaves in flight - before it returns the packet;
     with it the value is read when the packet comes out, one call later.  With rate control the unit's 9 bytes count in what
-    the controller is fed and in rc_bytes."""
+    the controller is fed and in rc_bytes.
+
+    grain (None = off: nothing changes): film grain for the decoder to synthesise (docs/film_grain.md).  A grain.GrainParams:
+    every I frame's packet carries it.  A callable (x, x_hat) -> GrainParams | None: called at every I frame with the
+    encoder's input and the I frame's reconstruction, and the packet carries what it returns (None: no unit); refused
+    together with defer_stream, where the picture is not at hand when the packet is made.  grain_units lists what was
+    attached.  With rate control a unit's 14 bytes count in what the controller is fed and in rc_bytes of its I frame."""
 
     def __init__(self, i_net, p_net, qp_i, qp_p=None, intra_period=-1, reset_interval=32, defer_stream=False,
-                 scenecut=None, min_keyint=4, analyzer=None, rate=None, digest=False):
+                 scenecut=None, min_keyint=4, analyzer=None, rate=None, digest=False, grain=None):
         self.i_net, self.p_net = i_net, p_net
         self.defer = defer_stream
         self._held = None            # (qp, use_ada_i, chunked, digest handle) of the P frame whose stream is still pending
         self.digest = bool(digest)
         self._digester = None        # (made at the first frame, on the frame's device)
+        if callable(grain) and defer_stream:
+            raise ValueError("a grain estimator cannot be combined with defer_stream: give the GrainParams themselves")
+        self.grain = grain
+        self.grain_units = []
         self.qp_i = qp_i
         self.qp_p = qp_i if qp_p is None else qp_p
         self.intra_period = intra_period
@@ -97,7 +109,7 @@ class SequenceEncoder:
             from .bitstream import frame_overhead_bytes
             for pkt in (pkts if isinstance(pkts, list) else [pkts]):
                 n = len(pkt.bit_stream)
-                self.rc_bytes.append(n + frame_overhead_bytes(n) + self._unit_bytes())
+                self.rc_bytes.append(n + frame_overhead_bytes(n) + self._unit_bytes(getattr(pkt, "grain", None)))
                 self.rate.record_exact(self._rc_out, n)
                 self._rc_out += 1
         return pkts
@@ -110,17 +122,24 @@ class SequenceEncoder:
             self._rc_pending = None
         return self.rate.base_qp()
 
-    def _rc_note(self, klass, base, qp, enc):
+    def _rc_note(self, klass, base, qp, enc, grain=None):
         from .bitstream import frame_overhead_bytes
         est = int(enc["est_bytes"])          # (compress() has waited for the hand-off's event, not for the host coder)
-        est += frame_overhead_bytes(est) + self._unit_bytes()
+        est += frame_overhead_bytes(est) + self._unit_bytes(grain)
         self._rc_pending = (klass, base, est)
         self.rc_qp.append(qp)
         self.rc_est_bytes.append(est)
 
-    def _unit_bytes(self):
-        from .bitstream import DIGEST_UNIT_BYTES
-        return DIGEST_UNIT_BYTES if self.digest else 0
+    def _unit_bytes(self, grain=None):
+        from .bitstream import DIGEST_UNIT_BYTES, GRAIN_UNIT_BYTES
+        return (DIGEST_UNIT_BYTES if self.digest else 0) + (GRAIN_UNIT_BYTES if grain is not None else 0)
+
+    def _grain_of(self, x_padded, x_hat):
+        """the I frame's grain unit (None: none)"""
+        grain = self.grain(x_padded, x_hat) if callable(self.grain) else self.grain
+        if grain is not None:
+            self.grain_units.append(grain)
+        return grain
 
     def _enqueue_digest(self):
         """digest on: the handle of the newest DPB entry's digest, enqueued on the current stream"""
@@ -169,14 +188,15 @@ class SequenceEncoder:
             base = self._rc_base() if self.rate is not None else None
             qp_i = self.qp_i if base is None else self.rate.i_qp(base)
             enc = self.i_net.compress(x_padded, qp_i)
+            grain = self._grain_of(x_padded, enc["x_hat"]) if self.grain is not None else None
             if base is not None:
                 from .ratecontrol import I_CLASS
-                self._rc_note(I_CLASS, base, qp_i, enc)
+                self._rc_note(I_CLASS, base, qp_i, enc, grain)
             self.p_net.clear_dpb()
             self.p_net.add_ref_frame(None, enc["x_hat"])
             handle = self._enqueue_digest()
             pkt = FramePacket(True, qp_i, 0, enc["bit_stream"], chunked=bool(enc.get("chunked", False)),
-                              digest=None if handle is None else handle.value())
+                              digest=None if handle is None else handle.value(), grain=grain)
             return done + [pkt] if self.defer else pkt
         use_ada_i = 0
         if self.reset_interval > 0 and pos % self.reset_interval == 1:
