@@ -263,7 +263,7 @@ class StreamReader:
     the frame came without one), `display` the (height, width, filter_name) of the display unit that belongs to that
     frame's SPS (None until a display unit was read), `grain` the grain.GrainParams in force for that frame (None: no grain
     unit so far, or the last one switched grain off) and `grain_t` the frame's counter since that unit (0 for the frame the
-    unit stands in front of)."""
+    unit stands in front of).  read_packet() is read_frame() with the frame as a pipeline.FramePacket."""
 
     def __init__(self, f):
         self.f = f
@@ -313,3 +313,10 @@ class StreamReader:
             self.display = self._displays.get(header["sps_id"])
         self.chunked = header["nal_type"] in (NalType.NAL_I_CHUNKED, NalType.NAL_P_CHUNKED)
         return sps, header["nal_type"] in (NalType.NAL_I, NalType.NAL_I_CHUNKED), qp, payload
+
+    def read_packet(self):
+        """read_frame() as what a decoder takes: -> (sps, pipeline.FramePacket), the packet with the frame's `chunked` and
+        `digest`; `display`, `grain` and `grain_t` are left as read_frame() leaves them"""
+        from .pipeline import FramePacket
+        sps, is_i, qp, payload = self.read_frame()
+        return sps, FramePacket(is_i, qp, sps["use_ada_i"], payload, chunked=self.chunked, digest=self.digest)

@@ -29,9 +29,9 @@ import time
 
 import numpy as np
 
-from .bitstream import StreamReader, StreamWriter
-from .pipeline import (PIXEL_FORMATS, PixelFormat, SequenceDecoder, SequenceEncoder, load_frame, load_yuv420_frame,
-                       store_frame, store_yuv420_frame, use_two_entropy_coders)
+from .bitstream import StreamWriter
+from .pipeline import (PIXEL_FORMATS, PixelFormat, SequenceEncoder, StreamDecoder, load_frame, load_yuv420_frame, store_frame,
+                       store_yuv420_frame, use_two_entropy_coders)
 
 SRC_TYPES = ("yuv420", "png") + tuple(PIXEL_FORMATS)     # "yuv420": planar 8-bit 4:2:0 with the reference harness's arithmetic
 
@@ -51,18 +51,22 @@ def calc_psnr(a, b, data_range=255.0):
     return psnr_from_mse(float(np.mean(np.square(a - b))), data_range)
 
 
-def yuv420_distortion(x_hat, y, u, v):
-    """test_video.py:94-111 on the device: x_hat [1,3,H',W'] (model dtype, cropped here), y/u/v uint8 planes.
-    The planes of the reconstruction are the clamped, NOT rounded, values (chroma = 2x2 mean), in the
-    reconstruction's own dtype like the reference's tensors; squared errors are summed in float64."""
+def _yuv420_metric_planes(x_hat, H, W):
+    """the planes the host metrics of a YUV 4:2:0 source compare: the H x W crop of x_hat [1,3,H',W'], clamped, NOT rounded
+    (chroma = 2x2 mean), in the reconstruction's own dtype like the reference's tensors -> (y, u, v)"""
     import torch
-    H, W = y.shape
     x = x_hat[:, :, :H, :W]
     y_rec = torch.clamp(x[:, :1] * 255, 0, 255)
     uv_rec = torch.clamp(torch.nn.functional.avg_pool2d(x[:, 1:], 2) * 255, 0, 255)
-    out = []
-    for rec, src in ((y_rec[0, 0], y), (uv_rec[0, 0], u), (uv_rec[0, 1], v)):
-        out.append(psnr_from_mse(float(torch.mean(torch.square(rec.double() - src.double())))))
+    return y_rec[0, 0], uv_rec[0, 0], uv_rec[0, 1]
+
+
+def yuv420_distortion(x_hat, y, u, v):
+    """test_video.py:94-111 on the device: x_hat [1,3,H',W'] (model dtype, cropped here), y/u/v uint8 planes.
+    PSNR of the planes of _yuv420_metric_planes; squared errors are summed in float64."""
+    import torch
+    out = [psnr_from_mse(float(torch.mean(torch.square(rec.double() - src.double()))))
+           for rec, src in zip(_yuv420_metric_planes(x_hat, *y.shape), (y, u, v))]
     return [(6 * out[0] + out[1] + out[2]) / 8] + out
 
 
@@ -159,13 +163,8 @@ def load_rgb_frame(rgb, dtype, pad_to=16):
 def yuv420_msssim(x_hat, y, u, v):
     """--calc_ssim on a YUV 4:2:0 source (test_video.py:106-112): MS-SSIM of the planes yuv420_distortion compares, combined
     (6 Y + U + V) / 8; host computation on the clamped, not rounded, planes"""
-    import torch
-    H, W = y.shape
-    x = x_hat[:, :, :H, :W]
-    y_rec = torch.clamp(x[:, :1] * 255, 0, 255)[0, 0]
-    uv_rec = torch.clamp(torch.nn.functional.avg_pool2d(x[:, 1:], 2) * 255, 0, 255)[0]
     vals = [calc_msssim(src.cpu().numpy(), rec.float().cpu().numpy().astype(np.float64))
-            for rec, src in ((y_rec, y), (uv_rec[0], u), (uv_rec[1], v))]
+            for rec, src in zip(_yuv420_metric_planes(x_hat, *y.shape), (y, u, v))]
     return [(6 * vals[0] + vals[1] + vals[2]) / 8] + vals
 
 
@@ -347,213 +346,240 @@ def _to_device(planes, device):
     return [torch.from_numpy(np.array(p, copy=True)).to(device) for p in planes]     # (the planes may be read-only views of the file buffer)
 
 
-# ---------------------------------------------------------------------------------- one rate point
-def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=None, intra_period=-1,
-                  reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
-                  src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
-                  target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3", film_grain=None):
-    """Encodes `frame_num` frames of a YUV 4:2:0 file (src_type "yuv420"), of a raw file in another pixel format
-    (pipeline.PIXEL_FORMATS: "yuv420p10le", "yuv444p", "nv12", "p010le", ...; metrics with data_range = max_val, rec_path in
-    the source's format) or of a directory of PNGs ("png": RGB, converted to YCbCr around the codec) into the reference's
-    container (optionally written to bin_path), decodes the container again, and returns the reference-schema log.  i_net / p_net: DMCI / DMC (weights loaded, .update() called, on `device`,
-    optionally .half()).  calc_ssim: MS-SSIM per frame (host computation, slow) instead of zeros.  rec_path: the decoded
-    sequence as a planar YUV file / as PNGs in that directory.  metrics: "host" (torch glue + host numpy / scipy MS-SSIM) or
-    "device" (metrics.DeviceMetrics: PSNR and MS-SSIM by HIP kernels, one synchronisation per frame).  entropy: "host" (the
-    reference's stream, host rANS coder) or "device" (chunked payloads entropy-coded by HIP kernels, docs/chunked_stream.md:
-    this project's extension, NOT readable by the reference; same pictures, slightly larger streams).  scenecut (percent,
-    0 = off; 150 is the recommended value) / min_keyint: adaptive I frames at scene cuts found on the device
-    (pipeline.SequenceEncoder, analysis.FrameAnalyzer); the log then carries one extra key, scene_cuts - the frames coded
-    as I frames because of a cut - and intra_period / reset_interval count from the most recent I frame.  target_bpp (None =
-    off: the fixed qp of the reference's RD sweep): target-bitrate control (ratecontrol.RateController fed by the device's
-    size estimate); qp_i / qp_p are then the starting qp and the log carries target_bpp, rc_qp (the mean qp of the packets)
-    and rc_est_bpp (the mean of what the controller was fed, to hold against ave_all_frame_bpp) - with verbose_json also
-    the per-frame lists frame_rc_qp and frame_rc_est_bpp.  digest: the encoder writes a digest unit in front of every frame
-    (docs/state_digest.md: this project's extension, NOT readable by the reference; 9 bytes per frame, counted in the bits)
-    and the decode loop checks its own reference state against it - a difference raises _lib.DigestMismatch; the log then
-    carries one extra key, digests_checked.  coded_size = (height, width), at most the source's size and at least 16 x 16 (None
-    or the source's size: off): reduced-resolution coding (docs/reduced_resolution.md: this project's extension, NOT readable
-    by the reference) - every frame is resampled down to that size on the device (resize.Resampler, scale_filter: bilinear,
-    bicubic or lanczos3) before the encoder sees it, the stream's SPS carries the coded size and a display unit the source's
-    size and the filter, and the decode loop resamples every decoded frame up to what the display unit says before metrics
-    and rec_path, which stay those of the source; bpp and target_bpp stay per SOURCE pixel.  The log then ends in coded_height,
-    coded_width and scale_filter.  film_grain (None = off): film-grain synthesis (docs/film_grain.md: this project's extension,
-    NOT readable by the reference) - a grain.GrainParams, written as a grain unit in front of every I frame, or "auto": at every
-    I frame the grain the codec removed is estimated on the device (grain.FilmGrain.estimate of the source frame against the I
-    frame's reconstruction - with coded_size the reconstruction resampled up against the full-size source, so grain is measured
-    at the size it is applied at; the unit's seed is the frame's index) and written if there is any.  The decode loop needs
-    no switch: while the stream's grain unit is in force, the picture behind the display upscale goes through
-    grain.FilmGrain.apply inside the timed region.  Metrics are taken from the picture BEFORE synthesis - they do not depend
-    on the switch - and rec_path gets the picture after it.  A unit's 14 bytes count in its frame's bits.  The log then ends
-    in grain_units, grain_scale_y (the last unit's eight values) and grain_corr."""
-    if metrics not in ("host", "device"):
-        raise ValueError(f"metrics {metrics!r}: 'host' or 'device'")
-    if entropy not in ("host", "device"):
-        raise ValueError(f"entropy {entropy!r}: 'host' or 'device'")
-    if src_type not in SRC_TYPES:
-        raise ValueError(f"src_type {src_type!r}: one of {', '.join(SRC_TYPES)}")
-    from .resize import FILTERS, Resampler, check_coded_size
-    if scale_filter not in FILTERS:
-        raise ValueError(f"scale_filter {scale_filter!r}: one of {', '.join(FILTERS)}")
-    coded_size = check_coded_size(coded_size, height, width)
-    from .grain import FilmGrain, GrainParams
-    if not (film_grain is None or film_grain == "auto" or isinstance(film_grain, GrainParams)):
-        raise ValueError(f"film_grain {film_grain!r}: None, 'auto' or a GrainParams")
-    ch, cw = coded_size or (height, width)          # what the SPS and the models see
-    png = src_type == "png"
+# ---------------------------------------------------------------------------------- the three source families
+class _Source:
+    """One source family as run_one_point needs it, put together by make_source: reader(), to_input(planes, dtype) -> the padded
+    model input, distortion(x_hat, planes, calc_ssim, dm) -> (psnr, ssim) of one frame as summarize() takes them (dm: a
+    metrics.DeviceMetrics, None: the host path) and the reconstruction writer - open_rec / write_rec / close_rec put the
+    planes of stored_planes(shown) into one raw file."""
+    rec = None
+
+    def __init__(self, width, height, make_reader, to_input, distortion, stored_planes=None):
+        self.w, self.h, self.make_reader, self.to_input = width, height, make_reader, to_input
+        self.distortion, self.stored_planes = distortion, stored_planes
+
+    def reader(self):
+        self.last_reader = self.make_reader()
+        return self.last_reader
+
+    def open_rec(self, rec_path):
+        self.rec = open(rec_path, "wb") if rec_path else None
+
+    def write_rec(self, shown, fi):
+        if self.rec is not None:
+            for plane in self.stored_planes(shown):
+                self.rec.write(plane.cpu().numpy().tobytes())
+
+    def close_rec(self):
+        if self.rec is not None:
+            self.rec.close()
+
+
+class _PNGSource(_Source):      # the reconstruction: PNGs named like the source's, clamp * 255 rounded to uint8 (test_video.py:314-318)
+    def open_rec(self, rec_path):
+        self.rec_dir = rec_path
+        if rec_path:
+            os.makedirs(rec_path, exist_ok=True)
+
+    def write_rec(self, shown, fi):
+        if self.rec_dir:
+            import torch
+            from PIL import Image
+            rgb8 = reconstruct_rgb(shown, self.h, self.w).float().round().to(torch.uint8).cpu().numpy()
+            name = "im%s.png" % str(fi + 1).zfill(self.last_reader.digits)
+            Image.fromarray(rgb8.transpose(1, 2, 0)).save(os.path.join(self.rec_dir, name))
+
+
+def make_source(src_type, path, width, height):
+    """the source object of a src_type (SRC_TYPES); touches no file.  The host metrics are looked up in this module when
+    they are called."""
     fmt = PIXEL_FORMATS.get(src_type)          # None: the reference harness's own two source types
     if fmt is not None:
         fmt.plane_shapes(height, width)        # (4:2:0 with an odd size is refused here)
-        make_reader = lambda: RawVideoReader(src_path, width, height, fmt)
-        to_input = lambda planes, dt: load_frame(planes, fmt, dt)
-    elif png:
-        make_reader = lambda: PNGSequenceReader(src_path, width, height)
-        to_input = lambda planes, dt: load_rgb_frame(planes[0], dt)
-    else:
-        make_reader = lambda: YUV420FileReader(src_path, width, height)
-        to_input = lambda planes, dt: load_yuv420_frame(*planes, dt)
+        return _Source(width, height, lambda: RawVideoReader(path, width, height, fmt), lambda p, dt: load_frame(p, fmt, dt),
+                       lambda x, p, ssim, dm: dm.yuv(x, p, fmt, ssim) if dm else pixfmt_distortion(x, p, fmt, ssim),
+                       lambda shown: store_frame(shown, height, width, fmt))          # the source's own format
+    if src_type == "png":
+        # (the PNG reader's planes are a transposed view: the kernels read them planar, as load_rgb_frame does)
+        return _PNGSource(width, height, lambda: PNGSequenceReader(path, width, height), lambda p, dt: load_rgb_frame(p[0], dt),
+                          lambda x, p, ssim, dm: dm.rgb(x, p[0].contiguous(), ssim) if dm else rgb_distortion(x, p[0], ssim))
+    # planar 8-bit 4:2:0, the reference's arithmetic: stored with Y rounded and chroma truncated (test_video.py:307-311)
+    def distortion(x, p, ssim, dm):
+        if dm:
+            return dm.yuv420(x, *p, ssim)
+        return yuv420_distortion(x, *p), (yuv420_msssim(x, *p) if ssim else [0.0, 0.0, 0.0, 0.0])
+    return _Source(width, height, lambda: YUV420FileReader(path, width, height), lambda p, dt: load_yuv420_frame(*p, dt),
+                   distortion, lambda shown: store_yuv420_frame(shown, height, width))
+
+
+# ---------------------------------------------------------------------------------- one rate point
+def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw):
+    """every frame of `src` through a SequenceEncoder(**enc_kw) into the container; coded: None or the (height, width) the
+    frames are resampled down to first; grain: None, a GrainParams, or "auto" (estimated at every I frame from the full-size
+    input against the reconstruction at that size, the unit's seed the frame's index).  The clock of a frame spans loader,
+    down-resample, encode and write_frame; the file read and the copy to the device stay outside.
+    -> (encoder, stream bytes, frame types, bits, times, the Resampler and the FilmGrain made here or None)"""
     import torch
-    dev = torch.device(device)
-    dtype = next(p_net.parameters()).dtype
-    two = use_two_entropy_coders(ch, cw)
-    scaler = Resampler(dev) if coded_size else None
-    for m in (i_net, p_net):
-        m.set_use_two_entropy_coders(two)
-        m.entropy = entropy
-    t_start = time.time()
-    reader = make_reader()
-    adaptive = dict(scenecut=scenecut, min_keyint=min_keyint) if scenecut else {}
-    if target_bpp:
-        from .ratecontrol import RateController
-        adaptive["rate"] = RateController(float(target_bpp) * height * width, qp_i if qp_p is None else qp_p, qp_i_init=qp_i)
-    else:
-        i_net.rate_estimate = p_net.rate_estimate = False       # (one pair codes every point)
-    if digest:
-        adaptive["digest"] = True
-    grainer = FilmGrain(dev) if film_grain is not None else None
-    source = []                                      # "auto": the full-size input of the frame being coded
-    if film_grain == "auto":
-        def estimate_grain(x_coded, x_hat):
+    from .grain import FilmGrain
+    from .resize import Resampler
+    size = (src.h, src.w)
+    ch, cw = coded or size
+    dtype = next(nets[1].parameters()).dtype
+    scaler = Resampler(dev) if coded else None
+    reader = src.reader()
+    grainer = FilmGrain(dev) if grain is not None else None
+    source, frame_types, bits, times = [], [], [], []
+    if grain is not None:
+        def estimate(x_coded, x_hat):
             if scaler:
-                x_hat = scaler.resample(x_hat, (ch, cw), (height, width), scale_filter)
-            return grainer.estimate(source[0], x_hat, (height, width), len(frame_types))
-        adaptive["grain"] = estimate_grain
-    elif film_grain is not None:
-        adaptive["grain"] = film_grain
-    enc = SequenceEncoder(i_net, p_net, qp_i, qp_p, intra_period, reset_interval, **adaptive)
+                x_hat = scaler.resample(x_hat, (ch, cw), size, scale_filter)
+            return grainer.estimate(source[0], x_hat, size, len(frame_types))
+        enc_kw = dict(enc_kw, grain=estimate if grain == "auto" else grain)
+    enc = SequenceEncoder(*nets, **enc_kw)
     out = io.BytesIO()
-    writer = StreamWriter(out, display=(height, width, scale_filter) if coded_size else None)
-    frame_types, bits, enc_time, dec_time, psnrs, ssims = [], [], [], [], [], []
+    writer = StreamWriter(out, display=size + (scale_filter,) if coded else None)
+    two = use_two_entropy_coders(ch, cw)
     for _ in range(frame_num):
         planes = _to_device(reader.read(), dev)
         torch.cuda.synchronize(dev)
         t0 = time.time()
-        x = to_input(planes, dtype)
-        source[:] = [x]
+        x = src.to_input(planes, dtype)
+        source[:] = [x]                                  # "auto": the full-size input of the frame being coded
         if scaler:
-            x = scaler.resample(x, (height, width), (ch, cw), scale_filter)
+            x = scaler.resample(x, size, (ch, cw), scale_filter)
         pkt = enc.encode(x)
         bits.append(8 * writer.write_frame(ch, cw, two, pkt))
         torch.cuda.synchronize(dev)
-        enc_time.append(time.time() - t0)
+        times.append(time.time() - t0)
         frame_types.append(0 if pkt.is_i else 1)
     reader.close()
-    stream = out.getvalue()
-    if bin_path:
-        with open(bin_path, "wb") as f:
-            f.write(stream)
+    return enc, out.getvalue(), frame_types, bits, times, scaler, grainer
 
-    reader = make_reader()
-    stream_reader = StreamReader(io.BytesIO(stream))
-    rec = None
-    if rec_path and png:
-        os.makedirs(rec_path, exist_ok=True)
-    elif rec_path:
-        rec = open(rec_path, "wb")
-    from .pipeline import FramePacket
-    dec = SequenceDecoder(i_net, p_net, ch, cw, two)
+
+def _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, device_metrics, rec_path, scaler, grainer):
+    """the container back through a StreamDecoder, frame by frame against the source: metrics of the decoded picture,
+    rec_path gets the shown one.  The clock of a frame spans the container read, the decoder's work, the synchronisation and
+    the digest check.  -> (decoder, times, psnrs, ssims)"""
+    import torch
+    reader = src.reader()
+    decoder = StreamDecoder(io.BytesIO(stream), *nets, dev, scaler=scaler, grainer=grainer)
+    src.open_rec(rec_path)
     dm = None
-    if metrics == "device":
+    if device_metrics:
         from .metrics import DeviceMetrics
         dm = DeviceMetrics(dev)
+    times, psnrs, ssims = [], [], []
     for fi in range(frame_num):
         planes = _to_device(reader.read(), dev)
         torch.cuda.synchronize(dev)
         t0 = time.time()
-        sps, is_i, qp, payload = stream_reader.read_frame()
-        dec.h, dec.w, dec.two = sps["height"], sps["width"], bool(sps["ec_part"])
-        x_hat = dec.decode(FramePacket(is_i, qp, sps["use_ada_i"], payload, chunked=stream_reader.chunked,
-                                       digest=stream_reader.digest))
-        if stream_reader.display is not None:       # the stream's word, not the arguments'
-            dh, dw, dfilter = stream_reader.display
-            if (dh, dw) != (height, width):
-                raise ValueError(f"the stream's display size {dw}x{dh} is not the source's {width}x{height}")
-            scaler = scaler or Resampler(dev)
-            x_hat = scaler.resample(x_hat, (sps["height"], sps["width"]), (dh, dw), dfilter)
-        shown = x_hat                               # what rec_path gets; the metrics below are x_hat's
-        if stream_reader.grain is not None:
-            grainer = grainer or FilmGrain(dev)
-            shown = grainer.apply(x_hat, (height, width), stream_reader.grain, stream_reader.grain_t)
+        frame = decoder.next()
+        if frame.display is not None and frame.display[:2] != (src.h, src.w):       # the stream's word, not the arguments'
+            raise ValueError(f"the stream's display size {frame.display[1]}x{frame.display[0]} is not the source's {src.w}x{src.h}")
         torch.cuda.synchronize(dev)
-        dec.check_digests()
-        dec_time.append(time.time() - t0)
-        if png:
-            # (the PNG reader's planes are a transposed view: the kernels read them planar, as load_rgb_frame does)
-            p_, s_ = dm.rgb(x_hat, planes[0].contiguous(), calc_ssim) if dm else rgb_distortion(x_hat, planes[0], calc_ssim)
-            psnrs.append(p_)
-            ssims.append(s_)
-            if rec_path:        # clamp * 255 rounded to uint8 (test_video.py:314-318), names like the source's
-                from PIL import Image
-                rgb8 = reconstruct_rgb(shown, height, width).float().round().to(torch.uint8).cpu().numpy()
-                Image.fromarray(rgb8.transpose(1, 2, 0)).save(os.path.join(rec_path, "im%s.png" % str(fi + 1).zfill(reader.digits)))
-            continue
-        if fmt is not None:
-            p_, s_ = dm.yuv(x_hat, planes, fmt, calc_ssim) if dm else pixfmt_distortion(x_hat, planes, fmt, calc_ssim)
-            psnrs.append(p_)
-            ssims.append(s_)
-            if rec is not None:     # the source's own format (pipeline.store_frame)
-                for plane in store_frame(shown, height, width, fmt):
-                    rec.write(plane.cpu().numpy().tobytes())
-            continue
-        y, u, v = planes
-        if dm:
-            p_, s_ = dm.yuv420(x_hat, y, u, v, calc_ssim)
-            psnrs.append(p_)
-            ssims.append(s_)
-        else:
-            psnrs.append(yuv420_distortion(x_hat, y, u, v))
-            ssims.append(yuv420_msssim(x_hat, y, u, v) if calc_ssim else [0.0, 0.0, 0.0, 0.0])
-        if rec is not None:     # clamp * 255, Y rounded, chroma truncated (test_video.py:307-311)
-            for plane in store_yuv420_frame(shown, height, width):
-                rec.write(plane.cpu().numpy().tobytes())
+        decoder.check_digests()
+        times.append(time.time() - t0)
+        psnr, ssim = src.distortion(frame.x_hat, planes, calc_ssim, dm)
+        psnrs.append(psnr)
+        ssims.append(ssim)
+        src.write_rec(frame.shown, fi)
     reader.close()
-    if rec is not None:
-        rec.close()
+    src.close_rec()
+    return decoder, times, psnrs, ssims
+
+
+def _rate_log(enc, target, frame_num, frame_pixel_num, per_frame):
+    """rate control's part of a point's log: rc_est_bpp is the mean of what the controller was fed, to hold against ave_all_frame_bpp"""
+    log = {"target_bpp": target, "rc_qp": float(np.mean(enc.rc_qp)),
+           "rc_est_bpp": float(8 * np.sum(enc.rc_est_bytes) / (frame_num * frame_pixel_num))}
+    if per_frame:
+        log["frame_rc_qp"] = [int(q) for q in enc.rc_qp]
+        log["frame_rc_est_bpp"] = [8 * b / frame_pixel_num for b in enc.rc_est_bytes]
+    return log
+
+
+def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=None, intra_period=-1,
+                  reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
+                  src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
+                  target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3", film_grain=None):
+    """Encodes `frame_num` frames of a source (src_type: SRC_TYPES - a planar 8-bit YUV 4:2:0 file, a directory of PNGs, a raw
+    file in a pipeline.PIXEL_FORMATS format) into the reference's container (optionally written to bin_path), decodes the
+    container again and returns the reference-schema log (summarize) plus one group of keys per extension switched on.
+    i_net / p_net: DMCI / DMC ready to code on `device`.  rec_path: the decoded sequence in the source's format / as PNGs in
+    that directory.  Every argument error is raised before a net, a file or the device is touched.
+      verbose >= 1                 avg_frame_encoding_time / avg_frame_decoding_time over the frames behind the first ten
+      verbose_json, calc_ssim      summarize: per-frame lists; MS-SSIM instead of zeros (slow on the host)
+      metrics, entropy             "host" | "device": torch glue + numpy / scipy or metrics.DeviceMetrics; docs/chunked_stream.md
+      scenecut, min_keyint         pipeline.SequenceEncoder (scenecut)        log: scene_cuts
+      target_bpp                   pipeline.SequenceEncoder (rate)            log: target_bpp, rc_qp, rc_est_bpp [, frame_rc_*]
+      digest                       docs/state_digest.md                       log: digests_checked
+      coded_size, scale_filter     docs/reduced_resolution.md                 log: coded_height, coded_width, scale_filter
+      film_grain                   docs/film_grain.md (None, "auto", a GrainParams)   log: grain_units, grain_scale_y, grain_corr"""
+    from .grain import GrainParams
+    from .resize import FILTERS, check_coded_size
+    for name, value, choices in (("metrics", metrics, ("host", "device")), ("entropy", entropy, ("host", "device")),
+                                 ("src_type", src_type, SRC_TYPES), ("scale_filter", scale_filter, FILTERS)):
+        if value not in choices:
+            raise ValueError(f"{name} {value!r}: one of {', '.join(choices)}")
+    coded_size = check_coded_size(coded_size, height, width)
+    if not (film_grain is None or film_grain == "auto" or isinstance(film_grain, GrainParams)):
+        raise ValueError(f"film_grain {film_grain!r}: None, 'auto' or a GrainParams")
+    src = make_source(src_type, src_path, width, height)
+    import torch
+    dev, nets = torch.device(device), (i_net, p_net)
+    for m in nets:
+        m.set_use_two_entropy_coders(use_two_entropy_coders(*(coded_size or (height, width))))     # what the SPS and the models see
+        m.entropy = entropy
+    t_start = time.time()
+    enc_kw = dict(qp_i=qp_i, qp_p=qp_p, intra_period=intra_period, reset_interval=reset_interval)
+    if scenecut:
+        enc_kw.update(scenecut=scenecut, min_keyint=min_keyint)
+    if target_bpp:
+        from .ratecontrol import RateController
+        enc_kw["rate"] = RateController(float(target_bpp) * height * width, qp_i if qp_p is None else qp_p, qp_i_init=qp_i)
+    else:
+        i_net.rate_estimate = p_net.rate_estimate = False       # (one pair codes every point)
+    if digest:
+        enc_kw["digest"] = True
+    enc, stream, frame_types, bits, enc_time, scaler, grainer = _encode_pass(nets, src, frame_num, dev, coded_size, scale_filter,
+                                                                             film_grain, enc_kw)
+    if bin_path:
+        with open(bin_path, "wb") as f:
+            f.write(stream)
+    decoder, dec_time, psnrs, ssims = _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, metrics == "device", rec_path,
+                                                   scaler, grainer)
     test_time = time.time() - t_start
-    avg_e = avg_d = None
-    if verbose >= 1 and frame_num > 10:     # the first 10 frames are warm-up (test_video.py:328-333)
-        avg_e = sum(enc_time[10:]) / len(enc_time[10:])
-        avg_d = sum(dec_time[10:]) / len(dec_time[10:])
+    timed = verbose >= 1 and frame_num > 10     # the first 10 frames are warm-up (test_video.py:328-333)
     log = summarize(height * width, test_time, frame_types, bits, psnrs, ssims, verbose=verbose_json,
-                    avg_encoding_time=avg_e, avg_decoding_time=avg_d)
+                    avg_encoding_time=sum(enc_time[10:]) / len(enc_time[10:]) if timed else None,
+                    avg_decoding_time=sum(dec_time[10:]) / len(dec_time[10:]) if timed else None)
     if scenecut:
         log["scene_cuts"] = list(enc.scene_cuts)
     if target_bpp:
-        log["target_bpp"] = float(target_bpp)
-        log["rc_qp"] = float(np.mean(enc.rc_qp))
-        log["rc_est_bpp"] = float(8 * np.sum(enc.rc_est_bytes) / (frame_num * height * width))
-        if verbose_json:
-            log["frame_rc_qp"] = [int(q) for q in enc.rc_qp]
-            log["frame_rc_est_bpp"] = [8 * b / (height * width) for b in enc.rc_est_bytes]
+        log.update(_rate_log(enc, float(target_bpp), frame_num, height * width, verbose_json))
     if digest:
-        log["digests_checked"] = dec.digests_checked
+        log["digests_checked"] = decoder.digests_checked
     if coded_size:
-        log["coded_height"], log["coded_width"], log["scale_filter"] = ch, cw, scale_filter
+        log["coded_height"], log["coded_width"], log["scale_filter"] = *coded_size, scale_filter
     if film_grain is not None:
         last = enc.grain_units[-1] if enc.grain_units else None
-        log["grain_units"] = len(enc.grain_units)
-        log["grain_scale_y"] = list(last.scale_y) if last else []
-        log["grain_corr"] = last.corr if last else 0
+        log.update(grain_units=len(enc.grain_units), grain_scale_y=list(last.scale_y) if last else [],
+                   grain_corr=last.corr if last else 0)
     return log
+
+
+# The per-point options: (run_one_point keyword, default, normaliser of a value that is set or None).  run_job, main and
+# manifest_options all go through point_kwargs, so a new option is one row here, one build_parser line under the same name and
+# its hook in run_one_point (DESIGN.md).  target_bpp is not one of them: it is worked out per sequence (target_bpp()).
+POINT_OPTIONS = (("verbose", 0, None), ("verbose_json", False, bool), ("calc_ssim", False, bool), ("metrics", "host", None),
+                 ("entropy", "host", None), ("scenecut", 0, None), ("min_keyint", 4, None), ("digest", False, bool),
+                 ("coded_size", None, None), ("scale_filter", "lanczos3", None), ("film_grain", None, None))
+
+
+def point_kwargs(opts):
+    """an options mapping (a manifest run's opts, vars() of the parsed command line) -> run_one_point's keywords of
+    POINT_OPTIONS; an option that is missing, None or otherwise false takes its default"""
+    return {name: (norm or (lambda v: v))(opts.get(name) or default) for name, default, norm in POINT_OPTIONS}
 
 
 def run_sweep(make_nets, src_path, width, height, frame_num, rate_num=4, qp_i=None, qp_p=None, bin_prefix=None, **kw):
@@ -700,15 +726,14 @@ def _init_worker(opts, gpu_num):
     _WORKER["opts"] = opts
 
 
-def default_nets(opts):
-    """(DMCI, DMC) ready to code: checkpoints if given (reference keys), else the synthetic weights; on cuda:0 of the
-    worker (its HIP_VISIBLE_DEVICES names one GPU); fp16 like the reference harness unless opts['fp32']."""
+def load_nets(model_i, model_p, force_zero_thres, fp32, device):
+    """(DMCI, DMC) ready to code on `device`: checkpoints if given (reference keys, a DataParallel "module." prefix dropped),
+    else the synthetic weights; fp16 like the reference harness unless fp32."""
     import torch
     from . import weights
     from .models import DMC, DMCI
-    torch.set_num_threads(1)          # src/utils/common.py:23
     nets = []
-    for cls, name, path in ((DMCI, "dmci", opts.get("model_i")), (DMC, "dmc", opts.get("model_p"))):
+    for cls, name, path in ((DMCI, "dmci", model_i), (DMC, "dmc", model_p)):
         m = cls()
         if path:
             ck = torch.load(path, map_location="cpu", weights_only=True)
@@ -718,12 +743,19 @@ def default_nets(opts):
         else:
             m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in
                                weights.make_state_dict(name, 1234).items()})
-        m.to("cuda:0").eval()
-        m.update(opts.get("force_zero_thres", 0.12))
-        if not opts.get("fp32"):
+        m.to(device).eval()
+        m.update(force_zero_thres)
+        if not fp32:
             m.half()
         nets.append(m)
     return nets
+
+
+def default_nets(opts):
+    """load_nets of a worker's options, on cuda:0 of the worker (its HIP_VISIBLE_DEVICES names one GPU)"""
+    import torch
+    torch.set_num_threads(1)          # src/utils/common.py:23
+    return load_nets(opts.get("model_i"), opts.get("model_p"), opts.get("force_zero_thres", 0.12), opts.get("fp32"), "cuda:0")
 
 
 def run_job(nets, job, opts):
@@ -748,13 +780,8 @@ def run_job(nets, job, opts):
             print(f"incorrect log for {json_path}, try to rerun.")
     log = run_one_point(nets[0], nets[1], job["src_path"], job["src_width"], job["src_height"], job["frame_num"],
                         job["qp_i"], job["qp_p"], intra_period=job["intra_period"], reset_interval=job["reset_interval"],
-                        bin_path=bin_path, rec_path=rec_path, verbose=opts.get("verbose", 0),
-                        verbose_json=opts.get("verbose_json", False), device="cuda:0", src_type=job.get("src_type", "yuv420"),
-                        calc_ssim=bool(opts.get("calc_ssim")), metrics=opts.get("metrics") or "host",
-                        entropy=opts.get("entropy") or "host", scenecut=opts.get("scenecut") or 0,
-                        min_keyint=opts.get("min_keyint") or 4, target_bpp=target_bpp(opts, job["src_width"], job["src_height"]),
-                        digest=bool(opts.get("digest")), coded_size=opts.get("coded_size"),
-                        scale_filter=opts.get("scale_filter") or "lanczos3", film_grain=opts.get("film_grain") or None)
+                        bin_path=bin_path, rec_path=rec_path, device="cuda:0", src_type=job.get("src_type", "yuv420"),
+                        target_bpp=target_bpp(opts, job["src_width"], job["src_height"]), **point_kwargs(opts))
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -820,10 +847,34 @@ def _str2bool(v):
     raise ValueError("boolean value expected, got %r" % (v,))
 
 
-def _coded_size(text):
-    """--coded-size WxH -> (height, width); argparse turns the ValueError of a malformed size into a usage error"""
-    from .resize import parse_size
-    return parse_size(text)
+def _add_extension_options(ap, flag):
+    """this project's options beyond the reference's: adaptive I frames, rate control, digests, reduced resolution, film grain"""
+    from .resize import FILTERS, parse_size
+    ap.add_argument("--scenecut", type=int, default=0, metavar="PCT",
+                    help="adaptive I frames: a frame whose low-resolution difference to its predecessor is at least PCT percent "
+                         "of its own spatial activity starts a new GOP (0 = off, the reference's placement; 150 is recommended); "
+                         "--intra-period and --reset-interval then count from the most recent I frame")
+    ap.add_argument("--min-keyint", "--min_keyint", type=int, default=4, metavar="N",
+                    help="with --scenecut: a cut fewer than N frames after the last I frame is coded as a P frame")
+    ap.add_argument("--target-bpp", "--target_bpp", type=float, default=None, metavar="X",
+                    help="target-bitrate control: aim at X bits per pixel (one rate point; --qp-i / --qp-p give the starting qp)")
+    ap.add_argument("--target-kbps", "--target_kbps", type=float, default=None, metavar="K",
+                    help="the same as a bitrate: K * 1000 / (--fps * width * height) bits per pixel, per sequence")
+    ap.add_argument("--fps", type=float, default=None, metavar="F", help="frame rate of the source, for --target-kbps")
+    ap.add_argument("--digest", **flag,
+                    help="write a digest of the decoder's reference state in front of every frame and check it while decoding "
+                         "(docs/state_digest.md) - this project's extension, not readable by the reference")
+    ap.add_argument("--coded-size", "--coded_size", type=parse_size, default=None, metavar="WxH",      # (a malformed size: a usage error)
+                    help="reduced-resolution coding: resample every frame down to W x H on the device, code that, and resample "
+                         "the decoded frames back up; metrics, bpp and --target-bpp stay those of the source "
+                         "(docs/reduced_resolution.md) - this project's extension, not readable by the reference")
+    ap.add_argument("--scale-filter", "--scale_filter", choices=FILTERS, default="lanczos3",
+                    help="the resampling filter of --coded-size, down and up")
+    ap.add_argument("--film-grain", "--film_grain", nargs="?", const="auto", default=None,
+                    type=lambda v: "auto" if v == "auto" or _str2bool(v) else None,
+                    help="film-grain synthesis: at every I frame the grain the codec removed is estimated on the device and "
+                         "written as a 14-byte grain unit; the decode loop puts it back on the pictures it stores, not on "
+                         "the ones it measures (docs/film_grain.md) - this project's extension, not readable by the reference")
 
 
 def build_parser():
@@ -873,30 +924,7 @@ def build_parser():
     ap.add_argument("--qp-p", "--qp_p", type=int, nargs="*")
     ap.add_argument("--intra-period", type=int, default=-1)
     ap.add_argument("--reset-interval", "--reset_interval", type=int, default=32)
-    ap.add_argument("--scenecut", type=int, default=0, metavar="PCT",
-                    help="adaptive I frames: a frame whose low-resolution difference to its predecessor is at least PCT percent "
-                         "of its own spatial activity starts a new GOP (0 = off, the reference's placement; 150 is recommended); "
-                         "--intra-period and --reset-interval then count from the most recent I frame")
-    ap.add_argument("--min-keyint", "--min_keyint", type=int, default=4, metavar="N",
-                    help="with --scenecut: a cut fewer than N frames after the last I frame is coded as a P frame")
-    ap.add_argument("--target-bpp", "--target_bpp", type=float, default=None, metavar="X",
-                    help="target-bitrate control: aim at X bits per pixel (one rate point; --qp-i / --qp-p give the starting qp)")
-    ap.add_argument("--target-kbps", "--target_kbps", type=float, default=None, metavar="K",
-                    help="the same as a bitrate: K * 1000 / (--fps * width * height) bits per pixel, per sequence")
-    ap.add_argument("--fps", type=float, default=None, metavar="F", help="frame rate of the source, for --target-kbps")
-    ap.add_argument("--digest", **flag,
-                    help="write a digest of the decoder's reference state in front of every frame and check it while decoding "
-                         "(docs/state_digest.md) - this project's extension, not readable by the reference")
-    ap.add_argument("--coded-size", "--coded_size", type=_coded_size, default=None, metavar="WxH",
-                    help="reduced-resolution coding: resample every frame down to W x H on the device, code that, and resample "
-                         "the decoded frames back up; metrics, bpp and --target-bpp stay those of the source "
-                         "(docs/reduced_resolution.md) - this project's extension, not readable by the reference")
-    ap.add_argument("--scale-filter", "--scale_filter", choices=("bilinear", "bicubic", "lanczos3"), default="lanczos3",
-                    help="the resampling filter of --coded-size, down and up")
-    ap.add_argument("--film-grain", "--film_grain", **flag,
-                    help="film-grain synthesis: at every I frame the grain the codec removed is estimated on the device and "
-                         "written as a 14-byte grain unit; the decode loop puts it back on the pictures it stores, not on "
-                         "the ones it measures (docs/film_grain.md) - this project's extension, not readable by the reference")
+    _add_extension_options(ap, flag)
     ap.add_argument("--model-i", "--model_path_i", help="DMCI checkpoint (.pth.tar); synthetic weights if omitted")
     ap.add_argument("--model-p", "--model_path_p", help="DMC checkpoint")
     ap.add_argument("--force-zero-thres", "--force_zero_thres", type=float, default=0.12)
@@ -917,21 +945,14 @@ def manifest_options(args, ap):
     if gpu_ids and gpus > len(gpu_ids):
         ap.error("--gpus %d but only %d device ids are given / visible (%s)" % (gpus, len(gpu_ids), ",".join(gpu_ids)))
     stream_path = args.stream_path or ("out_bin" if args.write_stream else None)      # (the reference's default folder)
-    opts = dict(gpu_ids=gpu_ids, rate_num=args.rate_num, qp_i=args.qp_i, qp_p=args.qp_p, force_root_path=args.force_root_path,
-                force_frame_num=args.force_frame_num, force_intra_period=args.force_intra_period,
-                reset_interval=args.reset_interval, model_i=args.model_i, model_p=args.model_p,
-                force_zero_thres=args.force_zero_thres, fp32=args.fp32, stream_path=stream_path,
-                verbose=args.verbose, verbose_json=args.verbose_json, calc_ssim=args.calc_ssim, metrics=args.metrics,
-                entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint, target_bpp=args.target_bpp,
-                target_kbps=args.target_kbps, fps=args.fps, digest=args.digest, coded_size=args.coded_size,
-                scale_filter=args.scale_filter, film_grain="auto" if args.film_grain else None, force_intra=args.force_intra, check_existing=args.check_existing, save_decoded_frame=args.save_decoded_frame)
+    opts = {k: getattr(args, k) for k in ("rate_num", "qp_i", "qp_p", "force_root_path", "force_frame_num", "force_intra_period",
+                                          "reset_interval", "model_i", "model_p", "force_zero_thres", "fp32", "target_bpp",
+                                          "target_kbps", "fps", "force_intra", "check_existing", "save_decoded_frame")}
+    opts.update(gpu_ids=gpu_ids, stream_path=stream_path, **point_kwargs(vars(args)))
     return opts, gpus
 
 
 def main(argv=None):
-    import torch
-    from . import weights
-    from .models import DMC, DMCI
     ap = build_parser()
     args = ap.parse_args(argv)
     check_rate_options(args, ap)
@@ -955,33 +976,11 @@ def main(argv=None):
     if not (args.src and args.width and args.height and args.frames):
         ap.error("either --test-config or --src/--width/--height/--frames")
 
-    def make_nets():
-        nets = []
-        for cls, name, path in ((DMCI, "dmci", args.model_i), (DMC, "dmc", args.model_p)):
-            m = cls()
-            if path:
-                ck = torch.load(path, map_location="cpu", weights_only=True)
-                ck = ck.get("state_dict", ck)
-                ck = ck.get("net", ck)
-                m.load_state_dict({k[7:] if k.startswith("module.") else k: v for k, v in ck.items()})
-            else:
-                m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in
-                                   weights.make_state_dict(name, 1234).items()})
-            m.to("cuda").eval()
-            m.update(args.force_zero_thres)
-            if not args.fp32:
-                m.half()
-            nets.append(m)
-        return nets
-
-    res = run_sweep(make_nets, args.src, args.width, args.height, args.frames, args.rate_num,
-                    args.qp_i or None, args.qp_p or None, bin_prefix=args.bin_prefix,
-                    intra_period=args.intra_period, reset_interval=args.reset_interval, verbose=args.verbose,
-                    verbose_json=args.verbose_json, src_type=args.src_type, calc_ssim=args.calc_ssim, metrics=args.metrics,
-                    entropy=args.entropy, scenecut=args.scenecut, min_keyint=args.min_keyint,
-                    target_bpp=target_bpp(vars(args), args.width, args.height), digest=args.digest,
-                    coded_size=args.coded_size, scale_filter=args.scale_filter,
-                    film_grain="auto" if args.film_grain else None)
+    res = run_sweep(lambda: load_nets(args.model_i, args.model_p, args.force_zero_thres, args.fp32, "cuda"),
+                    args.src, args.width, args.height, args.frames, args.rate_num, args.qp_i or None, args.qp_p or None,
+                    bin_prefix=args.bin_prefix, intra_period=args.intra_period, reset_interval=args.reset_interval,
+                    src_type=args.src_type, target_bpp=target_bpp(vars(args), args.width, args.height),
+                    **point_kwargs(vars(args)))
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:

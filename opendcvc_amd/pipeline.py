@@ -307,6 +307,67 @@ class SequenceDecoder:
         return [] if last is None else [last]
 
 
+@dataclass
+class DecodedFrame:
+    x_hat: object                    # the decoded picture at the size it is displayed at: what metrics read
+    shown: object                    # x_hat with the film grain in force on it: what gets stored (x_hat itself without grain)
+    sps: dict
+    is_i: bool
+    display: Optional[tuple]         # StreamReader.display / grain / grain_t behind this frame
+    grain: Optional[object]
+    grain_t: int
+
+
+class StreamDecoder:
+    """Container in, pictures out: the decode-side entry point.  Owns the StreamReader of the binary file-like `f`, the
+    SequenceDecoder (sequential: defer_output=False; made at the first frame, from then on it follows every frame's SPS) and
+    what the stream's extension units ask for behind it - the display unit's resample (docs/reduced_resolution.md) and the
+    grain unit's synthesis (docs/film_grain.md).  scaler / grainer: a resize.Resampler / grain.FilmGrain to use; otherwise
+    each is made when the stream first needs one, so a stream without these units launches the decoder's own kernels only."""
+
+    def __init__(self, f, i_net, p_net, device, scaler=None, grainer=None):
+        from .bitstream import StreamReader
+        self.reader = StreamReader(f)
+        self.i_net, self.p_net, self.device = i_net, p_net, device
+        self.scaler, self.grainer = scaler, grainer
+        self.dec = None
+
+    def next(self):
+        """the next frame of the stream -> DecodedFrame; everything is enqueued on the current stream, nothing is waited for"""
+        rd = self.reader
+        sps, pkt = rd.read_packet()
+        size = (sps["height"], sps["width"])
+        if self.dec is None:
+            self.dec = SequenceDecoder(self.i_net, self.p_net, *size, bool(sps["ec_part"]))
+        self.dec.h, self.dec.w, self.dec.two = *size, bool(sps["ec_part"])
+        x_hat = self.dec.decode(pkt)
+        if rd.display is not None:
+            if self.scaler is None:
+                from .resize import Resampler
+                self.scaler = Resampler(self.device)
+            x_hat, size = self.scaler.resample(x_hat, size, rd.display[:2], rd.display[2]), rd.display[:2]
+        shown = x_hat
+        if rd.grain is not None:
+            if self.grainer is None:
+                from .grain import FilmGrain
+                self.grainer = FilmGrain(self.device)
+            shown = self.grainer.apply(x_hat, size, rd.grain, rd.grain_t)
+        return DecodedFrame(x_hat, shown, sps, pkt.is_i, rd.display, rd.grain, rd.grain_t)
+
+    def check_digests(self):
+        if self.dec is not None:
+            self.dec.check_digests()
+
+    @property
+    def digests_checked(self):
+        return self.dec.digests_checked if self.dec is not None else 0
+
+    def flush(self):
+        """at the end of a stream: reads the digests still unchecked"""
+        if self.dec is not None:
+            self.dec.flush()
+
+
 class EncodeDecodePipeline:
     """Encoder and decoder of one stream as a two-stage pipeline on one GPU: each stage has its own host
     thread and HIP stream, so frame n is decoded while frame n+1 is encoded and one stage's host entropy
