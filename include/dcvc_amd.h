@@ -508,6 +508,37 @@ int dcvc_grain_apply(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W
 int dcvc_grain_stats(int dtype, const void* noisy_nchw, const void* clean_nchw, int Hp, int Wp, int H, int W, int64_t* table,
                      void* stream);
 /* ------------------------------------------------------------------------------------------
+ * Motion-compensated temporal pre-filter of the encoder's input (csrc/dcvc_tf.hip; docs/temporal_filter.md is the normative
+ * text; no reference counterpart).  Frames are model frames [3][Hp][Wp] with the picture H x W at its top left; every sample
+ * fetch clamps its coordinates to the picture, the padding is never read.  Nothing is allocated and nothing waited for.
+ * Common argument errors (checked before any device work; nothing is launched and no output is touched): dtype; a size that
+ * is not positive, Hp < H, Wp < W; a NULL pointer; a pointer not aligned to its element.
+ *
+ * The integer pyramid of the luma plane: Q0 [H][W] | Q1 [ceil(H/2)][ceil(W/2)] | Q2 (the halves of Q1), uint16, rows
+ * contiguous, dcvc_tf_pyramid_bytes(H, W) bytes.  Q0 = dcvc_frame_analyze's 10-bit quantiser, Q(l+1) = (a + b + c + d + 2) >> 2
+ * over 2 x 2 with clamped source coordinates.  One launch. */
+int64_t dcvc_tf_pyramid_bytes(int H, int W);
+int dcvc_tf_pyramid(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, uint16_t* pyramid, void* stream);
+/* Block motion search of the current pyramid against nref (1 .. 4) reference pyramids, 8 x 8 blocks, level 2 (+-4 around 0),
+ * level 1 and level 0 (+-2 around twice the parent's vector), the winner the minimum of (SAD, |dy| + |dx|, dy, dx):
+ * mv [nref][gh][gw][2] int16 as (y, x), err [nref][gh][gw] uint32 (the level-0 SAD), gh = ceil(H/8), gw = ceil(W/8).
+ * ws: dcvc_tf_motion_ws_bytes(H, W) bytes of device memory (the coarser levels' vectors).  Three launches.
+ * Further argument errors: nref outside 1 .. 4; err not 4-byte aligned. */
+int64_t dcvc_tf_motion_ws_bytes(int H, int W);
+int dcvc_tf_motion(const uint16_t* cur_pyramid, const uint16_t* const* ref_pyramids, int nref, int H, int W, int16_t* mv,
+                   uint32_t* err, void* ws, void* stream);
+/* The weighted blend of the current frame with nref (0 .. 4) reference frames gathered at their blocks' vectors, for the
+ * three planes in one launch.  refs_nchw / dists: host arrays; dists[r] is +-1 or +-2 (base weight 102 or 77 of 256), the
+ * references are accumulated in the order given.  level 1 .. 5: T = 4 << level.  Per sample, fp32, multiply and add never
+ * fused:  acc = 256 c;  acc = acc + float(w_r) * r  per reference;  out = acc * rcp(256 + sum w_r), ONE rounding to the
+ * storage type, no clamp; where no reference has weight the bits of c.  Elements outside the picture: the replicate pad of
+ * the filtered picture.  weight_sum (device memory, 8-byte aligned): the sum over the luma samples of (Wsum - 256) is ADDED
+ * to it (integer vector atomics: independent of order); the caller zeroes it.
+ * Further argument errors: level outside 1 .. 5; nref above 4; a distance that is not +-1 / +-2; out overlapping the current
+ * frame or a reference (neighbours are read); mv, err or weight_sum misaligned. */
+int dcvc_tf_blend(int dtype, const void* cur_nchw, const void* const* refs_nchw, const int* dists, int nref, int Hp, int Wp, int H,
+                  int W, const int16_t* mv, const uint32_t* err, int level, void* out_nchw, uint64_t* weight_sum, void* stream);
+/* ------------------------------------------------------------------------------------------
  * Frame analysis for the encoder's scene-cut decision (csrc/dcvc_analysis.hip; no reference counterpart: the reference
  * harness places I frames by fi % intra_period only).  luma: H x W samples of the model input (DCVC_F16 / DCVC_F32), row
  * stride ld elements, read in place.  Per sample q = (int)fminf(fmaxf(rintf(v * 1023.0f), 0.0f), 1023.0f) (one fp32

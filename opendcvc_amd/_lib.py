@@ -159,6 +159,11 @@ _SIGS = {
     "dcvc_resize_frame": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "dcvc_grain_apply": (_I, [_I, _P, _I, _I, _I, _I, _P, GrainParamsC, c_uint32, _P]),
     "dcvc_grain_stats": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "dcvc_tf_pyramid_bytes": (_L, [_I, _I]),
+    "dcvc_tf_pyramid": (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
+    "dcvc_tf_motion_ws_bytes": (_L, [_I, _I]),
+    "dcvc_tf_motion": (_I, [_P, POINTER(_P), _I, _I, _I, _P, _P, _P, _P]),
+    "dcvc_tf_blend": (_I, [_I, _P, POINTER(_P), POINTER(_I), _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     "dcvc_frame_analysis_ws_bytes": (_L, [_I, _I]),
     "dcvc_frame_analyze": (_I, [_I, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
     "dcvc_rate_estimate_ws_bytes": (_L, [_I, _I, _I]),

@@ -413,12 +413,14 @@ def make_source(src_type, path, width, height):
 
 
 # ---------------------------------------------------------------------------------- one rate point
-def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw):
+def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, tf_level=0, tf_radius=2):
     """every frame of `src` through a SequenceEncoder(**enc_kw) into the container; coded: None or the (height, width) the
     frames are resampled down to first; grain: None, a GrainParams, or "auto" (estimated at every I frame from the full-size
-    input against the reconstruction at that size, the unit's seed the frame's index).  The clock of a frame spans loader,
-    down-resample, encode and write_frame; the file read and the copy to the device stay outside.
-    -> (encoder, stream bytes, frame types, bits, times, the Resampler and the FilmGrain made here or None)"""
+    input against the reconstruction at that size, the unit's seed the frame's index); tf_level > 0: the frames pass a
+    prefilter.TemporalFilter at source size first, which reads tf_radius frames ahead - "auto" is still given the UNFILTERED
+    input of the frame being coded.  The clock of a frame spans loader, temporal filter, down-resample, encode and
+    write_frame; the file read and the copy to the device stay outside.
+    -> (encoder, stream bytes, frame types, bits, times, the Resampler, the FilmGrain and the TemporalFilter made here or None)"""
     import torch
     from .grain import FilmGrain
     from .resize import Resampler
@@ -439,12 +441,10 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw):
     out = io.BytesIO()
     writer = StreamWriter(out, display=size + (scale_filter,) if coded else None)
     two = use_two_entropy_coders(ch, cw)
-    for _ in range(frame_num):
-        planes = _to_device(reader.read(), dev)
-        torch.cuda.synchronize(dev)
-        t0 = time.time()
-        x = src.to_input(planes, dtype)
-        source[:] = [x]                                  # "auto": the full-size input of the frame being coded
+
+    def code(x_source, x, t0):
+        """x (the frame as the encoder is to see it at source size) from the clock reading t0 on"""
+        source[:] = [x_source]                           # "auto": the full-size unfiltered input of the frame being coded
         if scaler:
             x = scaler.resample(x, size, (ch, cw), scale_filter)
         pkt = enc.encode(x)
@@ -452,8 +452,34 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw):
         torch.cuda.synchronize(dev)
         times.append(time.time() - t0)
         frame_types.append(0 if pkt.is_i else 1)
+
+    tf = None
+    if tf_level:
+        from .prefilter import TemporalFilter
+        tf = TemporalFilter(dev, tf_level, tf_radius)
+        waiting = []                                     # (unfiltered input, seconds on the clock so far) of the frames read ahead
+    for _ in range(frame_num):
+        planes = _to_device(reader.read(), dev)
+        torch.cuda.synchronize(dev)
+        t0 = time.time()
+        x = src.to_input(planes, dtype)
+        if tf is None:
+            code(x, x, t0)
+            continue
+        ready = tf.push(x, size)                         # frame t comes out when frame t + radius has gone in
+        torch.cuda.synchronize(dev)
+        waiting.append((x, time.time() - t0))
+        for y in ready:
+            x_source, spent = waiting.pop(0)
+            code(x_source, y, time.time() - spent)
+    if tf is not None:
+        t0 = time.time()
+        for y in tf.flush():                             # (the last frames' blends are enqueued here: on the first one's clock)
+            x_source, spent = waiting.pop(0)
+            code(x_source, y, t0 - spent)
+            t0 = time.time()
     reader.close()
-    return enc, out.getvalue(), frame_types, bits, times, scaler, grainer
+    return enc, out.getvalue(), frame_types, bits, times, scaler, grainer, tf
 
 
 def _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, device_metrics, rec_path, scaler, grainer):
@@ -501,7 +527,8 @@ def _rate_log(enc, target, frame_num, frame_pixel_num, per_frame):
 def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=None, intra_period=-1,
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
                   src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
-                  target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3", film_grain=None):
+                  target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3", film_grain=None,
+                  temporal_filter=0, tf_radius=2):
     """Encodes `frame_num` frames of a source (src_type: SRC_TYPES - a planar 8-bit YUV 4:2:0 file, a directory of PNGs, a raw
     file in a pipeline.PIXEL_FORMATS format) into the reference's container (optionally written to bin_path), decodes the
     container again and returns the reference-schema log (summarize) plus one group of keys per extension switched on.
@@ -514,8 +541,10 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
       target_bpp                   pipeline.SequenceEncoder (rate)            log: target_bpp, rc_qp, rc_est_bpp [, frame_rc_*]
       digest                       docs/state_digest.md                       log: digests_checked
       coded_size, scale_filter     docs/reduced_resolution.md                 log: coded_height, coded_width, scale_filter
-      film_grain                   docs/film_grain.md (None, "auto", a GrainParams)   log: grain_units, grain_scale_y, grain_corr"""
+      film_grain                   docs/film_grain.md (None, "auto", a GrainParams)   log: grain_units, grain_scale_y, grain_corr
+      temporal_filter, tf_radius   docs/temporal_filter.md (level 0 = off .. 5; 1, 2)  log: tf_level, tf_radius, tf_mean_weight"""
     from .grain import GrainParams
+    from .prefilter import check_options
     from .resize import FILTERS, check_coded_size
     for name, value, choices in (("metrics", metrics, ("host", "device")), ("entropy", entropy, ("host", "device")),
                                  ("src_type", src_type, SRC_TYPES), ("scale_filter", scale_filter, FILTERS)):
@@ -524,6 +553,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     coded_size = check_coded_size(coded_size, height, width)
     if not (film_grain is None or film_grain == "auto" or isinstance(film_grain, GrainParams)):
         raise ValueError(f"film_grain {film_grain!r}: None, 'auto' or a GrainParams")
+    temporal_filter, tf_radius = check_options(temporal_filter, tf_radius)
     src = make_source(src_type, src_path, width, height)
     import torch
     dev, nets = torch.device(device), (i_net, p_net)
@@ -541,8 +571,9 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         i_net.rate_estimate = p_net.rate_estimate = False       # (one pair codes every point)
     if digest:
         enc_kw["digest"] = True
-    enc, stream, frame_types, bits, enc_time, scaler, grainer = _encode_pass(nets, src, frame_num, dev, coded_size, scale_filter,
-                                                                             film_grain, enc_kw)
+    enc, stream, frame_types, bits, enc_time, scaler, grainer, tf = _encode_pass(nets, src, frame_num, dev, coded_size,
+                                                                                 scale_filter, film_grain, enc_kw,
+                                                                                 temporal_filter, tf_radius)
     if bin_path:
         with open(bin_path, "wb") as f:
             f.write(stream)
@@ -565,12 +596,17 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         last = enc.grain_units[-1] if enc.grain_units else None
         log.update(grain_units=len(enc.grain_units), grain_scale_y=list(last.scale_y) if last else [],
                    grain_corr=last.corr if last else 0)
+    if tf is not None:
+        log.update(tf_level=temporal_filter, tf_radius=tf_radius,
+                   tf_mean_weight=tf.weight_sum() / (256.0 * height * width * frame_num))
     return log
 
 
 # The per-point options: (run_one_point keyword, default, normaliser of a value that is set or None).  run_job, main and
 # manifest_options all go through point_kwargs, so a new option is one row here, one build_parser line under the same name and
-# its hook in run_one_point.  target_bpp is not one of them: it is worked out per sequence (target_bpp()).
+# its hook in run_one_point.  target_bpp is not one of them: it is worked out per sequence (target_bpp()).  Nor
+# are temporal_filter / tf_radius: they act in front of the encoder, not on a rate point, and the table's names are pinned
+# (tests/test_harness_options.py), so they travel target_bpp's way - prefilter_kwargs(), passed beside point_kwargs().
 POINT_OPTIONS = (("verbose", 0, None), ("verbose_json", False, bool), ("calc_ssim", False, bool), ("metrics", "host", None),
                  ("entropy", "host", None), ("scenecut", 0, None), ("min_keyint", 4, None), ("digest", False, bool),
                  ("coded_size", None, None), ("scale_filter", "lanczos3", None), ("film_grain", None, None))
@@ -580,6 +616,12 @@ def point_kwargs(opts):
     """an options mapping (a manifest run's opts, vars() of the parsed command line) -> run_one_point's keywords of
     POINT_OPTIONS; an option that is missing, None or otherwise false takes its default"""
     return {name: (norm or (lambda v: v))(opts.get(name) or default) for name, default, norm in POINT_OPTIONS}
+
+
+def prefilter_kwargs(opts):
+    """an options mapping -> run_one_point's keywords of the temporal pre-filter; missing or None: the defaults (off, radius 2)"""
+    level, radius = opts.get("temporal_filter"), opts.get("tf_radius")
+    return {"temporal_filter": 0 if level is None else level, "tf_radius": 2 if radius is None else radius}
 
 
 def run_sweep(make_nets, src_path, width, height, frame_num, rate_num=4, qp_i=None, qp_p=None, bin_prefix=None, **kw):
@@ -781,7 +823,8 @@ def run_job(nets, job, opts):
     log = run_one_point(nets[0], nets[1], job["src_path"], job["src_width"], job["src_height"], job["frame_num"],
                         job["qp_i"], job["qp_p"], intra_period=job["intra_period"], reset_interval=job["reset_interval"],
                         bin_path=bin_path, rec_path=rec_path, device="cuda:0", src_type=job.get("src_type", "yuv420"),
-                        target_bpp=target_bpp(opts, job["src_width"], job["src_height"]), **point_kwargs(opts))
+                        target_bpp=target_bpp(opts, job["src_width"], job["src_height"]), **prefilter_kwargs(opts),
+                        **point_kwargs(opts))
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -848,7 +891,8 @@ def _str2bool(v):
 
 
 def _add_extension_options(ap, flag):
-    """this project's options beyond the reference's: adaptive I frames, rate control, digests, reduced resolution, film grain"""
+    """this project's options beyond the reference's: adaptive I frames, rate control, digests, reduced resolution, film grain,
+    the temporal pre-filter"""
     from .resize import FILTERS, parse_size
     ap.add_argument("--scenecut", type=int, default=0, metavar="PCT",
                     help="adaptive I frames: a frame whose low-resolution difference to its predecessor is at least PCT percent "
@@ -875,6 +919,13 @@ def _add_extension_options(ap, flag):
                     help="film-grain synthesis: at every I frame the grain the codec removed is estimated on the device and "
                          "written as a 14-byte grain unit; the decode loop puts it back on the pictures it stores, not on "
                          "the ones it measures (docs/film_grain.md) - this project's extension, not readable by the reference")
+    ap.add_argument("--temporal-filter", "--temporal_filter", type=int, default=0, choices=range(6), metavar="L",
+                    help="motion-compensated temporal denoising of the source in front of the encoder at strength L = 1 .. 5 "
+                         "(0 = off; 3 is recommended; docs/temporal_filter.md): encoder side only, the stream format is "
+                         "unchanged.  The counterpart of --film-grain: the encoder stops spending bits on noise the decoder "
+                         "synthesises anyway.  Metrics stay those against the unfiltered source")
+    ap.add_argument("--tf-radius", "--tf_radius", type=int, default=2, choices=(1, 2), metavar="R",
+                    help="with --temporal-filter: references up to R frames before and after a frame (the encoder reads R frames ahead)")
 
 
 def build_parser():
@@ -947,7 +998,8 @@ def manifest_options(args, ap):
     stream_path = args.stream_path or ("out_bin" if args.write_stream else None)      # (the reference's default folder)
     opts = {k: getattr(args, k) for k in ("rate_num", "qp_i", "qp_p", "force_root_path", "force_frame_num", "force_intra_period",
                                           "reset_interval", "model_i", "model_p", "force_zero_thres", "fp32", "target_bpp",
-                                          "target_kbps", "fps", "force_intra", "check_existing", "save_decoded_frame")}
+                                          "target_kbps", "fps", "force_intra", "check_existing", "save_decoded_frame",
+                                          "temporal_filter", "tf_radius")}
     opts.update(gpu_ids=gpu_ids, stream_path=stream_path, **point_kwargs(vars(args)))
     return opts, gpus
 
@@ -980,7 +1032,7 @@ def main(argv=None):
                     args.src, args.width, args.height, args.frames, args.rate_num, args.qp_i or None, args.qp_p or None,
                     bin_prefix=args.bin_prefix, intra_period=args.intra_period, reset_interval=args.reset_interval,
                     src_type=args.src_type, target_bpp=target_bpp(vars(args), args.width, args.height),
-                    **point_kwargs(vars(args)))
+                    **prefilter_kwargs(vars(args)), **point_kwargs(vars(args)))
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:

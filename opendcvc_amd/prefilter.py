@@ -1,0 +1,208 @@
+"""Motion-compensated temporal pre-filter of the encoder's input (docs/temporal_filter.md, csrc/dcvc_tf.hip; no reference
+counterpart): every frame is blended with up to four of its unfiltered neighbours, each gathered block by block at the vector
+an integer-pyramid motion search finds for it, with weights that fall to zero where the neighbour does not match.  Encoder
+side only - the stream and the decoder know nothing of it.  The arithmetic is integer up to one fp32 blend per sample; the
+kernels and the numpy restatement tests/tf_ref.py agree bit for bit."""
+import ctypes
+
+LEVELS = (1, 2, 3, 4, 5)                               # strength: T = 4 << level 10-bit codes
+RADII = (1, 2)
+MAX_REFS = 4
+
+
+def check_options(level, radius):
+    """(level, radius) as integers; level 0 (off) .. 5, radius 1 or 2"""
+    if isinstance(level, bool) or not isinstance(level, int) or not 0 <= level <= LEVELS[-1]:
+        raise ValueError(f"temporal filter level {level!r}: 0 (off) .. {LEVELS[-1]}")
+    if isinstance(radius, bool) or radius not in RADII:
+        raise ValueError(f"temporal filter radius {radius!r}: 1 or 2")
+    return level, int(radius)
+
+
+def window(n_frames, radius):
+    """for every frame t of an n_frames sequence the (index, distance) list of its references in accumulation order
+    (distance -1, +1, -2, +2, those inside the sequence).  Pure."""
+    n_frames, radius = int(n_frames), int(radius)
+    if n_frames < 0 or radius not in RADII:
+        raise ValueError(f"window({n_frames}, {radius}): a frame count >= 0 and radius 1 or 2")
+    return [_refs_of(t, n_frames, radius) for t in range(n_frames)]
+
+
+def _refs_of(t, n_frames, radius):
+    return [(t + d, d) for k in range(1, radius + 1) for d in (-k, k) if 0 <= t + d < n_frames]
+
+
+def _stream():
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class TemporalFilter:
+    """The filter on `device` at strength `level` (1 .. 5) with references up to `radius` (1, 2) frames away.
+    filter() and motion() are stateless; push() / flush() run a sequence through a ring of 2 * radius + 1 source frames whose
+    pyramids are made once per frame.  Everything is sized at the first frame (and again if the frames change shape) and
+    nothing is allocated per frame; all work is enqueued on the current stream and nothing is waited for, except by
+    weight_sum().  A frame push() / flush() returns lives in one of radius + 1 buffers of the object: it holds until radius + 1
+    further frames have come out."""
+
+    def __init__(self, device="cuda:0", level=3, radius=2):
+        import torch
+        level, radius = check_options(level, radius)
+        if level == 0:
+            raise ValueError("temporal filter level 0 is 'off': make no TemporalFilter")
+        self.device, self.level, self.radius = torch.device(device), level, radius
+        self._total = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._key = None
+        self.reset()
+
+    # ------------------------------------------------------------------------------ sizing
+    @staticmethod
+    def _frame(x):
+        if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 3:
+            raise ValueError(f"a [1, 3, Hp, Wp] frame is expected, got {tuple(x.shape)}")
+        return x.contiguous()
+
+    def _size(self, x, size):
+        """buffers for frames like x with the picture size = (H, W)"""
+        import torch
+        from . import _lib
+        H, W = (int(v) for v in size)
+        key = (tuple(x.shape), x.dtype, H, W)
+        if key == self._key:
+            return
+        if H < 1 or W < 1 or H > x.shape[2] or W > x.shape[3]:
+            raise ValueError(f"a {H} x {W} picture does not lie in a frame of {x.shape[2]} x {x.shape[3]}")
+        L = _lib.lib()
+        n = 2 * self.radius + 1
+        dev = self.device
+        gh, gw = (H + 7) // 8, (W + 7) // 8
+        self._ring = torch.empty((n,) + tuple(x.shape), dtype=x.dtype, device=dev)
+        self._out = torch.empty((self.radius + 1,) + tuple(x.shape), dtype=x.dtype, device=dev)
+        self._pyr_elems = L.dcvc_tf_pyramid_bytes(H, W) // 2
+        self._pyr = torch.empty((n + 1 + MAX_REFS, self._pyr_elems), dtype=torch.int16, device=dev)      # the ring's, then filter()'s own
+        self._ws = torch.empty(max(L.dcvc_tf_motion_ws_bytes(H, W), 1), dtype=torch.uint8, device=dev)
+        self._mv = torch.empty((MAX_REFS, gh, gw, 2), dtype=torch.int16, device=dev)
+        self._err = torch.empty((MAX_REFS, gh, gw), dtype=torch.int32, device=dev)
+        self._key = key
+        self.reset()
+
+    def reset(self):
+        """forgets the frames pushed so far and zeroes the weight sum; the buffers stay"""
+        self._pushed = self._emitted = 0
+        self._size_of_sequence = None
+        self._total.zero_()
+
+    # ------------------------------------------------------------------------------ the kernels
+    def _pyramid(self, x, size, slot):
+        from . import _lib
+        from . import nn as L
+        _lib.check(_lib.lib().dcvc_tf_pyramid(L.dtype_code(x.dtype), L._p(x), x.shape[-2], x.shape[-1], size[0], size[1],
+                                              L._p(self._pyr[slot]), _stream()), "dcvc_tf_pyramid")
+
+    def _motion(self, cur_slot, ref_slots, size):
+        from . import _lib
+        from . import nn as L
+        n = len(ref_slots)
+        pyrs = (ctypes.c_void_p * n)(*[self._pyr[s].data_ptr() for s in ref_slots])
+        _lib.check(_lib.lib().dcvc_tf_motion(L._p(self._pyr[cur_slot]), pyrs, n, size[0], size[1], L._p(self._mv), L._p(self._err),
+                                             L._p(self._ws), _stream()), "dcvc_tf_motion")
+
+    def _blend(self, cur, refs, dists, size, out):
+        from . import _lib
+        from . import nn as L
+        n = len(refs)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[r.data_ptr() for r in refs])
+        _lib.check(_lib.lib().dcvc_tf_blend(L.dtype_code(cur.dtype), L._p(cur), ptrs, (ctypes.c_int * max(n, 1))(*dists), n,
+                                            cur.shape[-2], cur.shape[-1], size[0], size[1], L._p(self._mv), L._p(self._err),
+                                            self.level, L._p(out), L._p(self._total), _stream()), "dcvc_tf_blend")
+
+    def _check(self, cur, refs, dists, size):
+        cur = self._frame(cur)
+        refs = [self._frame(r) for r in refs]
+        dists = [int(d) for d in dists]
+        if len(refs) != len(dists) or len(refs) > MAX_REFS:
+            raise ValueError(f"{len(refs)} references with {len(dists)} distances: at most {MAX_REFS}, one distance each")
+        if any(d not in (-2, -1, 1, 2) for d in dists):
+            raise ValueError(f"distances {dists}: each -2, -1, 1 or 2")
+        if any(r.shape != cur.shape or r.dtype != cur.dtype for r in refs):
+            raise ValueError("the references must have the current frame's shape and type")
+        return cur, refs, dists, tuple(int(v) for v in size)
+
+    # ------------------------------------------------------------------------------ stateless
+    def filter(self, cur, refs, dists, size, out=None):
+        """cur filtered against refs (accumulated in the order given; dists: their distances, +-1 / +-2) on its
+        size = (H, W) picture, replicate-padded to cur's shape.  out: None (a new tensor) or a contiguous tensor like cur that
+        overlaps no input.  Adds to the weight sum."""
+        import torch
+        cur, refs, dists, size = self._check(cur, refs, dists, size)
+        if out is None:
+            out = torch.empty_like(cur)
+        elif out.shape != cur.shape or out.dtype != cur.dtype or not out.is_contiguous():
+            raise ValueError("out must be a contiguous tensor of cur's shape and type")
+        self._size(cur, size)
+        n = 2 * self.radius + 1
+        if refs:
+            self._pyramid(cur, size, n)
+            for i, r in enumerate(refs):
+                self._pyramid(r, size, n + 1 + i)
+            self._motion(n, [n + 1 + i for i in range(len(refs))], size)
+        self._blend(cur, refs, dists, size, out)
+        return out
+
+    def motion(self, cur, ref, size):
+        """the level-0 vectors and errors of one reference: (mv int16 [gh, gw, 2] as (y, x), err int32 [gh, gw]), new tensors"""
+        cur, (ref,), _, size = self._check(cur, [ref], [1], size)
+        self._size(cur, size)
+        n = 2 * self.radius + 1
+        self._pyramid(cur, size, n)
+        self._pyramid(ref, size, n + 1)
+        self._motion(n, [n + 1], size)
+        return self._mv[0].clone(), self._err[0].clone()
+
+    def pyramid(self, x, size):
+        """Q0 | Q1 | Q2 of x's luma as one int16 tensor holding the uint16 codes (a new tensor)"""
+        x = self._frame(x)
+        size = tuple(int(v) for v in size)
+        self._size(x, size)
+        self._pyramid(x, size, 2 * self.radius + 1)
+        return self._pyr[2 * self.radius + 1].clone()
+
+    # ------------------------------------------------------------------------------ a sequence
+    def _emit(self, n_known):
+        """frame self._emitted of a sequence of which n_known frames are in the ring"""
+        t, n = self._emitted, 2 * self.radius + 1
+        refs = _refs_of(t, n_known, self.radius)
+        slots = [i % n for i, _ in refs]
+        if refs:
+            self._motion(t % n, slots, self._size_of_sequence)
+        out = self._out[t % (self.radius + 1)]
+        self._blend(self._ring[t % n], [self._ring[s] for s in slots], [d for _, d in refs], self._size_of_sequence, out)
+        self._emitted += 1
+        return out
+
+    def push(self, x, size):
+        """the next source frame (copied into the ring) -> the list of filtered frames it completes: none for the first
+        `radius` frames, then one per call, `radius` frames behind the input"""
+        x = self._frame(x)
+        size = tuple(int(v) for v in size)
+        if self._pushed and (self._key != (tuple(x.shape), x.dtype) + size or size != self._size_of_sequence):
+            raise ValueError("the frames of a sequence must have one shape, type and picture size: reset() first")
+        self._size(x, size)
+        self._size_of_sequence = size
+        slot = self._pushed % (2 * self.radius + 1)
+        self._ring[slot].copy_(x)
+        self._pyramid(self._ring[slot], size, slot)
+        self._pushed += 1
+        # frame t is complete once frame t + radius is in; the window of an early frame is cut at the sequence's start only
+        return [self._emit(self._pushed)] if self._pushed > self.radius else []
+
+    def flush(self):
+        """the filtered frames still owed (at most `radius`), in order; the sequence is over - the next push starts another,
+        the weight sum stays"""
+        out = [self._emit(self._pushed) for _ in range(self._pushed - self._emitted)]
+        self._pushed = self._emitted = 0
+        return out
+
+    def weight_sum(self):
+        """the sum over the luma samples filtered since reset() of (Wsum - 256); one read-back"""
+        return int(self._total.item())
