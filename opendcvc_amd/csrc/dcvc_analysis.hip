@@ -11,6 +11,7 @@
 // integer partials, and one small launch that sums the partials into pinned host memory.  No LDS in the luma pass, no
 // atomics anywhere.
 #include "common.hpp"
+#include "plane_math.hpp"
 
 #include <algorithm>
 #include <cstdint>
@@ -69,20 +70,6 @@ __global__ __launch_bounds__(AB) void lowres_kernel(const T* luma, int64_t ld, i
 
 __device__ __forceinline__ unsigned absdiff(unsigned a, unsigned b) { return a > b ? a - b : b - a; }
 
-// sum over the workgroup (tree over the thread index); thread 0 holds the result
-__device__ __forceinline__ unsigned long long block_sum(unsigned long long v, unsigned long long* red)
-{
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = AB / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const unsigned long long r = red[0];
-    __syncthreads();     // (red is reused by the next sum)
-    return r;
-}
-
 // partial[3 * workgroup + {0, 1, 2}] = the workgroup's share of inter, intra, total
 __global__ __launch_bounds__(AB) void stats_partial_kernel(const uint16_t* cur, const uint16_t* prev, int bw, int nblk,
                                                            unsigned long long* partial)
@@ -97,9 +84,9 @@ __global__ __launch_bounds__(AB) void stats_partial_kernel(const uint16_t* cur, 
         const unsigned dl = bx > 0 ? absdiff(v, cur[i - 1]) : 0u, dt = by > 0 ? absdiff(v, cur[i - bw]) : 0u;
         intra += (bx > 0 && by > 0) ? min(dl, dt) : dl + dt;     // (one of dl, dt is 0 on the first row / column)
     }
-    inter = block_sum(inter, red);
-    intra = block_sum(intra, red);
-    total = block_sum(total, red);
+    inter = block_sum<AB>(inter, red);
+    intra = block_sum<AB>(intra, red);
+    total = block_sum<AB>(total, red);
     if (threadIdx.x == 0) {
         partial[3 * blockIdx.x + 0] = inter;
         partial[3 * blockIdx.x + 1] = intra;
@@ -117,7 +104,7 @@ __global__ __launch_bounds__(AB) void stats_finish_kernel(const unsigned long lo
 #pragma unroll
         for (int k = 0; k < 3; ++k) s[k] += partial[3 * i + k];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) s[k] = block_sum(s[k], red);
+    for (int k = 0; k < 3; ++k) s[k] = block_sum<AB>(s[k], red);
     if (threadIdx.x == 0) {
         out[0] = s[0];
         out[1] = s[1];

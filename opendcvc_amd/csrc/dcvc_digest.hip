@@ -7,6 +7,7 @@
 // adds the partials by index, compares and writes {digest, status} into pinned host memory.  No atomics, no host read in
 // between.  A drift and damage check, not a cryptographic hash.
 #include "common.hpp"
+#include "plane_math.hpp"
 
 #include <algorithm>
 #include <cstdint>
@@ -26,13 +27,6 @@ __host__ __device__ __forceinline__ u64 mix(u64 z)
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 // partial[workgroup] = the sum of mix(w_j + (j + 1) G) over the words the workgroup reads.  head: 1 if w is not 16-byte

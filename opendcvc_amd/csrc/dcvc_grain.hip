@@ -13,6 +13,7 @@
 // roundings to integers is integer arithmetic, so the table does not depend on the order of summation.  Flat blocks are
 // added to a workgroup's table in LDS and that to the int64 table in memory: 24 integer vector atomics per workgroup.
 #include "common.hpp"
+#include "frame_host.hpp"
 #include "plane_math.hpp"
 
 #include <algorithm>
@@ -35,10 +36,6 @@ struct GrainArgs {               // dcvc_grain_params as the kernel reads it
     int scale_c[2];
 };
 
-template <typename T>
-struct alignas(16) Pix8 {        // 8 pixels of a model row: one 16-byte access in fp16, two in fp32
-    T v[8];
-};
 struct alignas(16) I4 {
     int v[4];
 };
@@ -148,35 +145,17 @@ __global__ __launch_bounds__(RB) void grain_apply_kernel(const T* x, int Hp, int
     }
 }
 
-template <typename T, int R>
-void launch_apply(bool vec, dim3 grid, hipStream_t st, const void* x, int Hp, int Wp, int H, int W, void* out, const GrainArgs& p)
+template <typename F>
+void with_corr(int corr, F&& f)
 {
-    if (vec)
-        grain_apply_kernel<T, R, true><<<grid, RB, 0, st>>>((const T*)x, Hp, Wp, H, W, (T*)out, p);
-    else
-        grain_apply_kernel<T, R, false><<<grid, RB, 0, st>>>((const T*)x, Hp, Wp, H, W, (T*)out, p);
-}
-
-template <typename T>
-void launch_apply_corr(int corr, bool vec, dim3 grid, hipStream_t st, const void* x, int Hp, int Wp, int H, int W, void* out,
-                       const GrainArgs& p)
-{
-    if (corr == 0)
-        launch_apply<T, 0>(vec, grid, st, x, Hp, Wp, H, W, out, p);
-    else if (corr == 1)
-        launch_apply<T, 1>(vec, grid, st, x, Hp, Wp, H, W, out, p);
-    else
-        launch_apply<T, 2>(vec, grid, st, x, Hp, Wp, H, W, out, p);
+    switch (corr) {
+    case 0: f(dcvc::IC<0>{}); break;
+    case 1: f(dcvc::IC<1>{}); break;
+    default: f(dcvc::IC<2>{}); break;
+    }
 }
 
 // ---------------------------------------------------------------------------------- estimation
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // four pixels of row (lane >> 2) of the block at `at`, widened
 template <typename T, bool VEC>
 __device__ __forceinline__ void load4(const T* p, int64_t at, float* f)
@@ -290,16 +269,11 @@ int dcvc_grain_apply(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W
                      uint32_t t, void* stream)
 {
     const char* who = "dcvc_grain_apply";
-    DCVC_REQUIRE(dtype == DCVC_F16 || dtype == DCVC_F32, "%s: bad dtype %d", who, dtype);
-    DCVC_REQUIRE(H > 0 && W > 0 && Hp >= H && Wp >= W, "%s: the tensor (%d x %d) does not hold the picture (%d x %d)", who, Hp,
-                 Wp, H, W);
-    DCVC_REQUIRE(x_nchw && out_nchw, "%s: null pointer", who);
+    if (int rc = dcvc::check_frame(who, "x", dtype, x_nchw, Hp, Wp, H, W)) return rc;
+    if (int rc = dcvc::check_frame(who, "out", dtype, out_nchw, Hp, Wp, H, W)) return rc;
     DCVC_REQUIRE(params.corr <= 2, "%s: corr %d above 2", who, (int)params.corr);
-    const uintptr_t es = (uintptr_t)dcvc::elem_size(dtype);
-    DCVC_REQUIRE((uintptr_t)x_nchw % es == 0 && (uintptr_t)out_nchw % es == 0, "%s: a tensor is not aligned to its element size", who);
-    DCVC_REQUIRE((int64_t)3 * Hp * Wp < ((int64_t)1 << 40), "%s: tensor too large", who);
-    const dim3 grid((unsigned)((Wp + TW - 1) / TW), (unsigned)((Hp + TH - 1) / TH), 3);
-    DCVC_REQUIRE(grid.y <= 65535u, "%s: height %d above %d", who, Hp, 65535 * TH);
+    dim3 grid;
+    if (int rc = dcvc::tile_grid(who, Wp, Hp, TW, TH, grid)) return rc;
     static const int gains[3] = {3547, 591, 51};
     GrainArgs a;
     a.key = (uint32_t)params.seed | (t & 0x3FFFu) << 18;
@@ -308,50 +282,40 @@ int dcvc_grain_apply(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W
     for (int k = 0; k < 8; ++k) a.scale_y |= (uint64_t)params.scale_y[k] << (8 * k);
     a.scale_c[0] = params.scale_cb;
     a.scale_c[1] = params.scale_cr;
-    const bool vec = (((uintptr_t)x_nchw | (uintptr_t)out_nchw) & 15) == 0 && ((int64_t)Wp * (int64_t)es) % 16 == 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DCVC_F16)
-        launch_apply_corr<_Float16>(params.corr, vec, grid, st, x_nchw, Hp, Wp, H, W, out_nchw, a);
-    else
-        launch_apply_corr<float>(params.corr, vec, grid, st, x_nchw, Hp, Wp, H, W, out_nchw, a);
-    DCVC_LAUNCH_CHECK();
-    return 0;
+    const size_t es = dcvc::elem_size(dtype);
+    const bool vec = dcvc::vec_ok(16 / (int)es, es, Wp, x_nchw, out_nchw);
+    return dcvc::typed(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        with_corr(params.corr, [&](auto r) {
+            dcvc::with_flag(vec, [&](auto v) {
+                grain_apply_kernel<T, decltype(r)::value, decltype(v)::value><<<grid, RB, 0, (hipStream_t)stream>>>(
+                    (const T*)x_nchw, Hp, Wp, H, W, (T*)out_nchw, a);
+            });
+        });
+    });
 }
 
 int dcvc_grain_stats(int dtype, const void* noisy_nchw, const void* clean_nchw, int Hp, int Wp, int H, int W, int64_t* table,
                      void* stream)
 {
     const char* who = "dcvc_grain_stats";
-    DCVC_REQUIRE(dtype == DCVC_F16 || dtype == DCVC_F32, "%s: bad dtype %d", who, dtype);
-    DCVC_REQUIRE(H > 0 && W > 0 && Hp >= H && Wp >= W, "%s: the tensors (%d x %d) do not hold the picture (%d x %d)", who, Hp,
-                 Wp, H, W);
-    DCVC_REQUIRE(noisy_nchw && clean_nchw && table, "%s: null pointer", who);
-    const uintptr_t es = (uintptr_t)dcvc::elem_size(dtype);
-    DCVC_REQUIRE((uintptr_t)noisy_nchw % es == 0 && (uintptr_t)clean_nchw % es == 0, "%s: a tensor is not aligned to its element size",
-                 who);
-    DCVC_REQUIRE(((uintptr_t)table & 7) == 0, "%s: the table is not 8-byte aligned", who);
-    DCVC_REQUIRE((int64_t)3 * Hp * Wp < ((int64_t)1 << 40), "%s: tensors too large", who);
+    if (int rc = dcvc::check_frame(who, "noisy", dtype, noisy_nchw, Hp, Wp, H, W)) return rc;
+    if (int rc = dcvc::check_frame(who, "clean", dtype, clean_nchw, Hp, Wp, H, W)) return rc;
+    DCVC_REQUIRE(table && ((uintptr_t)table & 7) == 0, "%s: the table is null or not 8-byte aligned", who);
     hipStream_t st = (hipStream_t)stream;
     DCVC_HIP(hipMemsetAsync(table, 0, TABLE_WORDS * sizeof(int64_t), st));
     const int bh = H / 16, bw = W / 16;
     if (bh == 0 || bw == 0) return 0;
     DCVC_REQUIRE((int64_t)bh * bw < ((int64_t)1 << 30), "%s: too many blocks", who);
     const int groups = (int)std::min<int64_t>(((int64_t)bh * bw + RB / 64 - 1) / (RB / 64), STATS_MAX_GROUPS);
-    const bool vec = (((uintptr_t)noisy_nchw | (uintptr_t)clean_nchw) % (4 * es)) == 0 && Wp % 4 == 0;
+    const bool vec = dcvc::vec_ok(4, dcvc::elem_size(dtype), Wp, noisy_nchw, clean_nchw);
     unsigned long long* tb = reinterpret_cast<unsigned long long*>(table);
-    if (dtype == DCVC_F16) {
-        if (vec)
-            grain_stats_kernel<_Float16, true><<<groups, RB, 0, st>>>((const _Float16*)noisy_nchw, (const _Float16*)clean_nchw, Hp, Wp, bh, bw, tb);
-        else
-            grain_stats_kernel<_Float16, false><<<groups, RB, 0, st>>>((const _Float16*)noisy_nchw, (const _Float16*)clean_nchw, Hp, Wp, bh, bw, tb);
-    } else {
-        if (vec)
-            grain_stats_kernel<float, true><<<groups, RB, 0, st>>>((const float*)noisy_nchw, (const float*)clean_nchw, Hp, Wp, bh, bw, tb);
-        else
-            grain_stats_kernel<float, false><<<groups, RB, 0, st>>>((const float*)noisy_nchw, (const float*)clean_nchw, Hp, Wp, bh, bw, tb);
-    }
-    DCVC_LAUNCH_CHECK();
-    return 0;
+    return dcvc::typed(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        dcvc::with_flag(vec, [&](auto v) {
+            grain_stats_kernel<T, decltype(v)::value><<<groups, RB, 0, st>>>((const T*)noisy_nchw, (const T*)clean_nchw, Hp, Wp, bh, bw, tb);
+        });
+    });
 }
 
 }  // extern "C"

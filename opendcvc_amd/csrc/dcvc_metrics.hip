@@ -4,6 +4,7 @@
 // All metric arithmetic is fp64 (var = E[a^2] - mu^2 cancels at values up to 65025) without contraction, reductions run
 // in a fixed order (per-thread strided sums, a block tree, partials summed by index): the same input gives the same bits.
 #include "common.hpp"
+#include "frame_host.hpp"
 #include "plane_math.hpp"
 
 #include <algorithm>
@@ -26,20 +27,6 @@ __device__ __forceinline__ double ldd(const void* p, int type, int64_t i)
     case DCVC_U16: return (double)static_cast<const uint16_t*>(p)[i];
     default: return static_cast<const double*>(p)[i];
     }
-}
-
-// sum over the block in a fixed order (tree over the thread index); every thread gets the result
-__device__ __forceinline__ double block_sum(double v, double* red)
-{
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = MB / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();     // (red may be reused by the caller)
-    return r;
 }
 
 // ------------------------------------------------------------------ metric planes
@@ -70,7 +57,7 @@ __global__ __launch_bounds__(MB) void sse_partial_kernel(int ta, const void* a, 
         const double d = ldd(a, ta, i) - ldd(b, tb, i);
         s = s + d * d;
     }
-    s = block_sum(s, red);
+    s = block_sum<MB>(s, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -87,7 +74,7 @@ __global__ __launch_bounds__(MB) void sum_partials_kernel(const double* partial,
     const int e = blockIdx.x;
     double s = 0.0;
     for (int i = threadIdx.x; i < a.cnt[e]; i += MB) s = s + partial[a.off[e] + i];
-    s = block_sum(s, red);
+    s = block_sum<MB>(s, red);
     if (threadIdx.x == 0) out[e] = s / a.div[e];
 }
 
@@ -172,8 +159,8 @@ __global__ __launch_bounds__(MB) void msssim_level_kernel(int ta, const void* a,
         cs = cs + cs_num / cs_den;
         ssim = ssim + ((2.0 * mu_a * mu_b + c1) * cs_num) / ((mu_a * mu_a + mu_b * mu_b + c1) * cs_den);
     }
-    ssim = block_sum(ssim, red);
-    cs = block_sum(cs, red);
+    ssim = block_sum<MB>(ssim, red);
+    cs = block_sum<MB>(cs, red);
     if (threadIdx.x == 0) {
         const int nb = gridDim.x * gridDim.y, bid = blockIdx.y * gridDim.x + blockIdx.x;
         partial[bid] = ssim;
@@ -216,21 +203,6 @@ bool ms_plan(int H, int W, MsPlan& p)
     return true;
 }
 
-template <typename F>
-int typed(int dtype, F&& launch)
-{
-    if (dtype == DCVC_F16)
-        launch(_Float16{});
-    else if (dtype == DCVC_F32)
-        launch(float{});
-    else {
-        dcvc::set_error("bad dtype %d", dtype);
-        return dcvc::E_ARG;
-    }
-    DCVC_LAUNCH_CHECK();
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -238,9 +210,12 @@ extern "C" {
 int dcvc_frame_to_yuv420_planes(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, void* y, void* u, void* v,
                                 void* stream)
 {
-    DCVC_REQUIRE(x_nchw && y && u && v && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && Hp >= H && Wp >= W,
-                 "dcvc_frame_to_yuv420_planes: bad arguments");
-    return typed(dtype, [&](auto tag) {
+    const char* who = "dcvc_frame_to_yuv420_planes";
+    if (int rc = dcvc::check_frame(who, "the frame", dtype, x_nchw, Hp, Wp, H, W)) return rc;
+    const uintptr_t planes = (uintptr_t)y | (uintptr_t)u | (uintptr_t)v;
+    DCVC_REQUIRE(y && u && v && planes % dcvc::elem_size(dtype) == 0 && H % 2 == 0 && W % 2 == 0,
+                 "%s: a null or misaligned plane or an odd size (%d x %d)", who, H, W);
+    return dcvc::typed(dtype, [&](auto tag) {
         using T = decltype(tag);
         metric_planes_kernel<T><<<mblocks((int64_t)H * W * 3 / 2), MB, 0, (hipStream_t)stream>>>(
             (const T*)x_nchw, Hp, Wp, H, W, (T*)y, (T*)u, (T*)v);

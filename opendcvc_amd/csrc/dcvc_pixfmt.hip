@@ -1,6 +1,7 @@
-// dcvc_pixfmt.hip - frame I/O for the raw formats beyond planar 8-bit 4:2:0: bit depths 8 .. 16 (little-endian 16-bit
-// words above 8 bits, value in the low or in the top bits), 4:2:0 and 4:4:4, planar and semi-planar (NV12 / P010: one
-// interleaved UV plane), rows with a pitch.  The arithmetic is the reference family's YUVReader / YUVWriter
+// dcvc_pixfmt.hip - frame I/O: raw planes and RGB pictures <-> model frames.  First the streaming kernels of the raw formats:
+// bit depths 8 .. 16 (little-endian 16-bit words above 8 bits, value in the low or in the top bits), 4:2:0 and 4:4:4, planar
+// and semi-planar (NV12 / P010: one interleaved UV plane), rows with a pitch.  The arithmetic is the reference family's
+// YUVReader / YUVWriter
 // (DCVC-FM src/utils/video_reader.py:130-181, video_writer.py:85-128, src/transforms/functional.py:98-131):
 //   load   (float)s / (float)max_val, ONE rounding to the storage type, nearest chroma up-sampling, replicate pad
 //   store  fp32: 4:2:0 chroma ((a + b) + (d + e)) * 0.25f, clip(., 0, 1) * max_val, rintf (nearest even), clip(0, max_val)
@@ -8,7 +9,11 @@
 // These are streaming kernels: a thread owns 8 consecutive pixels of a row (4:2:0: an 8 x 2 luma block and the 4 chroma
 // samples of both planes under it, read / formed once), the model side moves in 16-byte accesses, the sample side in the
 // widest access the planes' addresses and strides allow (chosen per launch, uniform over the grid).  No LDS, no atomics.
+// Then the older element-per-thread kernels of tight planar 8-bit 4:2:0 and of RGB (PNG sources), with the rounding rules
+// of DCVC-RT's test_video.py.
 #include "common.hpp"
+#include "dcvc_math.h"
+#include "frame_host.hpp"
 #include "plane_math.hpp"
 
 #include <algorithm>
@@ -23,10 +28,6 @@ enum { L_420P = 0, L_420SP = 1, L_444P = 2 }; // plane layout of a launch
 template <typename E, int VW>
 struct alignas(sizeof(E) * VW) Pack {
     E v[VW];
-};
-template <typename T>
-struct alignas(16) Pix8 {                     // 8 pixels of a model row: one 16-byte access in fp16, two in fp32
-    T v[8];
 };
 
 // an interleaved (U, V) pair of samples as one element: U in the low half (little-endian memory order U, V)
@@ -242,9 +243,104 @@ __global__ __launch_bounds__(PB) void frame_to_planes_kernel(const T* x, int HP,
     }
 }
 
+// ------------------------------------------------------------------ YUV 4:2:0 <-> model frame
+template <typename T>
+__global__ void yuv420_to_frame_kernel(const uint8_t* yp, const uint8_t* up, const uint8_t* vp, int H, int W, int HO,
+                                       int WO, T* out)
+{
+    const int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x;
+    if (i >= (int64_t)3 * HO * WO) return;
+    const int xw = (int)(i % WO), y = (int)((i / WO) % HO), c = (int)(i / ((int64_t)WO * HO));
+    const int sy = y < H ? y : H - 1, sx = xw < W ? xw : W - 1;        // replicate pad of the 4:4:4 frame
+    int v;
+    if (c == 0)
+        v = yp[(int64_t)sy * W + sx];
+    else
+        v = (c == 1 ? up : vp)[(int64_t)(sy >> 1) * (W >> 1) + (sx >> 1)];   // nearest chroma upsampling
+    st(out, i, (float)v / 255.0f);
+}
+
+template <typename T>
+__global__ void frame_to_yuv420_kernel(const T* x, int HP, int WP, int H, int W, int round_uv, uint8_t* yp, uint8_t* up,
+                                       uint8_t* vp)
+{
+    const int64_t ny = (int64_t)H * W, nc = (int64_t)(H >> 1) * (W >> 1);
+    const int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x;
+    if (i >= ny + 2 * nc) return;
+    if (i < ny) {
+        const int xw = (int)(i % W), y = (int)(i / W);
+        yp[i] = (uint8_t)dcvc_roundf(yuv420_luma<T>(x, WP, y, xw));
+        return;
+    }
+    const int64_t j = i - ny;
+    const int c = j < nc ? 1 : 2;
+    const int64_t k = c == 1 ? j : j - nc;
+    const int w2 = W >> 1;
+    const int xw = (int)(k % w2), y = (int)(k / w2);
+    float s = yuv420_chroma<T>(x + (int64_t)c * HP * WP, WP, y, xw);
+    if (round_uv) s = dcvc_roundf(s);
+    (c == 1 ? up : vp)[k] = (uint8_t)s;                                      // truncation like `.to(uint8)`
+}
+
+// ------------------------------------------------------------------ RGB (PNG sources) <-> model frame
+// ITU-R BT.709 weights as the reference's transforms.py:7-10 spells them; the scalars below are the fp32 values torch
+// uses when a Python float meets a float32 / float16 tensor.
+__device__ __forceinline__ void rgb_consts(float& kr, float& kg, float& kb)
+{
+    kr = 0.2126f;
+    kg = 0.7152f;
+    kb = 0.0722f;
+}
+
+// uint8 planar RGB [3][H][W] -> padded YCbCr model input: /255 (test_video.py:60-63), rgb2ycbcr in fp32 with the reference's
+// operation order and clamp (transforms.py:27-38), ONE rounding to the storage type (test_video.py:90), replicate pad (:179)
+template <typename T>
+__global__ void rgb_to_frame_kernel(const uint8_t* rgb, int H, int W, int HO, int WO, T* out)
+{
+    const int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x;
+    if (i >= (int64_t)HO * WO) return;
+    const int xw = (int)(i % WO), y = (int)(i / WO);
+    const int sy = y < H ? y : H - 1, sx = xw < W ? xw : W - 1;
+    const int64_t sp = (int64_t)sy * W + sx, plane = (int64_t)H * W;
+    const float r = (float)rgb[sp] / 255.0f, g = (float)rgb[plane + sp] / 255.0f, b = (float)rgb[2 * plane + sp] / 255.0f;
+    float kr, kg, kb;
+    rgb_consts(kr, kg, kb);
+    const float yy = (kr * r + kg * g) + kb * b;
+    const float cb = (0.5f * (b - yy)) / (float)(1.0 - 0.0722) + 0.5f;
+    const float cr = (0.5f * (r - yy)) / (float)(1.0 - 0.2126) + 0.5f;
+    const int64_t op = (int64_t)HO * WO;
+    st(out, i, clampf(yy, 0.f, 1.f));
+    st(out, op + i, clampf(cb, 0.f, 1.f));
+    st(out, 2 * op + i, clampf(cr, 0.f, 1.f));
+}
+
+// reconstruction [3][HP][WP] (YCbCr) -> clamp(ycbcr2rgb(x) * 255, 0, 255) of the HxW picture as [3][H][W] in the storage type:
+// every operation of transforms.py:41-53 + test_video.py:118-119 rounded to the storage type like the reference's tensors
+// (fp16 reconstructions are converted in fp16 there); what the reference's RGB PSNR / MS-SSIM / PNG writer read
+template <typename T>
+__global__ void frame_to_rgb_kernel(const T* x, int HP, int WP, int H, int W, T* out)
+{
+    const int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x;
+    if (i >= (int64_t)H * W) return;
+    const int xw = (int)(i % W), y = (int)(i / W);
+    const int64_t sp = (int64_t)y * WP + xw, plane = (int64_t)HP * WP;
+    auto q = [](float v) { return (float)to_t<T>(v); };
+    const float yy = ld(x, sp), cb = ld(x, plane + sp), cr = ld(x, 2 * plane + sp);
+    float kr, kg, kb;
+    rgb_consts(kr, kg, kb);
+    // (a Python scalar next to a half tensor enters torch's kernels in fp32 - the op-math type - not rounded to fp16)
+    const float sr = (float)(2.0 - 2.0 * 0.2126), sb = (float)(2.0 - 2.0 * 0.0722);
+    const float r = q(yy + q(sr * q(cr - 0.5f)));
+    const float b = q(yy + q(sb * q(cb - 0.5f)));
+    const float g = q(q(q(yy - q(kr * r)) - q(kb * b)) / kg);
+    const int64_t op = (int64_t)H * W;
+    st(out, i, clampf(q(clampf(r, 0.f, 1.f) * 255.0f), 0.f, 255.f));
+    st(out, op + i, clampf(q(clampf(g, 0.f, 1.f) * 255.0f), 0.f, 255.f));
+    st(out, 2 * op + i, clampf(q(clampf(b, 0.f, 1.f) * 255.0f), 0.f, 255.f));
+}
+
 // ------------------------------------------------------------------ host side
-template <int V>
-using IC = std::integral_constant<int, V>;
+using dcvc::IC;
 
 template <typename F>
 void with_access(int a, F&& f)
@@ -266,11 +362,6 @@ void with_layout(int layout, F&& f)
     }
 }
 
-inline bool aligned(const void* p, int64_t stride, int vw, int es)
-{
-    return ((uintptr_t)p % (uintptr_t)(vw * es)) == 0 && stride % vw == 0;
-}
-
 // the widest access class (8, 4, 2, 1) every plane of the launch allows: `es` bytes per element; the luma plane (and
 // 4:4:4 chroma, and UV pairs seen as samples) moves vw8 elements per access, planar 4:2:0 chroma vw4
 int access_class(int layout, int es, const void* y, const void* u, const void* v, int64_t ys, int64_t cs)
@@ -279,10 +370,10 @@ int access_class(int layout, int es, const void* y, const void* u, const void* v
     int a = 8;
     for (; a > 1; a >>= 1) {
         const int w8 = std::min(a, cap), w4 = std::min(std::max(a / 2, 1), cap);
-        bool ok = aligned(y, ys, w8, es);
-        if (layout == L_444P) ok = ok && aligned(u, cs, w8, es) && aligned(v, cs, w8, es);
-        if (layout == L_420P) ok = ok && aligned(u, cs, w4, es) && aligned(v, cs, w4, es);
-        if (layout == L_420SP) ok = ok && aligned(u, cs, 2 * std::min(std::max(a / 2, 1), 16 / (2 * es)), es);
+        bool ok = dcvc::vec_ok(w8, es, ys, y);
+        if (layout == L_444P) ok = ok && dcvc::vec_ok(w8, es, cs, u, v);
+        if (layout == L_420P) ok = ok && dcvc::vec_ok(w4, es, cs, u, v);
+        if (layout == L_420SP) ok = ok && dcvc::vec_ok(2 * std::min(std::max(a / 2, 1), 16 / (2 * es)), es, cs, u);
         if (ok) break;
     }
     return a;
@@ -324,7 +415,26 @@ int check_planes(const char* who, const Fmt& f, const void* y, const void* u, co
     return 0;
 }
 
+// the frame the streaming storers read, 8 pixels per access
+int check_frame8(const char* who, int dtype, const void* x, int Hp, int Wp, int H, int W)
+{
+    if (int rc = dcvc::check_frame(who, "the frame", dtype, x, Hp, Wp, H, W)) return rc;
+    DCVC_REQUIRE(Wp % 8 == 0 && ((uintptr_t)x & 15) == 0,
+                 "%s: the frame (%d x %d) must be 16-byte aligned and have a width that is a multiple of 8", who, Hp, Wp);
+    return 0;
+}
+
 inline unsigned blocks_for(int64_t threads) { return (unsigned)((threads + PB - 1) / PB); }
+
+// f(S{}) with S the sample type of `ss` bytes
+template <typename F>
+void with_sample(int ss, F&& f)
+{
+    if (ss == 1)
+        f(uint8_t{});
+    else
+        f(uint16_t{});
+}
 
 template <typename T, typename S>
 void launch_load(const Fmt& f, const void* y, const void* u, const void* v, int64_t ys, int64_t cs, int H, int W, int HO, int WO,
@@ -372,20 +482,11 @@ int dcvc_planes_to_frame(int dtype, int chroma, int bit_depth, int semi_planar, 
     DCVC_REQUIRE(WO % 8 == 0 && ((uintptr_t)out_nchw & 15) == 0 && (f.layout == L_444P || HO % 2 == 0),
                  "%s: the padded frame (%d x %d) must be 16-byte aligned, its width a multiple of 8 and, for 4:2:0, its "
                  "height even", who, HO, WO);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DCVC_F16) {
-        if (f.ss == 1)
-            launch_load<_Float16, uint8_t>(f, y, u_or_uv, v, y_stride, c_stride, H, W, HO, WO, out_nchw, st);
-        else
-            launch_load<_Float16, uint16_t>(f, y, u_or_uv, v, y_stride, c_stride, H, W, HO, WO, out_nchw, st);
-    } else {
-        if (f.ss == 1)
-            launch_load<float, uint8_t>(f, y, u_or_uv, v, y_stride, c_stride, H, W, HO, WO, out_nchw, st);
-        else
-            launch_load<float, uint16_t>(f, y, u_or_uv, v, y_stride, c_stride, H, W, HO, WO, out_nchw, st);
-    }
-    DCVC_LAUNCH_CHECK();
-    return 0;
+    return dcvc::typed(dtype, [&](auto tag) {
+        with_sample(f.ss, [&](auto s) {
+            launch_load<decltype(tag), decltype(s)>(f, y, u_or_uv, v, y_stride, c_stride, H, W, HO, WO, out_nchw, (hipStream_t)stream);
+        });
+    });
 }
 
 int dcvc_frame_to_planes(int dtype, int chroma, int bit_depth, int semi_planar, int msb_aligned, const void* x_nchw, int Hp,
@@ -395,50 +496,77 @@ int dcvc_frame_to_planes(int dtype, int chroma, int bit_depth, int semi_planar, 
     Fmt f;
     if (int rc = check_format(who, dtype, chroma, bit_depth, semi_planar, msb_aligned, H, W, f)) return rc;
     if (int rc = check_planes(who, f, y, u_or_uv, v, y_stride, c_stride, W)) return rc;
-    DCVC_REQUIRE(x_nchw && Hp >= H && Wp >= W && Wp % 8 == 0 && ((uintptr_t)x_nchw & 15) == 0,
-                 "%s: the frame (%d x %d) must hold the picture, be 16-byte aligned and have a width that is a multiple of 8", who,
-                 Hp, Wp);
-    hipStream_t st = (hipStream_t)stream;
-    if (f.ss == 1) {
-        const Quant<uint8_t> q{f.shift, f.maxf};
-        if (dtype == DCVC_F16)
-            launch_store<_Float16>(f.layout, q, x_nchw, Hp, Wp, H, W, y, u_or_uv, v, y_stride, c_stride, st);
-        else
-            launch_store<float>(f.layout, q, x_nchw, Hp, Wp, H, W, y, u_or_uv, v, y_stride, c_stride, st);
-    } else {
-        const Quant<uint16_t> q{f.shift, f.maxf};
-        if (dtype == DCVC_F16)
-            launch_store<_Float16>(f.layout, q, x_nchw, Hp, Wp, H, W, y, u_or_uv, v, y_stride, c_stride, st);
-        else
-            launch_store<float>(f.layout, q, x_nchw, Hp, Wp, H, W, y, u_or_uv, v, y_stride, c_stride, st);
-    }
-    DCVC_LAUNCH_CHECK();
-    return 0;
+    if (int rc = check_frame8(who, dtype, x_nchw, Hp, Wp, H, W)) return rc;
+    return dcvc::typed(dtype, [&](auto tag) {
+        with_sample(f.ss, [&](auto s) {
+            const Quant<decltype(s)> q{f.shift, f.maxf};
+            launch_store<decltype(tag)>(f.layout, q, x_nchw, Hp, Wp, H, W, y, u_or_uv, v, y_stride, c_stride, (hipStream_t)stream);
+        });
+    });
 }
 
 int dcvc_frame_to_metric_planes(int dtype, int chroma, int max_val, const void* x_nchw, int Hp, int Wp, int H, int W, float* y,
                                 float* u, float* v, void* stream)
 {
     const char* who = "dcvc_frame_to_metric_planes";
-    DCVC_REQUIRE(dtype == DCVC_F16 || dtype == DCVC_F32, "%s: bad dtype %d", who, dtype);
     DCVC_REQUIRE(chroma == 420 || chroma == 444, "%s: chroma %d (420 or 444)", who, chroma);
     DCVC_REQUIRE(max_val >= 255 && max_val <= 65535, "%s: max_val %d outside 255 .. 65535", who, max_val);
-    DCVC_REQUIRE(H > 0 && W > 0 && (chroma == 444 || (H % 2 == 0 && W % 2 == 0)),
-                 "%s: bad size %d x %d (4:2:0 needs an even height and width)", who, H, W);
+    DCVC_REQUIRE(chroma == 444 || (H % 2 == 0 && W % 2 == 0), "%s: 4:2:0 needs an even height and width (got %d x %d)", who, H, W);
     DCVC_REQUIRE(y && u && v && (((uintptr_t)y | (uintptr_t)u | (uintptr_t)v) & 3) == 0, "%s: null or misaligned plane", who);
-    DCVC_REQUIRE(x_nchw && Hp >= H && Wp >= W && Wp % 8 == 0 && ((uintptr_t)x_nchw & 15) == 0,
-                 "%s: the frame (%d x %d) must hold the picture, be 16-byte aligned and have a width that is a multiple of 8", who,
-                 Hp, Wp);
+    if (int rc = check_frame8(who, dtype, x_nchw, Hp, Wp, H, W)) return rc;
     const int layout = chroma == 444 ? L_444P : L_420P;
     const int64_t cs = chroma == 444 ? W : W / 2;
     const Metric m{(float)max_val};
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DCVC_F16)
-        launch_store<_Float16>(layout, m, x_nchw, Hp, Wp, H, W, y, u, v, W, cs, st);
-    else
-        launch_store<float>(layout, m, x_nchw, Hp, Wp, H, W, y, u, v, W, cs, st);
-    DCVC_LAUNCH_CHECK();
-    return 0;
+    return dcvc::typed(dtype, [&](auto tag) {
+        launch_store<decltype(tag)>(layout, m, x_nchw, Hp, Wp, H, W, y, u, v, W, cs, (hipStream_t)stream);
+    });
+}
+
+// ------------------------------------------------------------------ tight planar 8-bit 4:2:0 and RGB
+int dcvc_yuv420_to_frame(int dtype, const uint8_t* y, const uint8_t* u, const uint8_t* v, int H, int W, int pad_b,
+                         int pad_r, void* out_nchw, void* stream)
+{
+    DCVC_REQUIRE(y && u && v && out_nchw && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && pad_b >= 0 && pad_r >= 0,
+                 "dcvc_yuv420_to_frame: bad arguments (%dx%d)", H, W);
+    return dcvc::typed(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        yuv420_to_frame_kernel<T><<<blocks_for((int64_t)3 * (H + pad_b) * (W + pad_r)), PB, 0, (hipStream_t)stream>>>(
+            y, u, v, H, W, H + pad_b, W + pad_r, (T*)out_nchw);
+    });
+}
+
+int dcvc_frame_to_yuv420(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, int round_uv, uint8_t* y,
+                         uint8_t* u, uint8_t* v, void* stream)
+{
+    const char* who = "dcvc_frame_to_yuv420";
+    if (int rc = dcvc::check_frame(who, "the frame", dtype, x_nchw, Hp, Wp, H, W)) return rc;
+    DCVC_REQUIRE(y && u && v && H % 2 == 0 && W % 2 == 0, "%s: a null plane or an odd size (%d x %d)", who, H, W);
+    return dcvc::typed(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        frame_to_yuv420_kernel<T><<<blocks_for((int64_t)H * W * 3 / 2), PB, 0, (hipStream_t)stream>>>(
+            (const T*)x_nchw, Hp, Wp, H, W, round_uv, y, u, v);
+    });
+}
+
+int dcvc_rgb_to_frame(int dtype, const uint8_t* rgb, int H, int W, int pad_b, int pad_r, void* out_nchw, void* stream)
+{
+    DCVC_REQUIRE(rgb && out_nchw && H > 0 && W > 0 && pad_b >= 0 && pad_r >= 0, "dcvc_rgb_to_frame: bad arguments (%dx%d)", H, W);
+    return dcvc::typed(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        rgb_to_frame_kernel<T><<<blocks_for((int64_t)(H + pad_b) * (W + pad_r)), PB, 0, (hipStream_t)stream>>>(
+            rgb, H, W, H + pad_b, W + pad_r, (T*)out_nchw);
+    });
+}
+
+int dcvc_frame_to_rgb(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, void* out_chw, void* stream)
+{
+    const char* who = "dcvc_frame_to_rgb";
+    if (int rc = dcvc::check_frame(who, "the frame", dtype, x_nchw, Hp, Wp, H, W)) return rc;
+    DCVC_REQUIRE(out_chw && (uintptr_t)out_chw % dcvc::elem_size(dtype) == 0, "%s: out is null or not aligned to its element size", who);
+    return dcvc::typed(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        frame_to_rgb_kernel<T><<<blocks_for((int64_t)H * W), PB, 0, (hipStream_t)stream>>>((const T*)x_nchw, Hp, Wp, H, W, (T*)out_chw);
+    });
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 // Gaussian cost tables in LDS, z against its qp's rows in global memory), then one small launch that sums the partials
 // into pinned host memory.  No atomics, no host read in between.
 #include "common.hpp"
+#include "plane_math.hpp"
 
 #include <algorithm>
 #include <cstdint>
@@ -38,13 +39,6 @@ __device__ __forceinline__ unsigned symbol_cost(const uint32_t* row, int sym, bo
     const unsigned raw = value < 0 ? (unsigned)(-2 * value - 1) : (unsigned)(2 * (value - max_value));
     const unsigned n_bypass = raw ? (unsigned)(33 - __clz((int)raw)) >> 1 : 0u;      // 2-bit groups that hold raw
     return row[1 + max_value] + 2u * kOne * (n_bypass / 3u + 1u + n_bypass);
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 // partial[3 * workgroup + {0, 1, 2}] = the workgroup's Q16 bits, coded symbols, escapes

@@ -16,6 +16,7 @@
 // address or row length, or the picture's right edge, do not allow it) and the tile's weights are kept transposed, so the
 // gathers of the taps and the weight reads are LDS reads.  Wider windows gather from memory.  No atomics, no workspace.
 #include "common.hpp"
+#include "frame_host.hpp"
 #include "plane_math.hpp"
 
 #include <cstdint>
@@ -33,15 +34,10 @@ constexpr int TS = TW + 4;       // row stride of t in LDS (floats): rows of the
 constexpr int HR = 4;            // source rows a wave carries through one sweep over the taps (one weight load serves all)
 constexpr int MAX_TAPS = 64;
 
-template <typename T>
-struct alignas(16) Pix8 {        // 8 pixels of a model row: one 16-byte access in fp16, two in fp32
-    T v[8];
-};
 struct alignas(16) F4 {
     float v[4];
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 // a table's first index brought into [-MAX_TAPS, n - 1]: min(max(first + k, 0), n - 1) is the same for every k < taps, and
 // first + k cannot overflow whatever the table holds
 __device__ __forceinline__ int first_of(const int32_t* first, int i, int n) { return clampi(first[i], -MAX_TAPS, n - 1); }
@@ -211,18 +207,6 @@ __global__ __launch_bounds__(RB) void resize_kernel(const T* __restrict__ x, int
     }
 }
 
-template <typename T>
-void launch(bool vec, dim3 grid, hipStream_t st, const void* x, int Hp, int Wp, int H, int W, void* out, int HOp, int WOp, int HO,
-            int WO, const int32_t* first_h, const float* coef_h, int taps_h, const int32_t* first_v, const float* coef_v, int taps_v)
-{
-    if (vec)
-        resize_kernel<T, true><<<grid, RB, 0, st>>>((const T*)x, Hp, Wp, H, W, (T*)out, HOp, WOp, HO, WO, first_h, coef_h, taps_h,
-                                                    first_v, coef_v, taps_v);
-    else
-        resize_kernel<T, false><<<grid, RB, 0, st>>>((const T*)x, Hp, Wp, H, W, (T*)out, HOp, WOp, HO, WO, first_h, coef_h, taps_h,
-                                                     first_v, coef_v, taps_v);
-}
-
 }  // namespace
 
 extern "C" {
@@ -232,30 +216,28 @@ int dcvc_resize_frame(int dtype, const void* x_nchw, int Hp, int Wp, int H, int 
                       const float* coef_v, int taps_v, void* stream)
 {
     const char* who = "dcvc_resize_frame";
-    DCVC_REQUIRE(dtype == DCVC_F16 || dtype == DCVC_F32, "%s: bad dtype %d", who, dtype);
-    DCVC_REQUIRE(H > 0 && W > 0 && HO > 0 && WO > 0, "%s: bad size %d x %d -> %d x %d", who, H, W, HO, WO);
-    DCVC_REQUIRE(Hp >= H && Wp >= W, "%s: the source tensor (%d x %d) does not hold its valid region (%d x %d)", who, Hp, Wp, H, W);
+    if (int rc = dcvc::check_frame(who, "the source", dtype, x_nchw, Hp, Wp, H, W)) return rc;
+    DCVC_REQUIRE(HO > 0 && WO > 0, "%s: bad output size %d x %d", who, HO, WO);
     DCVC_REQUIRE(HOp >= HO && WOp >= WO, "%s: the output tensor (%d x %d) does not hold its valid region (%d x %d)", who, HOp,
                  WOp, HO, WO);
     DCVC_REQUIRE(taps_h >= 1 && taps_h <= MAX_TAPS && taps_v >= 1 && taps_v <= MAX_TAPS, "%s: taps %d / %d outside 1 .. %d", who,
                  taps_h, taps_v, MAX_TAPS);
-    DCVC_REQUIRE(x_nchw && out_nchw && first_h && coef_h && first_v && coef_v, "%s: null pointer", who);
-    const uintptr_t es = (uintptr_t)dcvc::elem_size(dtype);
-    DCVC_REQUIRE((uintptr_t)x_nchw % es == 0, "%s: the source is not aligned to its element size", who);
+    DCVC_REQUIRE(out_nchw && first_h && coef_h && first_v && coef_v, "%s: null pointer", who);
     DCVC_REQUIRE(((uintptr_t)out_nchw & 15) == 0 && WOp % 8 == 0,
                  "%s: the output tensor (%d x %d) must be 16-byte aligned and its width a multiple of 8", who, HOp, WOp);
     DCVC_REQUIRE((((uintptr_t)first_h | (uintptr_t)coef_h | (uintptr_t)first_v | (uintptr_t)coef_v) & 3) == 0,
                  "%s: a table is not 4-byte aligned", who);
-    const dim3 grid((unsigned)((WOp + TW - 1) / TW), (unsigned)((HOp + TH - 1) / TH), 3);
-    DCVC_REQUIRE(grid.y <= 65535u, "%s: output height %d above %d", who, HOp, 65535 * TH);
-    hipStream_t st = (hipStream_t)stream;
-    const bool vec = ((uintptr_t)x_nchw & 15) == 0 && (Wp * (int)es) % 16 == 0;
-    if (dtype == DCVC_F16)
-        launch<_Float16>(vec, grid, st, x_nchw, Hp, Wp, H, W, out_nchw, HOp, WOp, HO, WO, first_h, coef_h, taps_h, first_v, coef_v, taps_v);
-    else
-        launch<float>(vec, grid, st, x_nchw, Hp, Wp, H, W, out_nchw, HOp, WOp, HO, WO, first_h, coef_h, taps_h, first_v, coef_v, taps_v);
-    DCVC_LAUNCH_CHECK();
-    return 0;
+    dim3 grid;
+    if (int rc = dcvc::tile_grid(who, WOp, HOp, TW, TH, grid)) return rc;
+    const size_t es = dcvc::elem_size(dtype);
+    const bool vec = dcvc::vec_ok(16 / (int)es, es, Wp, x_nchw);
+    return dcvc::typed(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        dcvc::with_flag(vec, [&](auto v) {
+            resize_kernel<T, decltype(v)::value><<<grid, RB, 0, (hipStream_t)stream>>>(
+                (const T*)x_nchw, Hp, Wp, H, W, (T*)out_nchw, HOp, WOp, HO, WO, first_h, coef_h, taps_h, first_v, coef_v, taps_v);
+        });
+    });
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 //                       sum of (Wsum - 256) goes wave -> LDS -> ONE 64-bit integer vector atomic per workgroup.
 // No allocation and no synchronisation in any entry point.
 #include "common.hpp"
+#include "frame_host.hpp"
 #include "plane_math.hpp"
 
 #include <cstdint>
@@ -31,8 +32,6 @@ constexpr int TH = 32;           // blend: rows of a tile (TB / (TW / 8) threads
 constexpr int NB = 8;            // motion: blocks per workgroup (32 lanes each)
 constexpr int MAX_REFS = 4;
 constexpr float kScale = 1023.0f;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 __device__ __forceinline__ int quant10(float v)
 {
@@ -207,18 +206,6 @@ struct TfRefs {
     int base[MAX_REFS];          // B: 102 at distance 1, 77 at distance 2
 };
 
-template <typename T>
-struct alignas(16) Pix8 {        // 8 pixels of a model row: one 16-byte access in fp16, two in fp32
-    T v[8];
-};
-
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // VEC: cur and out are 16-byte aligned and the row length is a multiple of 16 bytes
 template <typename T, bool VEC>
 __global__ __launch_bounds__(TB) void tf_blend_kernel(const T* __restrict__ cur, TfRefs refs, int nref, int Hp, int Wp, int H, int W,
@@ -354,23 +341,16 @@ int64_t dcvc_tf_motion_ws_bytes(int H, int W)
 int dcvc_tf_pyramid(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, uint16_t* pyramid, void* stream)
 {
     const char* who = "dcvc_tf_pyramid";
-    DCVC_REQUIRE(dtype == DCVC_F16 || dtype == DCVC_F32, "%s: bad dtype %d", who, dtype);
-    DCVC_REQUIRE(H > 0 && W > 0 && Hp >= H && Wp >= W, "%s: the tensor (%d x %d) does not hold the picture (%d x %d)", who, Hp, Wp,
-                 H, W);
-    DCVC_REQUIRE(x_nchw && pyramid, "%s: null pointer", who);
-    DCVC_REQUIRE((uintptr_t)x_nchw % dcvc::elem_size(dtype) == 0 && ((uintptr_t)pyramid & 1) == 0,
-                 "%s: a pointer is not aligned to its element size", who);
-    DCVC_REQUIRE((int64_t)3 * Hp * Wp < ((int64_t)1 << 40) && (int64_t)H * W < ((int64_t)1 << 30), "%s: picture too large", who);
+    if (int rc = dcvc::check_frame(who, "x", dtype, x_nchw, Hp, Wp, H, W)) return rc;
+    DCVC_REQUIRE(pyramid && ((uintptr_t)pyramid & 1) == 0, "%s: the pyramid is null or not 2-byte aligned", who);
+    DCVC_REQUIRE((int64_t)H * W < ((int64_t)1 << 30), "%s: picture too large", who);
     const LevelDims d = level_dims(H, W);
     const dim3 grid((unsigned)((d.w[2] + 63) / 64), (unsigned)((d.h[2] + TB / 64 - 1) / (TB / 64)), 1);
     DCVC_REQUIRE(grid.y <= 65535u, "%s: height %d too large", who, H);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DCVC_F16)
-        tf_pyramid_kernel<_Float16><<<grid, TB, 0, st>>>((const _Float16*)x_nchw, Wp, H, W, pyramid);
-    else
-        tf_pyramid_kernel<float><<<grid, TB, 0, st>>>((const float*)x_nchw, Wp, H, W, pyramid);
-    DCVC_LAUNCH_CHECK();
-    return 0;
+    return dcvc::typed(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        tf_pyramid_kernel<T><<<grid, TB, 0, (hipStream_t)stream>>>((const T*)x_nchw, Wp, H, W, pyramid);
+    });
 }
 
 int dcvc_tf_motion(const uint16_t* cur_pyramid, const uint16_t* const* ref_pyramids, int nref, int H, int W, int16_t* mv,
@@ -406,21 +386,18 @@ int dcvc_tf_blend(int dtype, const void* cur_nchw, const void* const* refs_nchw,
                   int W, const int16_t* mv, const uint32_t* err, int level, void* out_nchw, uint64_t* weight_sum, void* stream)
 {
     const char* who = "dcvc_tf_blend";
-    DCVC_REQUIRE(dtype == DCVC_F16 || dtype == DCVC_F32, "%s: bad dtype %d", who, dtype);
-    DCVC_REQUIRE(H > 0 && W > 0 && Hp >= H && Wp >= W, "%s: the tensors (%d x %d) do not hold the picture (%d x %d)", who, Hp, Wp,
-                 H, W);
+    if (int rc = dcvc::check_frame(who, "the current frame", dtype, cur_nchw, Hp, Wp, H, W)) return rc;
+    if (int rc = dcvc::check_frame(who, "out", dtype, out_nchw, Hp, Wp, H, W)) return rc;
     DCVC_REQUIRE(level >= 1 && level <= 5, "%s: level %d outside 1 .. 5", who, level);
     DCVC_REQUIRE(nref >= 0 && nref <= MAX_REFS, "%s: %d references, at most %d are supported", who, nref, MAX_REFS);
-    DCVC_REQUIRE(cur_nchw && out_nchw && weight_sum && (nref == 0 || (refs_nchw && dists && mv && err)), "%s: null pointer", who);
-    DCVC_REQUIRE((int64_t)3 * Hp * Wp < ((int64_t)1 << 40) && (int64_t)H * W < ((int64_t)1 << 30), "%s: tensors too large", who);
-    const uintptr_t es = (uintptr_t)dcvc::elem_size(dtype);
+    DCVC_REQUIRE(weight_sum && (nref == 0 || (refs_nchw && dists && mv && err)), "%s: null pointer", who);
+    DCVC_REQUIRE((int64_t)H * W < ((int64_t)1 << 30), "%s: picture too large", who);
+    const size_t es = dcvc::elem_size(dtype);
     const uint64_t bytes = (uint64_t)3 * Hp * Wp * es;
-    DCVC_REQUIRE((uintptr_t)cur_nchw % es == 0 && (uintptr_t)out_nchw % es == 0, "%s: a tensor is not aligned to its element size", who);
     DCVC_REQUIRE(!overlaps(out_nchw, cur_nchw, bytes), "%s: out overlaps the current frame (neighbours are read)", who);
     TfRefs refs = {};
     for (int r = 0; r < nref; ++r) {
-        DCVC_REQUIRE(refs_nchw[r], "%s: null pointer", who);
-        DCVC_REQUIRE((uintptr_t)refs_nchw[r] % es == 0, "%s: a tensor is not aligned to its element size", who);
+        if (int rc = dcvc::check_frame(who, "a reference", dtype, refs_nchw[r], Hp, Wp, H, W)) return rc;
         DCVC_REQUIRE(!overlaps(out_nchw, refs_nchw[r], bytes), "%s: out overlaps reference %d (neighbours are read)", who, r);
         DCVC_REQUIRE(dists[r] == 1 || dists[r] == -1 || dists[r] == 2 || dists[r] == -2, "%s: distance %d is not +-1 or +-2", who,
                      dists[r]);
@@ -429,29 +406,18 @@ int dcvc_tf_blend(int dtype, const void* cur_nchw, const void* const* refs_nchw,
     }
     DCVC_REQUIRE(((uintptr_t)mv & 1) == 0 && ((uintptr_t)err & 3) == 0 && ((uintptr_t)weight_sum & 7) == 0,
                  "%s: mv, err or the weight sum is not aligned to its element size", who);
-    const dim3 grid((unsigned)((Wp + TW - 1) / TW), (unsigned)((Hp + TH - 1) / TH), 3);
-    DCVC_REQUIRE(grid.y <= 65535u, "%s: height %d above %d", who, Hp, 65535 * TH);
+    dim3 grid;
+    if (int rc = dcvc::tile_grid(who, Wp, Hp, TW, TH, grid)) return rc;
     const LevelDims d = level_dims(H, W);
-    const bool vec = (((uintptr_t)cur_nchw | (uintptr_t)out_nchw) & 15) == 0 && ((int64_t)Wp * (int64_t)es) % 16 == 0;
+    const bool vec = dcvc::vec_ok(16 / (int)es, es, Wp, cur_nchw, out_nchw);
     unsigned long long* total = reinterpret_cast<unsigned long long*>(weight_sum);
-    hipStream_t st = (hipStream_t)stream;
-#define TF_BLEND(T, V)                                                                                                        \
-    tf_blend_kernel<T, V><<<grid, TB, 0, st>>>((const T*)cur_nchw, refs, nref, Hp, Wp, H, W, mv, err, d.gh[0], d.gw[0], level, \
-                                                (T*)out_nchw, total)
-    if (dtype == DCVC_F16) {
-        if (vec)
-            TF_BLEND(_Float16, true);
-        else
-            TF_BLEND(_Float16, false);
-    } else {
-        if (vec)
-            TF_BLEND(float, true);
-        else
-            TF_BLEND(float, false);
-    }
-#undef TF_BLEND
-    DCVC_LAUNCH_CHECK();
-    return 0;
+    return dcvc::typed(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        dcvc::with_flag(vec, [&](auto v) {
+            tf_blend_kernel<T, decltype(v)::value><<<grid, TB, 0, (hipStream_t)stream>>>(
+                (const T*)cur_nchw, refs, nref, Hp, Wp, H, W, mv, err, d.gh[0], d.gw[0], level, (T*)out_nchw, total);
+        });
+    });
 }
 
 }  // extern "C"

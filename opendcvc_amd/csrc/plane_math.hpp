@@ -1,6 +1,7 @@
-// plane_math.hpp - storage-type load / store helpers of the elementwise kernels and the plane arithmetic of a
-// reconstruction [3][HP][WP] seen as YUV 4:2:0, shared by dcvc_elem.hip (frame_to_yuv420_kernel: the 8-bit planes) and
-// dcvc_metrics.hip (metric_planes_kernel: the same values before they are rounded / truncated).
+// plane_math.hpp - the device helpers the kernels share: storage-type load / store, clamps, the 8-pixel piece of a model
+// row, wave and workgroup sums, and the plane arithmetic of a reconstruction [3][HP][WP] seen as YUV 4:2:0, shared by
+// dcvc_pixfmt.hip (frame_to_yuv420_kernel: the 8-bit planes) and dcvc_metrics.hip (metric_planes_kernel: the same values
+// before they are rounded / truncated).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +33,38 @@ __device__ __forceinline__ float clampf(float v, float lo, float hi)
 {
     v = v < lo ? lo : v;
     return v > hi ? hi : v;
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+template <typename T>
+struct alignas(16) Pix8 {        // 8 pixels of a model row: one 16-byte access in fp16, two in fp32
+    T v[8];
+};
+
+// sum of an integer over the 64 lanes of a wave; every lane gets the result
+template <typename I>
+__device__ __forceinline__ I wave_sum(I v)
+{
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// sum over a workgroup of N threads in a fixed order (tree over the thread index, red[N] in LDS); every thread gets the
+// result
+template <int N, typename V>
+__device__ __forceinline__ V block_sum(V v, V* red)
+{
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = N / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const V r = red[0];
+    __syncthreads();     // (red is reused by the next sum)
+    return r;
 }
 
 // clamp(x * 255, 0, 255) of luma sample (y, xw): the product rounded to the storage type, as torch does

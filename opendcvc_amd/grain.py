@@ -108,41 +108,31 @@ class FilmGrain:
         self.device = torch.device(device)
         self._table = torch.zeros((TABLE_LINES, 2), dtype=torch.int64, device=self.device)
 
-    @staticmethod
-    def _frame(x):
-        if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 3:
-            raise ValueError(f"a [1, 3, Hp, Wp] frame is expected, got {tuple(x.shape)}")
-        return x.contiguous()
-
     def apply(self, x, size, params, t, out=None):
         """x with the grain of `params` for frame counter t on its size = (H, W) picture; elements outside it are copied.
         out: None (a new tensor) or a contiguous tensor like x, x itself included.  Enqueued on the current stream."""
         import torch
         from . import _lib
         from . import nn as L
-        x = self._frame(x)
+        x = L.frame(x)
         if out is None:
             out = torch.empty_like(x)
         elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous():
             raise ValueError("out must be a contiguous tensor of x's shape and type")
-        H, W = (int(v) for v in size)
-        _lib.check(_lib.lib().dcvc_grain_apply(L.dtype_code(x.dtype), L._p(x), x.shape[2], x.shape[3], H, W, L._p(out),
-                                               _c_params(params), int(t) & 0xFFFFFFFF,
-                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "dcvc_grain_apply")
+        _lib.check(_lib.lib().dcvc_grain_apply(*L.frame_args(x, size), L._p(out), _c_params(params), int(t) & 0xFFFFFFFF,
+                                               L._stream()), "dcvc_grain_apply")
         return out
 
     def stats(self, noisy, clean, size):
         """the table of every whole flat 16 x 16 block of the size = (H, W) picture: int64 numpy [12, 2], one read-back"""
-        import torch
         from . import _lib
         from . import nn as L
-        noisy, clean = self._frame(noisy), self._frame(clean)
+        noisy, clean = L.frame(noisy), L.frame(clean)
         if noisy.shape != clean.shape or noisy.dtype != clean.dtype:
             raise ValueError("noisy and clean must have one shape and type")
-        H, W = (int(v) for v in size)
-        _lib.check(_lib.lib().dcvc_grain_stats(L.dtype_code(clean.dtype), L._p(noisy), L._p(clean), clean.shape[2],
-                                               clean.shape[3], H, W, L._p(self._table),
-                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "dcvc_grain_stats")
+        code, _, Hp, Wp, H, W = L.frame_args(clean, size)
+        _lib.check(_lib.lib().dcvc_grain_stats(code, L._p(noisy), L._p(clean), Hp, Wp, H, W, L._p(self._table), L._stream()),
+                   "dcvc_grain_stats")
         return self._table.cpu().numpy()
 
     def estimate(self, noisy, clean, size, seed):

@@ -133,22 +133,18 @@ def rgb_distortion(x_hat, rgb, calc_ssim=False):
 def reconstruct_rgb(x_hat, height, width):
     """decoded [1,3,H',W'] YCbCr -> clamp(ycbcr2rgb * 255, 0, 255) of the height x width picture, [3,H,W] in x_hat's dtype
     (transforms.py:41-53, test_video.py:118-119)"""
-    import ctypes
     import torch
     from . import _lib
     from . import nn as L
     x = x_hat.contiguous()
-    _, _, Hp, Wp = x.shape
     out = torch.empty((3, height, width), dtype=x.dtype, device=x.device)
-    _lib.check(_lib.lib().dcvc_frame_to_rgb(L.dtype_code(x.dtype), L._p(x), Hp, Wp, height, width, L._p(out),
-                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "dcvc_frame_to_rgb")
+    _lib.check(_lib.lib().dcvc_frame_to_rgb(*L.frame_args(x, (height, width)), L._p(out), L._stream()), "dcvc_frame_to_rgb")
     return out
 
 
 def load_rgb_frame(rgb, dtype, pad_to=16):
     """uint8 device tensor [3,H,W] (RGB) -> padded YCbCr model input [1,3,H',W'] (one fused kernel; reference:
     np_image_to_tensor + rgb2ycbcr + the cast + replicate_pad, test_video.py:59-63,84-90,179)"""
-    import ctypes
     import torch
     from . import _lib
     from . import nn as L
@@ -156,7 +152,7 @@ def load_rgb_frame(rgb, dtype, pad_to=16):
     pr, pb = (-W) % pad_to, (-H) % pad_to
     out = torch.empty((1, 3, H + pb, W + pr), dtype=dtype, device=rgb.device)
     _lib.check(_lib.lib().dcvc_rgb_to_frame(L.dtype_code(dtype), L._p(rgb.contiguous()), H, W, pb, pr, L._p(out),
-                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "dcvc_rgb_to_frame")
+                                            L._stream()), "dcvc_rgb_to_frame")
     return out
 
 

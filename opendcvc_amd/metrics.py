@@ -52,7 +52,7 @@ class DeviceMetrics:
 
     # ------------------------------------------------------------------------------------------ enqueue
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return L._stream(self.device)
 
     def _slot_ptr(self, slot, offset=0):
         return ctypes.c_void_p(self._pinned.ptr + 8 * (slot * _SLOT + offset))
@@ -116,16 +116,14 @@ class DeviceMetrics:
         by the next call at the same size)"""
         if not x_hat.is_contiguous():
             raise ValueError("x_hat must be contiguous")
-        _, _, Hp, Wp = x_hat.shape
         key = ("yuv", height, width, x_hat.dtype)
         planes = self._planes.get(key)
         if planes is None:
             planes = self._planes[key] = (torch.empty((height, width), dtype=x_hat.dtype, device=self.device),
                                           torch.empty((height // 2, width // 2), dtype=x_hat.dtype, device=self.device),
                                           torch.empty((height // 2, width // 2), dtype=x_hat.dtype, device=self.device))
-        _lib.check(self._lib.dcvc_frame_to_yuv420_planes(L.dtype_code(x_hat.dtype), L._p(x_hat), Hp, Wp, height, width,
-                                                         L._p(planes[0]), L._p(planes[1]), L._p(planes[2]), self._stream()),
-                   "dcvc_frame_to_yuv420_planes")
+        _lib.check(self._lib.dcvc_frame_to_yuv420_planes(*L.frame_args(x_hat, (height, width)), L._p(planes[0]), L._p(planes[1]),
+                                                         L._p(planes[2]), self._stream()), "dcvc_frame_to_yuv420_planes")
         return planes
 
     def yuv420(self, x_hat, y, u, v, calc_ssim=False):
@@ -152,7 +150,6 @@ class DeviceMetrics:
         sub-LSB precision).  Enqueued on the current stream; the tensors are this object's buffers."""
         if not x_hat.is_contiguous():
             raise ValueError("x_hat must be contiguous")
-        _, _, Hp, Wp = x_hat.shape
         key = ("pix", height, width, fmt.chroma)
         planes = self._planes.get(key)
         if planes is None:
@@ -160,9 +157,9 @@ class DeviceMetrics:
             planes = self._planes[key] = (torch.empty((height, width), dtype=torch.float32, device=self.device),
                                           torch.empty((ch, cw), dtype=torch.float32, device=self.device),
                                           torch.empty((ch, cw), dtype=torch.float32, device=self.device))
-        _lib.check(self._lib.dcvc_frame_to_metric_planes(L.dtype_code(x_hat.dtype), fmt.chroma, fmt.max_val, L._p(x_hat), Hp, Wp,
-                                                         height, width, L._p(planes[0]), L._p(planes[1]), L._p(planes[2]),
-                                                         self._stream()), "dcvc_frame_to_metric_planes")
+        code, *frame = L.frame_args(x_hat, (height, width))
+        _lib.check(self._lib.dcvc_frame_to_metric_planes(code, fmt.chroma, fmt.max_val, *frame, L._p(planes[0]), L._p(planes[1]),
+                                                         L._p(planes[2]), self._stream()), "dcvc_frame_to_metric_planes")
         return planes
 
     def yuv(self, x_hat, planes, fmt, calc_ssim=False):
@@ -193,7 +190,6 @@ class DeviceMetrics:
         if not x_hat.is_contiguous():
             raise ValueError("x_hat must be contiguous")
         _, H, W = rgb.shape
-        _, _, Hp, Wp = x_hat.shape
         key = ("rgb", H, W, x_hat.dtype)
         rec = self._planes.get(key)
         if rec is None:
@@ -201,7 +197,7 @@ class DeviceMetrics:
         self._check_pair(rgb, rec)
         st = self._stream()
         tr, ts = L.dtype_code(x_hat.dtype), _type_code(rgb)
-        _lib.check(self._lib.dcvc_frame_to_rgb(tr, L._p(x_hat), Hp, Wp, H, W, L._p(rec), st), "dcvc_frame_to_rgb")
+        _lib.check(self._lib.dcvc_frame_to_rgb(*L.frame_args(x_hat, (H, W)), L._p(rec), st), "dcvc_frame_to_rgb")
         self._enqueue_sse(3, L._p(rgb), ts, L._p(rec), tr, 3 * H * W, st)
         levels = 0
         if calc_ssim:

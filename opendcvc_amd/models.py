@@ -393,8 +393,7 @@ class CompressionModel(tnn.Module):
     def _thres(self):
         return -1.0 if self.force_zero_thres is None else float(self.force_zero_thres)
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _stream = staticmethod(L._stream)
 
     def _pad_for_y(self, y):
         H, W, C = y.shape

@@ -29,12 +29,27 @@ def cpad(c, m=32):
     return (c + m - 1) // m * m
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _stream(device=None):
+    """torch's current stream (of `device`, default: the current device) as the C ABI takes it"""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def frame(x):
+    """x as a contiguous model frame [1, 3, Hp, Wp]"""
+    if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 3:
+        raise ValueError(f"a [1, 3, Hp, Wp] frame is expected, got {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def frame_args(x, size):
+    """(dtype code, pointer, Hp, Wp, H, W) of the frame x with the size = (H, W) picture at its top left: the leading
+    arguments of a picture-side entry.  That the picture lies in the frame is the library's check."""
+    H, W = size
+    return dtype_code(x.dtype), _p(x), x.shape[-2], x.shape[-1], int(H), int(W)
 
 
 def _host(a):

@@ -8,8 +8,6 @@ the unmodified reference model code take its accelerated branch on ROCm (INTEGRA
 Every function launches HIP kernels of libdcvc_amd.so on torch's current stream; there is no
 torch fallback.
 """
-import ctypes
-
 import torch
 
 from . import _lib
@@ -17,8 +15,7 @@ from . import nn as L
 from ._lib import DcvcError, check
 
 
-def _s():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_s = L._stream
 
 
 def _req(*ts):

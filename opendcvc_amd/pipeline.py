@@ -471,7 +471,6 @@ class EncodeDecodePipeline:
 def load_yuv420_frame(y, u, v, dtype, pad_to=16):
     """uint8 CUDA planes y [H,W], u/v [H/2,W/2] -> padded model input [1,3,H',W'] (one fused kernel;
     reference: get_src_frame + replicate_pad, test_video.py:74-91,150,179)."""
-    import ctypes
     import torch
     from . import _lib
     from . import nn as L
@@ -479,8 +478,7 @@ def load_yuv420_frame(y, u, v, dtype, pad_to=16):
     pr, pb = (-W) % pad_to, (-H) % pad_to
     out = torch.empty((1, 3, H + pb, W + pr), dtype=dtype, device=y.device)
     _lib.check(_lib.lib().dcvc_yuv420_to_frame(L.dtype_code(dtype), L._p(y.contiguous()), L._p(u.contiguous()),
-                                               L._p(v.contiguous()), H, W, pb, pr, L._p(out),
-                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                               L._p(v.contiguous()), H, W, pb, pr, L._p(out), L._stream()),
                "dcvc_yuv420_to_frame")
     return out
 
@@ -488,19 +486,15 @@ def load_yuv420_frame(y, u, v, dtype, pad_to=16):
 def store_yuv420_frame(x_hat, height, width, round_uv=False):
     """decoded [1,3,H',W'] -> uint8 CUDA planes (y, u, v) of the height x width picture
     (reference: yuv_444_to_420 + clamp*255 + uint8, test_video.py:307-311)."""
-    import ctypes
     import torch
     from . import _lib
     from . import nn as L
     x = x_hat.contiguous()
-    _, _, Hp, Wp = x.shape
     y = torch.empty((height, width), dtype=torch.uint8, device=x.device)
     u = torch.empty((height // 2, width // 2), dtype=torch.uint8, device=x.device)
     v = torch.empty_like(u)
-    _lib.check(_lib.lib().dcvc_frame_to_yuv420(L.dtype_code(x.dtype), L._p(x), Hp, Wp, height, width, int(round_uv),
-                                               L._p(y), L._p(u), L._p(v),
-                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-               "dcvc_frame_to_yuv420")
+    _lib.check(_lib.lib().dcvc_frame_to_yuv420(*L.frame_args(x, (height, width)), int(round_uv), L._p(y), L._p(u), L._p(v),
+                                               L._stream()), "dcvc_frame_to_yuv420")
     return y, u, v
 
 
@@ -591,7 +585,6 @@ def load_frame(planes, fmt, dtype, pad_to=16, height=None, width=None, strides=N
     YUVReader + ycbcr420_to_444 + this project's cast and replicate_pad).  planes: (y, u, v), or (y, uv) for semi-planar;
     uint8, or torch.uint16 / an int16 view above 8 bits.  strides=(y_stride, c_stride) in samples with height / width
     given reads pitched surfaces (flat or wider tensors) in place; by default the planes are tight [H, W] tensors."""
-    import ctypes
     import torch
     from . import _lib
     from . import nn as L
@@ -606,8 +599,7 @@ def load_frame(planes, fmt, dtype, pad_to=16, height=None, width=None, strides=N
     out = torch.empty((1, 3, height + pb, width + pr), dtype=dtype, device=planes[0].device)
     _lib.check(_lib.lib().dcvc_planes_to_frame(L.dtype_code(dtype), fmt.chroma, fmt.bit_depth, int(fmt.semi_planar),
                                                int(fmt.msb_aligned), *ptrs, ys, cs, height, width, pb, pr, L._p(out),
-                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-               "dcvc_planes_to_frame")
+                                               L._stream()), "dcvc_planes_to_frame")
     return out
 
 
@@ -615,19 +607,16 @@ def store_frame(x_hat, height, width, fmt):
     """decoded [1,3,H',W'] -> the device planes of the height x width picture in `fmt` ((y, u, v), or (y, uv) for
     semi-planar; uint8 / torch.uint16): crop, fp32, 4:2:0 chroma = 2x2 mean, clip(., 0, 1) * max_val, round to nearest
     even, clip (the reference family's ycbcr444_to_420 + YUVWriter), shifted up for msb-aligned formats."""
-    import ctypes
     import torch
     from . import _lib
     from . import nn as L
     fmt = PixelFormat.parse(fmt)
     x = x_hat.contiguous()
-    _, _, Hp, Wp = x.shape
     planes = [torch.empty(s, dtype=fmt.torch_dtype, device=x.device) for s in fmt.plane_shapes(height, width)]
     ptrs, ys, cs = _plane_args(planes, fmt, height, width, None)
-    _lib.check(_lib.lib().dcvc_frame_to_planes(L.dtype_code(x.dtype), fmt.chroma, fmt.bit_depth, int(fmt.semi_planar),
-                                               int(fmt.msb_aligned), L._p(x), Hp, Wp, height, width, *ptrs, ys, cs,
-                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-               "dcvc_frame_to_planes")
+    code, *frame = L.frame_args(x, (height, width))
+    _lib.check(_lib.lib().dcvc_frame_to_planes(code, fmt.chroma, fmt.bit_depth, int(fmt.semi_planar), int(fmt.msb_aligned),
+                                               *frame, *ptrs, ys, cs, L._stream()), "dcvc_frame_to_planes")
     return tuple(planes)
 
 

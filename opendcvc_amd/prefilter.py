@@ -32,11 +32,6 @@ def _refs_of(t, n_frames, radius):
     return [(t + d, d) for k in range(1, radius + 1) for d in (-k, k) if 0 <= t + d < n_frames]
 
 
-def _stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class TemporalFilter:
     """The filter on `device` at strength `level` (1 .. 5) with references up to `radius` (1, 2) frames away.
     filter() and motion() are stateless; push() / flush() run a sequence through a ring of 2 * radius + 1 source frames whose
@@ -58,9 +53,8 @@ class TemporalFilter:
     # ------------------------------------------------------------------------------ sizing
     @staticmethod
     def _frame(x):
-        if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 3:
-            raise ValueError(f"a [1, 3, Hp, Wp] frame is expected, got {tuple(x.shape)}")
-        return x.contiguous()
+        from . import nn as L
+        return L.frame(x)
 
     def _size(self, x, size):
         """buffers for frames like x with the picture size = (H, W)"""
@@ -96,8 +90,7 @@ class TemporalFilter:
     def _pyramid(self, x, size, slot):
         from . import _lib
         from . import nn as L
-        _lib.check(_lib.lib().dcvc_tf_pyramid(L.dtype_code(x.dtype), L._p(x), x.shape[-2], x.shape[-1], size[0], size[1],
-                                              L._p(self._pyr[slot]), _stream()), "dcvc_tf_pyramid")
+        _lib.check(_lib.lib().dcvc_tf_pyramid(*L.frame_args(x, size), L._p(self._pyr[slot]), L._stream()), "dcvc_tf_pyramid")
 
     def _motion(self, cur_slot, ref_slots, size):
         from . import _lib
@@ -105,16 +98,16 @@ class TemporalFilter:
         n = len(ref_slots)
         pyrs = (ctypes.c_void_p * n)(*[self._pyr[s].data_ptr() for s in ref_slots])
         _lib.check(_lib.lib().dcvc_tf_motion(L._p(self._pyr[cur_slot]), pyrs, n, size[0], size[1], L._p(self._mv), L._p(self._err),
-                                             L._p(self._ws), _stream()), "dcvc_tf_motion")
+                                             L._p(self._ws), L._stream()), "dcvc_tf_motion")
 
     def _blend(self, cur, refs, dists, size, out):
         from . import _lib
         from . import nn as L
         n = len(refs)
         ptrs = (ctypes.c_void_p * max(n, 1))(*[r.data_ptr() for r in refs])
-        _lib.check(_lib.lib().dcvc_tf_blend(L.dtype_code(cur.dtype), L._p(cur), ptrs, (ctypes.c_int * max(n, 1))(*dists), n,
-                                            cur.shape[-2], cur.shape[-1], size[0], size[1], L._p(self._mv), L._p(self._err),
-                                            self.level, L._p(out), L._p(self._total), _stream()), "dcvc_tf_blend")
+        code, cur_p, Hp, Wp, H, W = L.frame_args(cur, size)
+        _lib.check(_lib.lib().dcvc_tf_blend(code, cur_p, ptrs, (ctypes.c_int * max(n, 1))(*dists), n, Hp, Wp, H, W, L._p(self._mv),
+                                            L._p(self._err), self.level, L._p(out), L._p(self._total), L._stream()), "dcvc_tf_blend")
 
     def _check(self, cur, refs, dists, size):
         cur = self._frame(cur)

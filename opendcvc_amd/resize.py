@@ -6,8 +6,6 @@ codes a sequence at the size it arrives in.
 The table definition is the one Pillow's Image.resize and torch's interpolate(antialias=True) use: the filter's support is
 stretched by the scale when shrinking, every window is cut at the picture's border and its weights are normalised.
 """
-import ctypes
-
 import numpy as np
 
 FILTERS = ("bilinear", "bicubic", "lanczos3")          # the container's filter ids (bitstream.NAL_DISPLAY) are the positions
@@ -104,16 +102,12 @@ class Resampler:
             raise ValueError(f"filter {filter!r}: one of {', '.join(FILTERS)}")
         if (H, W) == (HO, WO):
             return x
-        if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 3:
-            raise ValueError(f"a [1, 3, Hp, Wp] frame is expected, got {tuple(x.shape)}")
-        x = x.contiguous()
-        Hp, Wp = x.shape[2], x.shape[3]
+        x = L.frame(x)
         first_h, coef_h, kh = self.tables(W, WO, filter)
         first_v, coef_v, kv = self.tables(H, HO, filter)
         out = torch.empty((1, 3, padded(HO, pad_to), padded(WO, pad_to)), dtype=x.dtype, device=x.device)
-        _lib.check(_lib.lib().dcvc_resize_frame(L.dtype_code(x.dtype), L._p(x), Hp, Wp, H, W, L._p(out), out.shape[2],
-                                                out.shape[3], HO, WO, L._p(first_h), L._p(coef_h), kh, L._p(first_v),
-                                                L._p(coef_v), kv, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+        _lib.check(_lib.lib().dcvc_resize_frame(*L.frame_args(x, (H, W)), L._p(out), out.shape[2], out.shape[3], HO, WO,
+                                                L._p(first_h), L._p(coef_h), kh, L._p(first_v), L._p(coef_v), kv, L._stream()),
                    "dcvc_resize_frame")
         return out
 

@@ -188,6 +188,41 @@ def test_round_trip_on_the_device(pairs, fg, corr, tdt, ndt):
     assert got is not None and got == want and got.corr == corr and got.seed == 5
 
 
+# ---------------------------------------------------------------------------------- where the frame lies
+def _placements(picture, fill=np.nan):
+    """a 45 x 77 picture in frames [3, 48, Wp], Wp 80 and 84, each once on a 16-byte boundary and once one element into a
+    larger allocation: [(host, device)] x 4.  Wp 80 on the boundary takes the wide accesses in fp16 and fp32, Wp 84 only
+    in fp32 (apply) or with either type (stats: four elements), the view never"""
+    out = []
+    for wp in (80, 84):
+        host = np.full((3, 48, wp), fill, picture.dtype)
+        host[:, :45, :77] = picture
+        for mis in (False, True):
+            dev = _to_device(host, mis)
+            assert mis or dev.data_ptr() % 16 == 0
+            out.append((host, dev))
+    return out
+
+
+@pytest.mark.parametrize("tdt,ndt", DTYPES)
+def test_apply_and_stats_do_not_depend_on_where_the_frame_lies(fg, tdt, ndt):
+    size = (45, 77)
+    p = GrainParams(808, 2, (24, 32, 40, 48, 56, 64, 72, 80), 36, 52)
+    clean = _blocky(size, ndt)[:, :45, :77]
+    pictures, tables = [], []
+    for host, dev in _placements(clean):
+        want = G.apply(host, size, p.seed, p.corr, p.scale_y, p.scale_cb, p.scale_cr, 3)
+        out = _to_device(np.full_like(host, 7.0), dev.data_ptr() % 16 != 0)
+        fg.apply(dev, size, p, 3, out=out)
+        got = out[0].cpu().numpy()
+        assert np.array_equal(_bits(got), _bits(want))
+        pictures.append(_bits(got[:, :45, :77]))
+        tables.append(fg.stats(out, dev, size))
+        assert np.array_equal(tables[-1], G.stats(want, host, size)) and tables[-1][8, 0] > 0
+    assert all(np.array_equal(a, pictures[0]) for a in pictures) and all(np.array_equal(t, tables[0]) for t in tables)
+    assert (pictures[0] != _bits(clean)).mean() > 0.5
+
+
 # ---------------------------------------------------------------------------------- end to end
 H, W, N, CODED = 64, 96, 8, (48, 64)
 PARAMS = GrainParams(1001, 1, (20, 24, 28, 32, 36, 40, 44, 48), 16, 12)

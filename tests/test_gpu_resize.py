@@ -114,6 +114,30 @@ def test_out_of_range_first_values_are_clamped(sources, size_in, size_out, tdt, 
     assert rc == 0 and np.isfinite(got).all() and np.array_equal(_bits(got), _bits(want))
 
 
+@pytest.mark.parametrize("tdt,ndt", DTYPES)
+def test_kernel_does_not_depend_on_where_the_source_lies(tdt, ndt):
+    """a 45 x 77 picture in source frames [3, 48, Wp], Wp 80 and 84, each once on a 16-byte boundary and once one element
+    into a larger allocation: Wp 80 on the boundary is staged with wide accesses in fp16 and fp32, Wp 84 only in fp32, the
+    view never"""
+    size_in, size_out = (45, 77), (30, 52)
+    picture = np.random.default_rng(4577).random((3, 45, 77), dtype=np.float32).astype(ndt)
+    th, tv = filter_taps("bicubic", 77, 52), filter_taps("bicubic", 45, 30)
+    got = []
+    for wp in (80, 84):
+        host = np.full((3, 48, wp), np.nan, ndt)
+        host[:, :45, :77] = picture
+        want = R.resize_tables_ref(host, size_in, th, tv, (32, 64))
+        for mis in (False, True):
+            flat = torch.empty(host.size + 8, dtype=tdt, device="cuda")
+            dev = flat[int(mis):int(mis) + host.size].view(1, 3, 48, wp)
+            dev.copy_(torch.from_numpy(host)[None])
+            assert dev.data_ptr() % 16 == int(mis) * host.itemsize and dev.is_contiguous()
+            rc, out = _launch(dev, size_in, size_out, th, tv)
+            got.append(out[0].cpu().numpy())
+            assert rc == 0 and np.isfinite(got[-1]).all() and np.array_equal(_bits(got[-1]), _bits(want))
+    assert all(np.array_equal(_bits(g), _bits(got[0])) for g in got)
+
+
 def test_refused_call_leaves_the_output_untouched(sources):
     size_in, size_out = (72, 120), (48, 80)
     _, dev = sources(size_in, np.float16)

@@ -156,6 +156,34 @@ def test_a_cut_is_a_bit_copy(filters, tdt, ndt):
     assert np.array_equal(_bits(got), _bits(R.filter_frame(pics[0], pics[1:], [-1, 1, -2, 2], size, 3)[0]))
 
 
+@pytest.mark.parametrize("tdt,ndt", DTYPES)
+def test_blend_does_not_depend_on_where_the_frames_lie(tex, filters, tdt, ndt):
+    """a 45 x 77 picture in frames [3, 48, Wp], Wp 80 and 84, each once on a 16-byte boundary and once one element into a
+    larger allocation (the current frame, the references and out alike): Wp 80 on the boundary takes the wide accesses in
+    fp16 and fp32, Wp 84 only in fp32, the view never"""
+    size, dists, rng = (45, 77), [-1, 1], np.random.default_rng(4577)
+    pics = [(R.shift(tex, *SHIFTS[d], 45, 77) * 1.1 - 0.05 + rng.standard_normal((3, 45, 77)) * (2.0 / 255.0)).astype(ndt)
+            for d in [0] + dists]
+    tf = filters(3)
+    got, totals = [], []
+    for wp in (80, 84):
+        hosts = [np.full((3, 48, wp), np.nan, ndt) for _ in pics]
+        for f, pic in zip(hosts, pics):
+            f[:, :45, :77] = pic
+        want, want_total, _ = R.filter_frame(hosts[0], hosts[1:], dists, size, 3)
+        for mis in (False, True):
+            dev = [_to_device(f, mis) for f in hosts]
+            out = _to_device(np.full_like(hosts[0], 7.0), mis)
+            assert mis or all(t.data_ptr() % 16 == 0 for t in dev + [out])
+            tf.reset()
+            tf.filter(dev[0], dev[1:], dists, size, out=out)
+            totals.append(tf.weight_sum())
+            got.append(out[0].cpu().numpy())
+            assert np.array_equal(_bits(got[-1]), _bits(want)) and totals[-1] == want_total > 0
+    assert all(np.array_equal(_bits(g[:, :45, :77]), _bits(got[0][:, :45, :77])) for g in got) and len(set(totals)) == 1
+    assert (_bits(got[0][:, :45, :77]) != _bits(pics[0])).mean() > 0.5
+
+
 def test_refused_calls_leave_out_untouched(frames, filters):
     _, dev, _ = frames((70, 118), np.float16)
     tf = TemporalFilter("cuda:0", 3, 2)
@@ -186,7 +214,7 @@ def test_refused_calls_leave_out_untouched(frames, filters):
     assert bool((keep == 7.0).all())
     L, p = _lib.lib(), lambda t: t.data_ptr()
     assert L.dcvc_tf_blend(0, p(dev[0]), None, None, 0, 80, 128, 81, 118, None, None, 3, p(keep), p(tf._total), None) < 0
-    assert b"do not hold the picture" in L.dcvc_last_error()
+    assert b"does not hold the picture" in L.dcvc_last_error()
     assert L.dcvc_tf_pyramid(5, p(dev[0]), 80, 128, 70, 118, p(tf._pyr), None) < 0
     torch.cuda.synchronize()
     assert bool((keep == 7.0).all())
