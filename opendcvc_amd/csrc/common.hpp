@@ -1,11 +1,14 @@
 // common.hpp - error reporting and small host helpers shared by the translation units of
-// libdcvc_amd.so.
+// libdcvc_amd.so:
+//   DCVC_HIP / DCVC_REQUIRE / DCVC_LAUNCH_CHECK   return E_HIP / E_ARG with the error text set
+//   typed / with_flag                             run one launch expression for an entry's storage type and for a compile-time switch
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "dcvc_amd.h"
 
@@ -47,3 +50,38 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
             return dcvc::E_HIP;                                                           \
         }                                                                                 \
     } while (0)
+
+#ifdef __HIPCC__   // (the host-compiler translation units launch nothing and need not know _Float16)
+namespace dcvc {
+
+template <int V>
+using IC = std::integral_constant<int, V>;
+
+// launch(T{}) with T the storage type of `dtype`, then the launch check: return typed(dtype, [&](auto tag) { ... });
+template <typename F>
+int typed(int dtype, F&& launch)
+{
+    if (dtype == DCVC_F16)
+        launch(_Float16{});
+    else if (dtype == DCVC_F32)
+        launch(float{});
+    else {
+        set_error("bad dtype %d", dtype);
+        return E_ARG;
+    }
+    DCVC_LAUNCH_CHECK();
+    return 0;
+}
+
+// f(std::true_type{}) or f(std::false_type{}): decltype(flag)::value is a template argument
+template <typename F>
+void with_flag(bool flag, F&& f)
+{
+    if (flag)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+
+}  // namespace dcvc
+#endif

@@ -1,45 +1,15 @@
 // frame_host.hpp - the host scaffolding every picture-side entry shares (host only: no device code).  The object is a model
-// frame [3][Hp][Wp] of _Float16 or float whose top-left H x W is the picture:
-//   typed / with_flag   run one launch expression for the entry's storage type and for a compile-time switch
+// frame [3][Hp][Wp] of _Float16 or float whose top-left H x W is the picture (typed / with_flag, the dispatch on the storage
+// type and on a compile-time switch, are common.hpp's):
 //   check_frame         the argument check of one frame, one wording; an entry keeps only the checks that are its own
 //   vec_ok              may a launch use accesses of `elems` elements
 //   tile_grid           the grid of a launch with a workgroup per TW x TH tile of each of the three planes
 #pragma once
 #include <cstdint>
-#include <type_traits>
 
 #include "common.hpp"
 
 namespace dcvc {
-
-template <int V>
-using IC = std::integral_constant<int, V>;
-
-// launch(T{}) with T the storage type of `dtype`, then the launch check: return typed(dtype, [&](auto tag) { ... });
-template <typename F>
-int typed(int dtype, F&& launch)
-{
-    if (dtype == DCVC_F16)
-        launch(_Float16{});
-    else if (dtype == DCVC_F32)
-        launch(float{});
-    else {
-        set_error("bad dtype %d", dtype);
-        return E_ARG;
-    }
-    DCVC_LAUNCH_CHECK();
-    return 0;
-}
-
-// f(std::true_type{}) or f(std::false_type{}): decltype(flag)::value is a template argument
-template <typename F>
-void with_flag(bool flag, F&& f)
-{
-    if (flag)
-        f(std::true_type{});
-    else
-        f(std::false_type{});
-}
 
 // the frame `what` of entry `who`; no device is touched
 inline int check_frame(const char* who, const char* what, int dtype, const void* p, int Hp, int Wp, int H, int W)

@@ -258,7 +258,7 @@ class WholeArrayFrame(_Frame):
         m, lib = self.m, _lib.lib()
         n = (C // groups) * H * W
         idx = torch.empty(n, dtype=torch.uint8, device=scales.device)
-        check(lib.dcvc_prior_dec_index(L.dtype_code(scales.dtype), groups, unit, L._p(scales), scales.stride(1),
+        check(lib.dcvc_prior_dec_index(L.dtype_code(scales.dtype), groups, unit, *L.map_args(scales),
                                        H, W, C, m._thres(), L._p(idx), m._stream()), "prior_dec_index")
         buf = self._pinned(unit, "_idx", n)
         check(lib.dcvc_memcpy_d2h(ctypes.c_void_p(buf.ptr), L._p(idx), n, m._stream()), "d2h")
@@ -272,8 +272,8 @@ class WholeArrayFrame(_Frame):
         m, lib = self.m, _lib.lib()
         sym = torch.empty(st.n, dtype=torch.int8, device=yhat.device)
         check(lib.dcvc_memcpy_h2d(L._p(sym), ctypes.c_void_p(st.sym.ptr), st.n, m._stream()), "h2d")
-        check(lib.dcvc_prior_dec_restore(L.dtype_code(means.dtype), groups, unit, L._p(sym), L._p(means), means.stride(1),
-                                         H, W, C, L._p(yhat), yhat.stride(1), L._p(out), out.stride(1), m._stream()),
+        check(lib.dcvc_prior_dec_restore(L.dtype_code(means.dtype), groups, unit, L._p(sym), *L.map_args(means),
+                                         H, W, C, *L.map_args(yhat), *L.map_args(out), m._stream()),
               "prior_dec_restore")
 
 
@@ -288,7 +288,7 @@ class CompactFrame(_Frame):
         idx = torch.empty(n, dtype=torch.uint8, device=scales.device)
         ws = torch.empty(int(lib.dcvc_prior_dec_compact_ws_bytes(H, W, C, groups)), dtype=torch.uint8, device=scales.device)
         buf, cnt = self._pinned(unit, "_cidx", cap), self._pinned(unit, "_ccnt", 16)
-        check(lib.dcvc_prior_dec_index_compact(L.dtype_code(scales.dtype), groups, unit, L._p(scales), scales.stride(1),
+        check(lib.dcvc_prior_dec_index_compact(L.dtype_code(scales.dtype), groups, unit, *L.map_args(scales),
                                                H, W, C, m._thres(), L._p(idx), L._p(ws), ctypes.c_void_p(buf.ptr),
                                                ctypes.c_void_p(cnt.ptr), m._stream()), "prior_dec_index_compact")
         return Step(n, cap, idx, ws, buf, cnt, self._pinned(unit, "_csym", cap))
@@ -305,8 +305,8 @@ class CompactFrame(_Frame):
 
     def restore(self, st, groups, unit, means, yhat, H, W, C, out):
         check(_lib.lib().dcvc_prior_dec_restore_compact(
-            L.dtype_code(means.dtype), groups, unit, ctypes.c_void_p(st.sym.ptr), L._p(st.idx), L._p(st.ws), L._p(means),
-            means.stride(1), H, W, C, L._p(yhat), yhat.stride(1), L._p(out), out.stride(1), self.m._stream()),
+            L.dtype_code(means.dtype), groups, unit, ctypes.c_void_p(st.sym.ptr), L._p(st.idx), L._p(st.ws),
+            *L.map_args(means), H, W, C, *L.map_args(yhat), *L.map_args(out), self.m._stream()),
             "prior_dec_restore_compact")
 
 
@@ -363,7 +363,7 @@ class ChunkedDeviceFrame(_Frame):
         cidx = torch.empty(cap, dtype=torch.uint8, device=dev)
         cnt = torch.empty(4, dtype=torch.int32, device=dev)
         dsym = torch.empty(cap, dtype=torch.int8, device=dev)
-        check(lib.dcvc_prior_dec_index_compact_dev(L.dtype_code(scales.dtype), groups, unit, L._p(scales), scales.stride(1),
+        check(lib.dcvc_prior_dec_index_compact_dev(L.dtype_code(scales.dtype), groups, unit, *L.map_args(scales),
                                                    H, W, C, m._thres(), L._p(idx), L._p(ws), L._p(cidx), L._p(cnt),
                                                    m._stream()), "prior_dec_index_compact_dev")
         coder = m._device_coder()
@@ -378,8 +378,8 @@ class ChunkedDeviceFrame(_Frame):
 
     def restore(self, st, groups, unit, means, yhat, H, W, C, out):
         check(_lib.lib().dcvc_prior_dec_restore_compact_dev(
-            L.dtype_code(means.dtype), groups, unit, L._p(st.sym), L._p(st.idx), L._p(st.ws), L._p(means),
-            means.stride(1), H, W, C, L._p(yhat), yhat.stride(1), L._p(out), out.stride(1), self.m._stream()),
+            L.dtype_code(means.dtype), groups, unit, L._p(st.sym), L._p(st.idx), L._p(st.ws), *L.map_args(means),
+            H, W, C, *L.map_args(yhat), *L.map_args(out), self.m._stream()),
             "prior_dec_restore_compact_dev")
 
     def close(self):

@@ -460,15 +460,15 @@ class CompressionModel(tnn.Module):
         return handoff.open_frame(self, bit_stream, sps, units, prefix, chunked, DEC_COMPACT)
 
     def _prior_enc_step(self, groups, step, q_mode, y, qsrc, scales, means, yhat, packed):
-        H, W, C, ldy = L._geom(y)
+        H, W, C, _ = L._geom(y)
         check(_lib.lib().dcvc_prior_enc_step(
-            L.dtype_code(y.dtype), groups, step, q_mode, L._p(y), ldy, L._p(qsrc), qsrc.stride(1), L._p(scales),
-            scales.stride(1), L._p(means), means.stride(1), H, W, C, self._thres(), L._p(yhat), yhat.stride(1),
-            L._p(yhat), yhat.stride(1), L._p(packed), self._stream()), "prior_enc_step")
+            L.dtype_code(y.dtype), groups, step, q_mode, *L.map_args(y), *L.map_args(qsrc), *L.map_args(scales),
+            *L.map_args(means), H, W, C, self._thres(), *L.map_args(yhat), *L.map_args(yhat), L._p(packed), self._stream()),
+            "prior_enc_step")
 
     def _prior_finish(self, q_mode, yhat, qsrc):
-        H, W, C, ld = L._geom(yhat)
-        check(_lib.lib().dcvc_prior_finish(L.dtype_code(yhat.dtype), q_mode, L._p(yhat), ld, L._p(qsrc), qsrc.stride(1),
+        H, W, C, _ = L._geom(yhat)
+        check(_lib.lib().dcvc_prior_finish(L.dtype_code(yhat.dtype), q_mode, *L.map_args(yhat), *L.map_args(qsrc),
                                            H, W, C, self._stream()), "prior_finish")
 
 

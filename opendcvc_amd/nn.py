@@ -69,6 +69,12 @@ def _geom(x):
     return x.shape[0], x.shape[1], x.shape[2], x.stride(1)
 
 
+def map_args(x):
+    """(pointer, ld) of the HWC tensor or channel-slice view x: one operand of a latent-side entry (the counterpart of
+    frame_args).  That ld holds the entry's channels is the library's check."""
+    return _p(x), _geom(x)[3]
+
+
 def _io(x0, x1, out, out_shape, dtype):
     """The source and output arguments of a forward call: ((x0, ld0, c0, x1, ld1, c1, H, W), out, ldo) of the concat
     sources x0, x1 (or None) and of `out`, allocated here if None.  out_shape(H, W): the HWC shape the layer writes."""

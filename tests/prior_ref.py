@@ -1,4 +1,4 @@
-"""prior_ref.py - CPU restatement of the entropy-model glue kernels of dcvc_elem.hip (TEST INFRASTRUCTURE ONLY).
+"""prior_ref.py - CPU restatement of the entropy-model glue kernels of dcvc_prior.hip (TEST INFRASTRUCTURE ONLY).
 
 One function per C ABI entry point: dcvc_prior_enc_step, dcvc_prior_dec_index, dcvc_prior_dec_restore, dcvc_prior_finish,
 dcvc_round_z and dcvc_z_from_int8.  Tensors are HWC numpy arrays in the storage type (np.float32 or np.float16); an input
@@ -9,7 +9,7 @@ order of the collapsed [H, W, C / n_groups] tensor.
 Built from the oracle's own pieces (masks_2x / masks_4x, process_with_mask, scale_to_index through CodecBase._indexes,
 sigmoid, the collapse of compress_prior_2x / _4x and the CHW packing of CodecBase.pack_y), not from the kernels: in fp32 it
 is the oracle's arithmetic by construction.  In fp16 it rounds to fp16 exactly where the kernels store and nowhere else
-(dcvc_elem.hip, prior_enc_kernel):
+(dcvc_prior.hip, prior_enc_kernel):
   - inputs are loaded from fp16 (exact in fp32);
   - the quantisation step qe, yq = y * qe and v = rint(yq - m) are fp32;
   - y_hat of the step = half(v + m);  after step 0 the running sum is half(prev + y_hat);

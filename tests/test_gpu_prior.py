@@ -1,5 +1,5 @@
-"""The entropy-model glue kernels (dcvc_elem.hip: the checkerboard prior steps, the decoder's index build and restore, the
-compacted decoder hand-off, finish, the z quantiser) called through the C ABI and compared BIT FOR BIT with the CPU
+"""The entropy-model glue kernels (dcvc_prior.hip: the checkerboard prior steps, the decoder's index build and restore, the
+compacted decoder hand-off, finish; dcvc_elem.hip: the z quantiser) called through the C ABI and compared BIT FOR BIT with the CPU
 restatement tests/prior_ref.py, in fp32 and in fp16.  The arithmetic is elementwise and the restatement rounds where the
 kernels store, so no tolerance is needed in either storage type.
 
@@ -350,3 +350,97 @@ def test_round_z_and_z_from_int8(dname):
         torch.cuda.synchronize()
         assert np.array_equal(_bits(ov.cpu().numpy()), _bits(R.z_from_int8(want8, H, W, C, dt_n)))
         assert guards_intact(out, 1, C)
+
+
+# ------------------------------------------------------------------ placement: pinned host memory or device memory
+# (n_groups, H, W, C / n_groups): HW on and off the 16-byte path, an odd n16, both group counts
+PLACEMENT_CASES = [(2, 3, 5, 5), (4, 1, 17, 5), (2, 4, 4, 64), (4, 9, 13, 64)]
+
+
+@pytest.mark.parametrize("dname", list(DTYPES))
+@pytest.mark.parametrize("n_groups,H,W,Cg", PLACEMENT_CASES)
+def test_compacted_hand_off_in_device_memory_equals_the_pinned_one(dname, n_groups, H, W, Cg):
+    """dcvc_prior_dec_index_compact_dev (kept indexes and their count into DEVICE memory) followed by
+    dcvc_prior_dec_restore_compact_dev (compacted symbols read from device memory, no gather) against the pinned pair, at every
+    step: same indexes, count, index array and y_hat bit for bit, and nothing written behind what each call owns."""
+    from opendcvc_amd import entropy
+    dt_t, dt_n = DTYPES[dname]
+    lib = _lib().lib()
+    dt = 1 if dt_n == np.float32 else 0
+    C, thres, st = Cg * n_groups, 0.12, _stream()
+    n = Cg * H * W
+    cap = (n + 15) // 16 * 16
+    rng = np.random.default_rng(100 * H + W + Cg + n_groups)
+    draw = lambda f: torch.from_numpy(f((H, W, C)).astype(np.float32)).to(dt_t).cuda()
+    ws_bytes = int(lib.dcvc_prior_dec_compact_ws_bytes(H, W, C, n_groups))
+    for step in range(n_groups):
+        what = "%s step %d" % (dname, step)
+        scales = draw(lambda s: np.exp(rng.normal(-2.4, 1.0, s)))
+        means, prev = draw(lambda s: rng.normal(0, 2, s)), draw(lambda s: rng.normal(0, 2, s))
+        # ---- index: pinned, then device
+        idx_p, idx_d = (torch.full((n,), 9, dtype=torch.uint8, device="cuda") for _ in range(2))
+        ws_p, ws_d = (torch.zeros(ws_bytes, dtype=torch.uint8, device="cuda") for _ in range(2))
+        hidx, hcnt, hsym = entropy.PinnedBuffer(cap), entropy.PinnedBuffer(16), entropy.PinnedBuffer(cap)
+        hidx.u8[:] = GUARD_IDX
+        _check(lib.dcvc_prior_dec_index_compact(dt, n_groups, step, _p(scales), scales.stride(1), H, W, C, thres, _p(idx_p),
+                                                _p(ws_p), ctypes.c_void_p(hidx.ptr), ctypes.c_void_p(hcnt.ptr), st), "index_compact")
+        cidx = torch.full((cap + 16,), GUARD_IDX, dtype=torch.uint8, device="cuda")
+        cnt = torch.full((4,), 0x6E6E6E6E, dtype=torch.int32, device="cuda")
+        _check(lib.dcvc_prior_dec_index_compact_dev(dt, n_groups, step, _p(scales), scales.stride(1), H, W, C, thres, _p(idx_d),
+                                                    _p(ws_d), _p(cidx), _p(cnt), st), "index_compact_dev")
+        torch.cuda.synchronize()
+        count = int(hcnt.view(np.int32, 1)[0])
+        got_cnt, got_cidx = cnt.cpu().numpy(), cidx.cpu().numpy()
+        assert 0 < count < n, what + ": the case keeps some positions, not all"
+        assert got_cnt[0] == count and np.all(got_cnt[1:] == 0x6E6E6E6E), what + ": count in device memory"
+        assert np.array_equal(got_cidx[:count], hidx.u8[:count]), what + ": compacted indexes in device memory"
+        assert np.all(got_cidx[count:] == GUARD_IDX), what + ": written past the compacted indexes"
+        assert np.array_equal(idx_d.cpu().numpy(), idx_p.cpu().numpy()), what + ": index array"
+        # ---- restore: the same compacted symbols from pinned memory (gathered) and from device memory
+        csym = rng.integers(-128, 128, count).astype(np.int8)
+        hsym.u8[:] = 0x55
+        hsym.view(np.int8, cap)[:count] = csym
+        dsym = torch.full((cap,), 0x55, dtype=torch.int8)
+        dsym[:count] = torch.from_numpy(csym)
+        dsym = dsym.cuda()
+        bufs = [torch.full((H, W, C + 5), GUARD_Y, dtype=dt_t, device="cuda") for _ in range(2)]
+        out_p, out_d = bufs[0][:, :, 2:2 + C], bufs[1][:, :, 2:2 + C]
+        _check(lib.dcvc_prior_dec_restore_compact(dt, n_groups, step, ctypes.c_void_p(hsym.ptr), _p(idx_p), _p(ws_p), _p(means),
+                                                  means.stride(1), H, W, C, _p(prev) if step else None, prev.stride(1),
+                                                  _p(out_p), out_p.stride(1), st), "restore_compact")
+        _check(lib.dcvc_prior_dec_restore_compact_dev(dt, n_groups, step, _p(dsym), _p(idx_d), _p(ws_d), _p(means),
+                                                      means.stride(1), H, W, C, _p(prev) if step else None, prev.stride(1),
+                                                      _p(out_d), out_d.stride(1), st), "restore_compact_dev")
+        torch.cuda.synchronize()
+        assert np.array_equal(_bits(out_d.cpu().numpy()), _bits(out_p.cpu().numpy())), what + ": restore from device symbols"
+        assert guards_intact(bufs[0], 2, C) and guards_intact(bufs[1], 2, C), what + ": restore guard channels"
+
+
+@pytest.mark.parametrize("parts,n", [(1, 1), (4, 777), (2, 5000)])
+def test_compact_symbols_in_device_memory_equals_the_pinned_one(parts, n):
+    """dcvc_compact_symbols_dev against dcvc_compact_symbols: the kept symbols of every part in order and the counts, in device
+    memory as in pinned memory, nothing else touched."""
+    from opendcvc_amd import entropy
+    lib = _lib().lib()
+    st = _stream()
+    rng = np.random.default_rng(parts * 1000 + n)
+    a = rng.integers(-32768, 32767, (parts, n), dtype=np.int16)
+    skip = rng.random((parts, n)) < 0.7
+    skip[:, 0] = False
+    a = np.where(skip, (a & ~0xFF) | 0xFF, np.where((a & 0xFF) == 0xFF, a & ~1, a)).astype(np.int16)
+    dev = torch.from_numpy(a).cuda()
+    out, cnt = entropy.PinnedBuffer(parts * n * 2), entropy.PinnedBuffer(4 * parts)
+    out.u8[:] = 0x7E
+    ws = torch.zeros(256 * parts, dtype=torch.int32, device="cuda")
+    _check(lib.dcvc_compact_symbols(_p(dev), n, parts, ctypes.c_void_p(out.ptr), ctypes.c_void_p(cnt.ptr), _p(ws), st), "compact")
+    dout = torch.full((parts * n + 8,), GUARD_PACKED, dtype=torch.int16, device="cuda")
+    dcnt = torch.full((parts + 2,), 0x6E6E6E6E, dtype=torch.int32, device="cuda")
+    ws_d = torch.zeros(256 * parts, dtype=torch.int32, device="cuda")
+    _check(lib.dcvc_compact_symbols_dev(_p(dev), n, parts, _p(dout), _p(dcnt), _p(ws_d), st), "compact_dev")
+    torch.cuda.synchronize()
+    want, kept = out.view(np.int16, parts * n), cnt.view(np.int32, parts)
+    got, got_cnt = dout.cpu().numpy(), dcnt.cpu().numpy()
+    assert np.array_equal(kept, (~skip).sum(axis=1))
+    assert np.array_equal(got_cnt[:parts], kept) and np.all(got_cnt[parts:] == 0x6E6E6E6E)
+    assert np.array_equal(got[:parts * n], want)     # (kept symbols, then the sentinel of either buffer: 0x7E7E)
+    assert np.all(got[parts * n:] == GUARD_PACKED)
