@@ -538,6 +538,29 @@ int dcvc_tf_motion(const uint16_t* cur_pyramid, const uint16_t* const* ref_pyram
  * frame or a reference (neighbours are read); mv, err or weight_sum misaligned. */
 int dcvc_tf_blend(int dtype, const void* cur_nchw, const void* const* refs_nchw, const int* dists, int nref, int Hp, int Wp, int H,
                   int W, const int16_t* mv, const uint32_t* err, int level, void* out_nchw, uint64_t* weight_sum, void* stream);
+/* The level chosen from the picture (docs/temporal_filter.md, "Choosing the level from the picture"): one value per 8 x 8
+ * block in up to three tables - the Laplacian sum of the current Q0 (S >> 2) and the level-0 SADs of the references passed
+ * with distance +-1 (at most two), all clipped to 4095 - each table's lower quartile of its positive values (0 where fewer
+ * than an eighth are positive), N the minimum, and the level rule.  cur_pyramid: dcvc_tf_pyramid's; err / dists: those
+ * given to dcvc_tf_motion / dcvc_tf_blend (host array dists); nref 0 .. 4 - with none, or none at distance +-1, only the
+ * spatial table is formed.  ws: dcvc_tf_noise_ws_bytes() bytes of device memory (three 4096-bin uint32 histograms, cleared
+ * by the call).  result (device memory, 4 x int32): {level 0 .. 5, N, the smallest temporal figure or -1, the spatial
+ * figure}.  totals (device memory, 8 x int64, 8-byte aligned) or NULL: totals[level] += 1, totals[6] += N, totals[7] += 1;
+ * the caller zeroes it.  A memset and two launches on the stream; integer atomics only: independent of order.
+ * Further argument errors: nref outside 0 .. 4; a distance that is not +-1 / +-2. */
+int64_t dcvc_tf_noise_ws_bytes(void);
+/* A developer's knob, not for callers: at most n (1 .. 65535) workgroups share the tiles of dcvc_tf_noise's spatial pass from
+ * now on (512 as built; the result does not depend on it); any other n changes nothing.  Returns the count before the call. */
+int dcvc_tf_noise_workgroups(int n);
+int dcvc_tf_noise(const uint16_t* cur_pyramid, const uint32_t* err, const int* dists, int nref, int H, int W, void* ws,
+                  int32_t* result, int64_t* totals, void* stream);
+/* dcvc_tf_blend with its level in device memory (result of dcvc_tf_noise): the kernel reads the word once.  Level 0 gives
+ * every block the weight 0: the bits of the current picture and its replicate pad, nothing added to weight_sum.  A word
+ * outside 0 .. 5 counts as 0 (the host cannot check it).  The same kernel, checks and launch shape as dcvc_tf_blend.
+ * Further argument errors: those of dcvc_tf_blend but the level's; level_dev NULL or not 4-byte aligned. */
+int dcvc_tf_blend_auto(int dtype, const void* cur_nchw, const void* const* refs_nchw, const int* dists, int nref, int Hp, int Wp,
+                       int H, int W, const int16_t* mv, const uint32_t* err, const int32_t* level_dev, void* out_nchw,
+                       uint64_t* weight_sum, void* stream);
 /* ------------------------------------------------------------------------------------------
  * Frame analysis for the encoder's scene-cut decision (csrc/dcvc_analysis.hip; no reference counterpart: the reference
  * harness places I frames by fi % intra_period only).  luma: H x W samples of the model input (DCVC_F16 / DCVC_F32), row

@@ -16,7 +16,17 @@
 //                       its alignment), element by element with clamped columns where it does not.  fp32 multiply and add in
 //                       reference order, never fused; ONE rounding to the storage type.  Elements outside the picture are
 //                       computed at the clamped coordinate: the replicate pad of the filtered picture.  The luma plane's
-//                       sum of (Wsum - 256) goes wave -> LDS -> ONE 64-bit integer vector atomic per workgroup.
+//                       sum of (Wsum - 256) goes wave -> LDS -> ONE 64-bit integer vector atomic per workgroup.  Its level
+//                       is an argument, or (dcvc_tf_blend_auto) a word of device memory read once, uniformly.
+//   tf_noise_kernel     the level's choice, part one: one value per 8 x 8 block and table - the Laplacian sum S >> 2 of the
+//                       current Q0 and the level-0 SADs of the references at distance +-1, clipped to 4095 - counted into
+//                       4096-bin histograms.  A workgroup walks 32 x 64 tiles of Q0, each staged in LDS with a one-sample
+//                       halo and the clamps applied (every sample is read from memory once per tile); a thread forms the
+//                       8 responses of one row of a block (the mask is [1 -2 1]' [1 -2 1]: columns first), a wave sums a row
+//                       of 8 blocks.  Integer atomics into the workgroup's LDS histograms, whose non-zero bins go to the
+//                       global ones at the end: no result depends on the order of arrival.
+//   tf_level_kernel     part two, one workgroup: per table the number of positive values and the value of rank n_pos >> 2
+//                       among them (a prefix sum over the bins), the minimum over the tables, the level rule, the totals.
 // No allocation and no synchronisation in any entry point.
 #include "common.hpp"
 #include "frame_host.hpp"
@@ -26,7 +36,7 @@
 
 namespace {
 
-constexpr int TB = 256;          // threads per workgroup, all three kernels
+constexpr int TB = 256;          // threads per workgroup, every kernel
 constexpr int TW = 64;           // blend: columns of a tile
 constexpr int TH = 32;           // blend: rows of a tile (TB / (TW / 8) threads of 8 columns)
 constexpr int NB = 8;            // motion: blocks per workgroup (32 lanes each)
@@ -206,14 +216,23 @@ struct TfRefs {
     int base[MAX_REFS];          // B: 102 at distance 1, 77 at distance 2
 };
 
-// VEC: cur and out are 16-byte aligned and the row length is a multiple of 16 bytes
-template <typename T, bool VEC>
-__global__ __launch_bounds__(TB) void tf_blend_kernel(const T* __restrict__ cur, TfRefs refs, int nref, int Hp, int Wp, int H, int W,
+// VEC: cur and out are 16-byte aligned and the row length is a multiple of 16 bytes.  AUTO: the level is the word at level_dev
+// (a compile-time switch: the fixed-level kernel keeps its code; its level_dev is null and not looked at)
+template <typename T, bool VEC, bool AUTO>
+__global__ __launch_bounds__(TB) void tf_blend_kernel(const int32_t* __restrict__ level_dev, const T* __restrict__ cur, TfRefs refs, int nref, int Hp, int Wp, int H, int W,
                                                       const int16_t* __restrict__ mv, const uint32_t* __restrict__ err, int gh,
                                                       int gw, int L, T* __restrict__ out, unsigned long long* __restrict__ total)
 {
     __shared__ long long s_part[TB / 64];
     const int tid = threadIdx.x, plane = blockIdx.z;
+    if (AUTO) {
+        // One scalar load per workgroup, uniform.  level_dev is the kernel's FIRST parameter and this file is built with the
+        // first two dwords of the kernel arguments preloaded into registers (csrc/Makefile): the pointer is there when a wave
+        // starts, so the word's cold scalar-cache miss runs beside that of the other arguments and not behind it.  With the
+        // pointer fetched like any argument this kernel was 0.2 - 0.45 us slower than the fixed-level one.
+        L = *level_dev;
+        if (L < 1 || L > 5) L = nref = 0;                                    // level 0, or no level at all: every weight is 0
+    }
     const int y = blockIdx.y * TH + (tid >> 3), xc = blockIdx.x * TW + (tid & 7) * 8;
     long long stat = 0;
 
@@ -315,6 +334,132 @@ __global__ __launch_bounds__(TB) void tf_blend_kernel(const T* __restrict__ cur,
     }
 }
 
+// ---------------------------------------------------------------------------------- noise estimate
+constexpr int BINS = 4096;       // a block value is clipped to BINS - 1
+constexpr int MAX_TABLES = 3;    // the spatial table, then the references at distance -1 / +1
+constexpr int NOISE_WGS = 512;   // at most so many workgroups share the tiles: each flushes its histograms once
+int g_noise_wgs = NOISE_WGS;     // (dcvc_tf_noise_workgroups: a developer's knob, tools/tf_time.py sweeps it)
+
+struct TfTables {
+    int ntemporal;               // 0 .. 2
+    int ref[MAX_TABLES - 1];     // which of err's tables
+};
+
+// hist [MAX_TABLES][BINS], zero on entry: table 0 the spatial one, 1 .. the temporal ones
+__global__ __launch_bounds__(TB) void tf_noise_kernel(const uint16_t* __restrict__ q0, int H, int W, int gh, int gw, int tiles_x,
+                                                      int tiles, const uint32_t* __restrict__ err, TfTables tabs,
+                                                      uint32_t* __restrict__ hist)
+{
+    constexpr int SW = TW + 2, SH = TH + 2;
+    __shared__ uint32_t s_hist[MAX_TABLES * BINS];
+    __shared__ uint16_t s_q[SH * SW];                     // row r, column c: Q0[clamp(y0 - 1 + r)][clamp(x0 - 1 + c)]
+    const int tid = threadIdx.x, ntab = 1 + tabs.ntemporal;
+    for (int i = tid; i < ntab * BINS; i += TB) s_hist[i] = 0u;
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+        const int y0 = ty * TH, x0 = tx * TW;
+        // a wave: the 8 rows of 8 blocks; lanes 0 .. 7 count their spatial values, lanes 8 .. 15 and 16 .. 23 the same blocks'
+        // values of the temporal tables (loaded here, ahead of the staging)
+        const int by = (y0 >> 3) + wave, bx = (x0 >> 3) + (lane & 7), t = (lane >> 3) - 1;
+        const bool counted = by < gh && bx < gw;
+        uint32_t e = 0u;
+        if (counted && t >= 0 && t < tabs.ntemporal) e = err[(int64_t)tabs.ref[t] * gh * gw + (int64_t)by * gw + bx];
+        __syncthreads();                                  // (the histograms are cleared; the last tile is done with)
+        for (int i = tid; i < SH * SW; i += TB) {
+            const int r = i / SW, c = i - r * SW;
+            s_q[i] = q0[(int64_t)clampi(y0 - 1 + r, 0, H - 1) * W + clampi(x0 - 1 + c, 0, W - 1)];
+        }
+        __syncthreads();
+        // a thread: row tid >> 3 of the tile, the 8 columns of block tid & 7
+        const int y = y0 + (tid >> 3), xb = x0 + (tid & 7) * 8;
+        int sum = 0;
+        if (xb < W) {                                     // (else the block lies past the grid)
+            const int r = min(y, H - 1) - y0 + 1;         // the edge position stands for a position past the edge
+            const uint16_t* up = s_q + (r - 1) * SW + (tid & 7) * 8;
+            int v[10];                                    // the column sums under the 10 columns the 8 positions touch
+#pragma unroll
+            for (int j = 0; j < 10; ++j) v[j] = (int)up[j] - 2 * (int)up[SW + j] + (int)up[2 * SW + j];
+            const int hx = min(7, W - 1 - xb);
+            int resp = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int a = v[i] - 2 * v[i + 1] + v[i + 2];
+                if (i <= hx) resp = a < 0 ? -a : a;
+                sum += resp;
+            }
+        }
+#pragma unroll
+        for (int m = 8; m < 64; m <<= 1) sum += __shfl_xor(sum, m, 64);
+        if (counted && t < tabs.ntemporal)
+            atomicAdd(&s_hist[(t + 1) * BINS + (t < 0 ? min(sum >> 2, BINS - 1) : (int)min(e, (uint32_t)(BINS - 1)))], 1u);
+    }
+    __syncthreads();
+    for (int i = tid; i < ntab * BINS; i += TB) {
+        const uint32_t n = s_hist[i];
+        if (n != 0u) atomicAdd(&hist[i], n);
+    }
+}
+
+// one workgroup.  result: {level, N, smallest temporal figure or -1, spatial figure}; totals: nullptr or
+// [level 0 .. 5 counts, sum of N, frames]
+__global__ __launch_bounds__(TB) void tf_level_kernel(const uint32_t* __restrict__ hist, int ntab, int nblk, int32_t* __restrict__ result,
+                                                      long long* __restrict__ totals)
+{
+    constexpr int PER = BINS / TB;                        // consecutive bins of a thread
+    __shared__ uint32_t s_scan[TB];
+    __shared__ int s_fig[MAX_TABLES];
+    const int tid = threadIdx.x;
+    for (int t = 0; t < ntab; ++t) {
+        uint32_t c[PER], mine = 0u;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            c[i] = (tid == 0 && i == 0) ? 0u : hist[t * BINS + tid * PER + i];      // exact zeros are left out
+            mine += c[i];
+        }
+        if (tid == 0) s_fig[t] = 0;
+        s_scan[tid] = mine;
+        __syncthreads();
+        for (int d = 1; d < TB; d <<= 1) {                // inclusive prefix sums of the threads' counts
+            const uint32_t add = tid >= d ? s_scan[tid - d] : 0u;
+            __syncthreads();
+            s_scan[tid] += add;
+            __syncthreads();
+        }
+        const uint32_t n_pos = s_scan[TB - 1], rank = n_pos >> 2;
+        uint32_t below = s_scan[tid] - mine;              // positive values in the bins before this thread's
+        if ((int64_t)n_pos * 8 >= (int64_t)nblk && below <= rank && rank < below + mine) {      // (one thread)
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {
+                if (rank >= below && rank < below + c[i]) s_fig[t] = tid * PER + i;
+                below += c[i];
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int spatial = s_fig[0];
+        int temporal = -1, n = spatial;
+        for (int t = 1; t < ntab; ++t) temporal = temporal < 0 ? s_fig[t] : min(temporal, s_fig[t]);
+        if (temporal >= 0) n = min(n, temporal);
+        int level = 0;
+        if (n >= 40) {
+            level = 5;
+            for (int l = 4; l >= 1; --l)
+                if (n <= (80 << l)) level = l;
+        }
+        result[0] = level;
+        result[1] = n;
+        result[2] = temporal;
+        result[3] = spatial;
+        if (totals != nullptr) {                          // (launches on a stream run in order: no other adder)
+            totals[level] += 1;
+            totals[6] += n;
+            totals[7] += 1;
+        }
+    }
+}
+
 bool overlaps(const void* a, const void* b, uint64_t bytes)
 {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
@@ -382,13 +527,55 @@ int dcvc_tf_motion(const uint16_t* cur_pyramid, const uint16_t* const* ref_pyram
     return 0;
 }
 
-int dcvc_tf_blend(int dtype, const void* cur_nchw, const void* const* refs_nchw, const int* dists, int nref, int Hp, int Wp, int H,
-                  int W, const int16_t* mv, const uint32_t* err, int level, void* out_nchw, uint64_t* weight_sum, void* stream)
+int64_t dcvc_tf_noise_ws_bytes(void) { return (int64_t)MAX_TABLES * BINS * sizeof(uint32_t); }
+
+int dcvc_tf_noise_workgroups(int n)
 {
-    const char* who = "dcvc_tf_blend";
+    const int was = g_noise_wgs;
+    if (n >= 1 && n <= 65535) g_noise_wgs = n;
+    return was;
+}
+
+int dcvc_tf_noise(const uint16_t* cur_pyramid, const uint32_t* err, const int* dists, int nref, int H, int W, void* ws,
+                  int32_t* result, int64_t* totals, void* stream)
+{
+    const char* who = "dcvc_tf_noise";
+    DCVC_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 30), "%s: bad size %d x %d", who, H, W);
+    DCVC_REQUIRE(nref >= 0 && nref <= MAX_REFS, "%s: %d references, 0 .. %d are supported", who, nref, MAX_REFS);
+    DCVC_REQUIRE(cur_pyramid && ws && result && (nref == 0 || (err && dists)), "%s: null pointer", who);
+    DCVC_REQUIRE(((uintptr_t)cur_pyramid & 1) == 0, "%s: the pyramid is not 2-byte aligned", who);
+    DCVC_REQUIRE(((uintptr_t)err & 3) == 0 && ((uintptr_t)ws & 3) == 0 && ((uintptr_t)result & 3) == 0 && ((uintptr_t)totals & 7) == 0,
+                 "%s: err, ws, result or totals is not aligned to its element size", who);
+    TfTables tabs = {};
+    for (int r = 0; r < nref; ++r) {
+        DCVC_REQUIRE(dists[r] == 1 || dists[r] == -1 || dists[r] == 2 || dists[r] == -2, "%s: distance %d is not +-1 or +-2", who,
+                     dists[r]);
+        if ((dists[r] == 1 || dists[r] == -1) && tabs.ntemporal < MAX_TABLES - 1) tabs.ref[tabs.ntemporal++] = r;
+    }
+    const LevelDims d = level_dims(H, W);
+    const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH), ntab = 1 + tabs.ntemporal;
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* hist = (uint32_t*)ws;
+    DCVC_HIP(hipMemsetAsync(hist, 0, (size_t)ntab * BINS * sizeof(uint32_t), st));
+    tf_noise_kernel<<<(unsigned)(tiles < g_noise_wgs ? tiles : g_noise_wgs), TB, 0, st>>>(cur_pyramid, H, W, d.gh[0], d.gw[0], tiles_x, tiles,
+                                                                                     err, tabs, hist);
+    tf_level_kernel<<<1, TB, 0, st>>>(hist, ntab, d.gh[0] * d.gw[0], result, reinterpret_cast<long long*>(totals));
+    DCVC_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// dcvc_tf_blend (level_dev null: the level is the argument) and dcvc_tf_blend_auto (level_dev checked there; level not looked at)
+int blend(const char* who, int dtype, const void* cur_nchw, const void* const* refs_nchw, const int* dists, int nref, int Hp, int Wp,
+          int H, int W, const int16_t* mv, const uint32_t* err, int level, const int32_t* level_dev, void* out_nchw,
+          uint64_t* weight_sum, void* stream)
+{
     if (int rc = dcvc::check_frame(who, "the current frame", dtype, cur_nchw, Hp, Wp, H, W)) return rc;
     if (int rc = dcvc::check_frame(who, "out", dtype, out_nchw, Hp, Wp, H, W)) return rc;
-    DCVC_REQUIRE(level >= 1 && level <= 5, "%s: level %d outside 1 .. 5", who, level);
+    DCVC_REQUIRE(level_dev || (level >= 1 && level <= 5), "%s: level %d outside 1 .. 5", who, level);
     DCVC_REQUIRE(nref >= 0 && nref <= MAX_REFS, "%s: %d references, at most %d are supported", who, nref, MAX_REFS);
     DCVC_REQUIRE(weight_sum && (nref == 0 || (refs_nchw && dists && mv && err)), "%s: null pointer", who);
     DCVC_REQUIRE((int64_t)H * W < ((int64_t)1 << 30), "%s: picture too large", who);
@@ -414,10 +601,32 @@ int dcvc_tf_blend(int dtype, const void* cur_nchw, const void* const* refs_nchw,
     return dcvc::typed(dtype, [&](auto tag) {
         using T = decltype(tag);
         dcvc::with_flag(vec, [&](auto v) {
-            tf_blend_kernel<T, decltype(v)::value><<<grid, TB, 0, (hipStream_t)stream>>>(
-                (const T*)cur_nchw, refs, nref, Hp, Wp, H, W, mv, err, d.gh[0], d.gw[0], level, (T*)out_nchw, total);
+            dcvc::with_flag(level_dev != nullptr, [&](auto a) {
+                tf_blend_kernel<T, decltype(v)::value, decltype(a)::value><<<grid, TB, 0, (hipStream_t)stream>>>(
+                    level_dev, (const T*)cur_nchw, refs, nref, Hp, Wp, H, W, mv, err, d.gh[0], d.gw[0], level, (T*)out_nchw, total);
+            });
         });
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int dcvc_tf_blend(int dtype, const void* cur_nchw, const void* const* refs_nchw, const int* dists, int nref, int Hp, int Wp, int H,
+                  int W, const int16_t* mv, const uint32_t* err, int level, void* out_nchw, uint64_t* weight_sum, void* stream)
+{
+    return blend("dcvc_tf_blend", dtype, cur_nchw, refs_nchw, dists, nref, Hp, Wp, H, W, mv, err, level, nullptr, out_nchw,
+                 weight_sum, stream);
+}
+
+int dcvc_tf_blend_auto(int dtype, const void* cur_nchw, const void* const* refs_nchw, const int* dists, int nref, int Hp, int Wp,
+                       int H, int W, const int16_t* mv, const uint32_t* err, const int32_t* level_dev, void* out_nchw,
+                       uint64_t* weight_sum, void* stream)
+{
+    DCVC_REQUIRE(level_dev && ((uintptr_t)level_dev & 3) == 0, "dcvc_tf_blend_auto: the level's word is null or not 4-byte aligned");
+    return blend("dcvc_tf_blend_auto", dtype, cur_nchw, refs_nchw, dists, nref, Hp, Wp, H, W, mv, err, 0, level_dev, out_nchw,
+                 weight_sum, stream);
 }
 
 }  // extern "C"

@@ -412,8 +412,8 @@ def make_source(src_type, path, width, height):
 def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, tf_level=0, tf_radius=2):
     """every frame of `src` through a SequenceEncoder(**enc_kw) into the container; coded: None or the (height, width) the
     frames are resampled down to first; grain: None, a GrainParams, or "auto" (estimated at every I frame from the full-size
-    input against the reconstruction at that size, the unit's seed the frame's index); tf_level > 0: the frames pass a
-    prefilter.TemporalFilter at source size first, which reads tf_radius frames ahead - "auto" is still given the UNFILTERED
+    input against the reconstruction at that size, the unit's seed the frame's index); tf_level 1 .. 5 or "auto": the frames pass
+    a prefilter.TemporalFilter at source size first, which reads tf_radius frames ahead - grain "auto" is still given the UNFILTERED
     input of the frame being coded.  The clock of a frame spans loader, temporal filter, down-resample, encode and
     write_frame; the file read and the copy to the device stay outside.
     -> (encoder, stream bytes, frame types, bits, times, the Resampler, the FilmGrain and the TemporalFilter made here or None)"""
@@ -538,7 +538,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
       digest                       docs/state_digest.md                       log: digests_checked
       coded_size, scale_filter     docs/reduced_resolution.md                 log: coded_height, coded_width, scale_filter
       film_grain                   docs/film_grain.md (None, "auto", a GrainParams)   log: grain_units, grain_scale_y, grain_corr
-      temporal_filter, tf_radius   docs/temporal_filter.md (level 0 = off .. 5; 1, 2)  log: tf_level, tf_radius, tf_mean_weight"""
+      temporal_filter, tf_radius   docs/temporal_filter.md (level 0 = off .. 5; 1, 2)  log: tf_level, tf_radius, tf_mean_weight
+                                   level "auto": chosen per frame from a noise estimate   log: + tf_levels, tf_noise"""
     from .grain import GrainParams
     from .prefilter import check_options
     from .resize import FILTERS, check_coded_size
@@ -595,6 +596,9 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     if tf is not None:
         log.update(tf_level=temporal_filter, tf_radius=tf_radius,
                    tf_mean_weight=tf.weight_sum() / (256.0 * height * width * frame_num))
+        if temporal_filter == "auto":                     # frames per level 0 .. 5; the mean N as white noise's sigma in 8-bit codes
+            totals = tf.levels()
+            log.update(tf_levels=totals[:6], tf_noise=totals[6] / max(totals[7], 1) * (255.0 / (68.0 * 1023.0)))
     return log
 
 
@@ -915,13 +919,28 @@ def _add_extension_options(ap, flag):
                     help="film-grain synthesis: at every I frame the grain the codec removed is estimated on the device and "
                          "written as a 14-byte grain unit; the decode loop puts it back on the pictures it stores, not on "
                          "the ones it measures (docs/film_grain.md) - this project's extension, not readable by the reference")
-    ap.add_argument("--temporal-filter", "--temporal_filter", type=int, default=0, choices=range(6), metavar="L",
+    ap.add_argument("--temporal-filter", "--temporal_filter", type=_tf_level, default=0, metavar="L",
                     help="motion-compensated temporal denoising of the source in front of the encoder at strength L = 1 .. 5 "
-                         "(0 = off; 3 is recommended; docs/temporal_filter.md): encoder side only, the stream format is "
+                         "(0 = off; 3 is recommended; docs/temporal_filter.md), or `auto`: the level is chosen per frame from "
+                         "a noise estimate made on the device.  Encoder side only, the stream format is "
                          "unchanged.  The counterpart of --film-grain: the encoder stops spending bits on noise the decoder "
                          "synthesises anyway.  Metrics stay those against the unfiltered source")
     ap.add_argument("--tf-radius", "--tf_radius", type=int, default=2, choices=(1, 2), metavar="R",
                     help="with --temporal-filter: references up to R frames before and after a frame (the encoder reads R frames ahead)")
+
+
+def _tf_level(v):
+    """--temporal-filter: 0 .. 5 as an int, or auto"""
+    import argparse
+    if v == "auto":
+        return v
+    try:
+        level = int(v)
+    except ValueError:
+        level = -1
+    if not 0 <= level <= 5:
+        raise argparse.ArgumentTypeError(f"{v!r}: 0 .. 5 or auto")
+    return level
 
 
 def build_parser():

@@ -2,21 +2,24 @@
 counterpart): every frame is blended with up to four of its unfiltered neighbours, each gathered block by block at the vector
 an integer-pyramid motion search finds for it, with weights that fall to zero where the neighbour does not match.  Encoder
 side only - the stream and the decoder know nothing of it.  The arithmetic is integer up to one fp32 blend per sample; the
-kernels and the numpy restatement tests/tf_ref.py agree bit for bit."""
+kernels and the numpy restatement tests/tf_ref.py agree bit for bit.  Level "auto": the level is chosen per frame on the device
+from a noise estimate of the picture and never read back (tests/tf_auto_ref.py restates it)."""
 import ctypes
 
 LEVELS = (1, 2, 3, 4, 5)                               # strength: T = 4 << level 10-bit codes
 RADII = (1, 2)
 MAX_REFS = 4
+AUTO = "auto"                                          # the level chosen per frame from the picture's noise
 
 
 def check_options(level, radius):
-    """(level, radius) as integers; level 0 (off) .. 5, radius 1 or 2"""
-    if isinstance(level, bool) or not isinstance(level, int) or not 0 <= level <= LEVELS[-1]:
+    """(level, radius) as integers; level 0 (off) .. 5 or "auto", radius 1 or 2"""
+    auto = isinstance(level, str) and level == AUTO
+    if not auto and (isinstance(level, bool) or not isinstance(level, int) or not 0 <= level <= LEVELS[-1]):
         raise ValueError(f"temporal filter level {level!r}: 0 (off) .. {LEVELS[-1]}")
     if isinstance(radius, bool) or radius not in RADII:
         raise ValueError(f"temporal filter radius {radius!r}: 1 or 2")
-    return level, int(radius)
+    return (AUTO if auto else level), int(radius)
 
 
 def window(n_frames, radius):
@@ -33,11 +36,12 @@ def _refs_of(t, n_frames, radius):
 
 
 class TemporalFilter:
-    """The filter on `device` at strength `level` (1 .. 5) with references up to `radius` (1, 2) frames away.
+    """The filter on `device` at strength `level` (1 .. 5, or "auto": chosen per frame from a noise estimate that stays on the
+    device) with references up to `radius` (1, 2) frames away.
     filter() and motion() are stateless; push() / flush() run a sequence through a ring of 2 * radius + 1 source frames whose
     pyramids are made once per frame.  Everything is sized at the first frame (and again if the frames change shape) and
     nothing is allocated per frame; all work is enqueued on the current stream and nothing is waited for, except by
-    weight_sum().  A frame push() / flush() returns lives in one of radius + 1 buffers of the object: it holds until radius + 1
+    weight_sum(), levels() and noise().  A frame push() / flush() returns lives in one of radius + 1 buffers of the object: it holds until radius + 1
     further frames have come out."""
 
     def __init__(self, device="cuda:0", level=3, radius=2):
@@ -47,6 +51,9 @@ class TemporalFilter:
             raise ValueError("temporal filter level 0 is 'off': make no TemporalFilter")
         self.device, self.level, self.radius = torch.device(device), level, radius
         self._total = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._levels = torch.zeros(8, dtype=torch.int64, device=self.device)        # six level counts, the sum of N, the frames
+        self._result = torch.zeros(4, dtype=torch.int32, device=self.device)        # level, N, temporal, spatial of the last estimate
+        self._noise_ws = None
         self._key = None
         self.reset()
 
@@ -77,14 +84,17 @@ class TemporalFilter:
         self._ws = torch.empty(max(L.dcvc_tf_motion_ws_bytes(H, W), 1), dtype=torch.uint8, device=dev)
         self._mv = torch.empty((MAX_REFS, gh, gw, 2), dtype=torch.int16, device=dev)
         self._err = torch.empty((MAX_REFS, gh, gw), dtype=torch.int32, device=dev)
+        if self._noise_ws is None:
+            self._noise_ws = torch.empty(L.dcvc_tf_noise_ws_bytes(), dtype=torch.uint8, device=dev)
         self._key = key
         self.reset()
 
     def reset(self):
-        """forgets the frames pushed so far and zeroes the weight sum; the buffers stay"""
+        """forgets the frames pushed so far and zeroes the weight sum and the levels' totals; the buffers stay"""
         self._pushed = self._emitted = 0
         self._size_of_sequence = None
         self._total.zero_()
+        self._levels.zero_()
 
     # ------------------------------------------------------------------------------ the kernels
     def _pyramid(self, x, size, slot):
@@ -100,14 +110,28 @@ class TemporalFilter:
         _lib.check(_lib.lib().dcvc_tf_motion(L._p(self._pyr[cur_slot]), pyrs, n, size[0], size[1], L._p(self._mv), L._p(self._err),
                                              L._p(self._ws), L._stream()), "dcvc_tf_motion")
 
+    def _noise(self, cur_slot, dists, size, totals):
+        """the estimate of the frame whose pyramid is in cur_slot, after _motion() on its references -> self._result"""
+        from . import _lib
+        from . import nn as L
+        n = len(dists)
+        _lib.check(_lib.lib().dcvc_tf_noise(L._p(self._pyr[cur_slot]), L._p(self._err), (ctypes.c_int * max(n, 1))(*dists), n, size[0],
+                                            size[1], L._p(self._noise_ws), L._p(self._result), L._p(self._levels) if totals else None,
+                                            L._stream()), "dcvc_tf_noise")
+
     def _blend(self, cur, refs, dists, size, out):
+        """at the object's level; "auto": at the level _noise() left in self._result (a frame without references is a copy)"""
         from . import _lib
         from . import nn as L
         n = len(refs)
         ptrs = (ctypes.c_void_p * max(n, 1))(*[r.data_ptr() for r in refs])
         code, cur_p, Hp, Wp, H, W = L.frame_args(cur, size)
-        _lib.check(_lib.lib().dcvc_tf_blend(code, cur_p, ptrs, (ctypes.c_int * max(n, 1))(*dists), n, Hp, Wp, H, W, L._p(self._mv),
-                                            L._p(self._err), self.level, L._p(out), L._p(self._total), L._stream()), "dcvc_tf_blend")
+        head = (code, cur_p, ptrs, (ctypes.c_int * max(n, 1))(*dists), n, Hp, Wp, H, W, L._p(self._mv), L._p(self._err))
+        tail = (L._p(out), L._p(self._total), L._stream())
+        if self.level == AUTO and n:
+            _lib.check(_lib.lib().dcvc_tf_blend_auto(*head, L._p(self._result), *tail), "dcvc_tf_blend_auto")
+        else:
+            _lib.check(_lib.lib().dcvc_tf_blend(*head, LEVELS[0] if self.level == AUTO else self.level, *tail), "dcvc_tf_blend")
 
     def _check(self, cur, refs, dists, size):
         cur = self._frame(cur)
@@ -125,7 +149,8 @@ class TemporalFilter:
     def filter(self, cur, refs, dists, size, out=None):
         """cur filtered against refs (accumulated in the order given; dists: their distances, +-1 / +-2) on its
         size = (H, W) picture, replicate-padded to cur's shape.  out: None (a new tensor) or a contiguous tensor like cur that
-        overlaps no input.  Adds to the weight sum."""
+        overlaps no input.  Adds to the weight sum (level "auto": and to the levels' totals).  Frames of another shape, type or
+        picture size than the object's current ones make it size its buffers anew, which is a reset()."""
         import torch
         cur, refs, dists, size = self._check(cur, refs, dists, size)
         if out is None:
@@ -139,8 +164,26 @@ class TemporalFilter:
             for i, r in enumerate(refs):
                 self._pyramid(r, size, n + 1 + i)
             self._motion(n, [n + 1 + i for i in range(len(refs))], size)
+            if self.level == AUTO:
+                self._noise(n, dists, size, True)
         self._blend(cur, refs, dists, size, out)
         return out
+
+    def noise(self, cur, refs, dists, size):
+        """the estimate of cur against refs (dists: their distances; none: the spatial table alone) as Python ints
+        (level, N, the smallest temporal figure or -1, the spatial figure); adds to no total; one read-back.  Like filter(),
+        motion() and pyramid() it keeps no frame, but frames of another shape, type or picture size than the object's current
+        ones make it size its buffers anew, which is a reset(): a push() sequence under way and the totals are dropped"""
+        cur, refs, dists, size = self._check(cur, refs, dists, size)
+        self._size(cur, size)
+        n = 2 * self.radius + 1
+        self._pyramid(cur, size, n)
+        for i, r in enumerate(refs):
+            self._pyramid(r, size, n + 1 + i)
+        if refs:
+            self._motion(n, [n + 1 + i for i in range(len(refs))], size)
+        self._noise(n, dists, size, False)
+        return tuple(int(v) for v in self._result.tolist())
 
     def motion(self, cur, ref, size):
         """the level-0 vectors and errors of one reference: (mv int16 [gh, gw, 2] as (y, x), err int32 [gh, gw]), new tensors"""
@@ -168,6 +211,8 @@ class TemporalFilter:
         slots = [i % n for i, _ in refs]
         if refs:
             self._motion(t % n, slots, self._size_of_sequence)
+            if self.level == AUTO:
+                self._noise(t % n, [d for _, d in refs], self._size_of_sequence, True)
         out = self._out[t % (self.radius + 1)]
         self._blend(self._ring[t % n], [self._ring[s] for s in slots], [d for _, d in refs], self._size_of_sequence, out)
         self._emitted += 1
@@ -199,3 +244,8 @@ class TemporalFilter:
     def weight_sum(self):
         """the sum over the luma samples filtered since reset() of (Wsum - 256); one read-back"""
         return int(self._total.item())
+
+    def levels(self):
+        """of the frames estimated since reset() (level "auto"; a frame without references is not one): the number that got
+        level 0 .. 5, the sum of their N, their number - eight ints; one read-back"""
+        return [int(v) for v in self._levels.tolist()]
