@@ -561,6 +561,25 @@ int dcvc_tf_noise(const uint16_t* cur_pyramid, const uint32_t* err, const int* d
 int dcvc_tf_blend_auto(int dtype, const void* cur_nchw, const void* const* refs_nchw, const int* dists, int nref, int Hp, int Wp,
                        int H, int W, const int16_t* mv, const uint32_t* err, const int32_t* level_dev, void* out_nchw,
                        uint64_t* weight_sum, void* stream);
+/* Quarter-pel motion (csrc/dcvc_tf_subpel.hip; docs/temporal_filter.md, "Quarter-pel motion"), opt-in: a caller that does not
+ * want it calls neither entry.  dcvc_tf_refine refines dcvc_tf_motion's level-0 vectors of nref (1 .. 4) references on the two
+ * frames' Q0 (the pyramids given to dcvc_tf_motion; mv / err: its outputs, read only): stage H tries the nine vectors
+ * 4 * mv + (dy, dx), dy and dx in {-2, 0, 2} quarter pels, and with subpel 2 stage Q the nine around H's winner with
+ * {-1, 0, 1}; reference samples are interpolated in integers with the HEVC luma taps, a candidate ranks by its SAD, plus an
+ * eighth of it unless it is the stage's centre, ties by (|dy| + |dx|, dy, dx).  mvq [nref][gh][gw][2] int16 as (y, x) in
+ * quarter pels; errq [nref][gh][gw] uint32: the winner's own SAD, which takes err's place in dcvc_tf_noise and in the blend.
+ * One launch, no workspace.  Further argument errors: nref outside 1 .. 4; subpel that is not 1 or 2; err or errq not 4-byte
+ * aligned; mvq or errq overlapping mv, err or each other. */
+int dcvc_tf_refine(const uint16_t* cur_pyramid, const uint16_t* const* ref_pyramids, int nref, int H, int W, int subpel,
+                   const int16_t* mv, const uint32_t* err, int16_t* mvq, uint32_t* errq, void* stream);
+/* dcvc_tf_blend with quarter-pel vectors: the reference sample is interpolated in fp32 with the same taps, rows first, each
+ * sum in rising tap order over the non-zero taps and scaled by 1 / 64, multiply and add never fused, no clamp; a whole
+ * component is not filtered, so a whole vector gives dcvc_tf_blend's bits.  level_dev NULL: the fixed level 1 .. 5; otherwise
+ * the level is the device word, with dcvc_tf_blend_auto's meaning, and level is not looked at.  One launch for the three
+ * planes.  Argument errors: those of dcvc_tf_blend (dcvc_tf_blend_auto where level_dev is given). */
+int dcvc_tf_blend_subpel(int dtype, const void* cur_nchw, const void* const* refs_nchw, const int* dists, int nref, int Hp, int Wp,
+                         int H, int W, const int16_t* mvq, const uint32_t* errq, int level, const int32_t* level_dev, void* out_nchw,
+                         uint64_t* weight_sum, void* stream);
 /* ------------------------------------------------------------------------------------------
  * Frame analysis for the encoder's scene-cut decision (csrc/dcvc_analysis.hip; no reference counterpart: the reference
  * harness places I frames by fi % intra_period only).  luma: H x W samples of the model input (DCVC_F16 / DCVC_F32), row

@@ -168,6 +168,8 @@ _SIGS = {
     "dcvc_tf_noise_workgroups": (_I, [_I]),
     "dcvc_tf_noise": (_I, [_P, _P, POINTER(_I), _I, _I, _I, _P, _P, _P, _P]),
     "dcvc_tf_blend_auto": (_I, [_I, _P, POINTER(_P), POINTER(_I), _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "dcvc_tf_refine": (_I, [_P, POINTER(_P), _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "dcvc_tf_blend_subpel": (_I, [_I, _P, POINTER(_P), POINTER(_I), _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "dcvc_frame_analysis_ws_bytes": (_L, [_I, _I]),
     "dcvc_frame_analyze": (_I, [_I, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
     "dcvc_rate_estimate_ws_bytes": (_L, [_I, _I, _I]),

@@ -409,11 +409,12 @@ def make_source(src_type, path, width, height):
 
 
 # ---------------------------------------------------------------------------------- one rate point
-def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, tf_level=0, tf_radius=2):
+def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, tf_level=0, tf_radius=2, tf_subpel=0):
     """every frame of `src` through a SequenceEncoder(**enc_kw) into the container; coded: None or the (height, width) the
     frames are resampled down to first; grain: None, a GrainParams, or "auto" (estimated at every I frame from the full-size
     input against the reconstruction at that size, the unit's seed the frame's index); tf_level 1 .. 5 or "auto": the frames pass
-    a prefilter.TemporalFilter at source size first, which reads tf_radius frames ahead - grain "auto" is still given the UNFILTERED
+    a prefilter.TemporalFilter (vectors refined to half / quarter pels with tf_subpel 1 / 2) at source size first, which reads
+    tf_radius frames ahead - grain "auto" is still given the UNFILTERED
     input of the frame being coded.  The clock of a frame spans loader, temporal filter, down-resample, encode and
     write_frame; the file read and the copy to the device stay outside.
     -> (encoder, stream bytes, frame types, bits, times, the Resampler, the FilmGrain and the TemporalFilter made here or None)"""
@@ -452,7 +453,7 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
     tf = None
     if tf_level:
         from .prefilter import TemporalFilter
-        tf = TemporalFilter(dev, tf_level, tf_radius)
+        tf = TemporalFilter(dev, tf_level, tf_radius, tf_subpel)
         waiting = []                                     # (unfiltered input, seconds on the clock so far) of the frames read ahead
     for _ in range(frame_num):
         planes = _to_device(reader.read(), dev)
@@ -524,7 +525,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
                   src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
                   target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3", film_grain=None,
-                  temporal_filter=0, tf_radius=2):
+                  temporal_filter=0, tf_radius=2, tf_subpel=0):
     """Encodes `frame_num` frames of a source (src_type: SRC_TYPES - a planar 8-bit YUV 4:2:0 file, a directory of PNGs, a raw
     file in a pipeline.PIXEL_FORMATS format) into the reference's container (optionally written to bin_path), decodes the
     container again and returns the reference-schema log (summarize) plus one group of keys per extension switched on.
@@ -539,9 +540,10 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
       coded_size, scale_filter     docs/reduced_resolution.md                 log: coded_height, coded_width, scale_filter
       film_grain                   docs/film_grain.md (None, "auto", a GrainParams)   log: grain_units, grain_scale_y, grain_corr
       temporal_filter, tf_radius   docs/temporal_filter.md (level 0 = off .. 5; 1, 2)  log: tf_level, tf_radius, tf_mean_weight
-                                   level "auto": chosen per frame from a noise estimate   log: + tf_levels, tf_noise"""
+                                   level "auto": chosen per frame from a noise estimate   log: + tf_levels, tf_noise
+      tf_subpel                    its vectors in whole (0), half (1) or quarter pels (2)     log: + tf_subpel where not 0"""
     from .grain import GrainParams
-    from .prefilter import check_options
+    from .prefilter import check_options, check_subpel
     from .resize import FILTERS, check_coded_size
     for name, value, choices in (("metrics", metrics, ("host", "device")), ("entropy", entropy, ("host", "device")),
                                  ("src_type", src_type, SRC_TYPES), ("scale_filter", scale_filter, FILTERS)):
@@ -551,6 +553,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     if not (film_grain is None or film_grain == "auto" or isinstance(film_grain, GrainParams)):
         raise ValueError(f"film_grain {film_grain!r}: None, 'auto' or a GrainParams")
     temporal_filter, tf_radius = check_options(temporal_filter, tf_radius)
+    tf_subpel = check_subpel(tf_subpel)
     src = make_source(src_type, src_path, width, height)
     import torch
     dev, nets = torch.device(device), (i_net, p_net)
@@ -570,7 +573,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         enc_kw["digest"] = True
     enc, stream, frame_types, bits, enc_time, scaler, grainer, tf = _encode_pass(nets, src, frame_num, dev, coded_size,
                                                                                  scale_filter, film_grain, enc_kw,
-                                                                                 temporal_filter, tf_radius)
+                                                                                 temporal_filter, tf_radius,
+                                                                                 **({"tf_subpel": tf_subpel} if tf_subpel else {}))
     if bin_path:
         with open(bin_path, "wb") as f:
             f.write(stream)
@@ -599,13 +603,15 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         if temporal_filter == "auto":                     # frames per level 0 .. 5; the mean N as white noise's sigma in 8-bit codes
             totals = tf.levels()
             log.update(tf_levels=totals[:6], tf_noise=totals[6] / max(totals[7], 1) * (255.0 / (68.0 * 1023.0)))
+        if tf_subpel:
+            log["tf_subpel"] = tf_subpel
     return log
 
 
 # The per-point options: (run_one_point keyword, default, normaliser of a value that is set or None).  run_job, main and
 # manifest_options all go through point_kwargs, so a new option is one row here, one build_parser line under the same name and
 # its hook in run_one_point.  target_bpp is not one of them: it is worked out per sequence (target_bpp()).  Nor
-# are temporal_filter / tf_radius: they act in front of the encoder, not on a rate point, and the table's names are pinned
+# are temporal_filter / tf_radius / tf_subpel: they act in front of the encoder, not on a rate point, and the table's names are pinned
 # (tests/test_harness_options.py), so they travel target_bpp's way - prefilter_kwargs(), passed beside point_kwargs().
 POINT_OPTIONS = (("verbose", 0, None), ("verbose_json", False, bool), ("calc_ssim", False, bool), ("metrics", "host", None),
                  ("entropy", "host", None), ("scenecut", 0, None), ("min_keyint", 4, None), ("digest", False, bool),
@@ -619,9 +625,13 @@ def point_kwargs(opts):
 
 
 def prefilter_kwargs(opts):
-    """an options mapping -> run_one_point's keywords of the temporal pre-filter; missing or None: the defaults (off, radius 2)"""
+    """an options mapping -> run_one_point's keywords of the temporal pre-filter; missing or None: the defaults (off, radius 2);
+    tf_subpel only where it is set and not 0 (whole-pel vectors: the keywords of before the option)"""
     level, radius = opts.get("temporal_filter"), opts.get("tf_radius")
-    return {"temporal_filter": 0 if level is None else level, "tf_radius": 2 if radius is None else radius}
+    kw = {"temporal_filter": 0 if level is None else level, "tf_radius": 2 if radius is None else radius}
+    if opts.get("tf_subpel"):
+        kw["tf_subpel"] = opts["tf_subpel"]
+    return kw
 
 
 def run_sweep(make_nets, src_path, width, height, frame_num, rate_num=4, qp_i=None, qp_p=None, bin_prefix=None, **kw):
@@ -927,6 +937,9 @@ def _add_extension_options(ap, flag):
                          "synthesises anyway.  Metrics stay those against the unfiltered source")
     ap.add_argument("--tf-radius", "--tf_radius", type=int, default=2, choices=(1, 2), metavar="R",
                     help="with --temporal-filter: references up to R frames before and after a frame (the encoder reads R frames ahead)")
+    ap.add_argument("--tf-subpel", "--tf_subpel", type=int, default=0, choices=(0, 1, 2), metavar="S",
+                    help="with --temporal-filter: refine the filter's motion vectors to half (1) or quarter pels (2) and gather "
+                         "interpolated reference samples (0 = whole-pel vectors; 2 is recommended for camera material)")
 
 
 def _tf_level(v):
@@ -1014,7 +1027,7 @@ def manifest_options(args, ap):
     opts = {k: getattr(args, k) for k in ("rate_num", "qp_i", "qp_p", "force_root_path", "force_frame_num", "force_intra_period",
                                           "reset_interval", "model_i", "model_p", "force_zero_thres", "fp32", "target_bpp",
                                           "target_kbps", "fps", "force_intra", "check_existing", "save_decoded_frame",
-                                          "temporal_filter", "tf_radius")}
+                                          "temporal_filter", "tf_radius", "tf_subpel")}
     opts.update(gpu_ids=gpu_ids, stream_path=stream_path, **point_kwargs(vars(args)))
     return opts, gpus
 

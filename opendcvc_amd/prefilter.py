@@ -3,13 +3,15 @@ counterpart): every frame is blended with up to four of its unfiltered neighbour
 an integer-pyramid motion search finds for it, with weights that fall to zero where the neighbour does not match.  Encoder
 side only - the stream and the decoder know nothing of it.  The arithmetic is integer up to one fp32 blend per sample; the
 kernels and the numpy restatement tests/tf_ref.py agree bit for bit.  Level "auto": the level is chosen per frame on the device
-from a noise estimate of the picture and never read back (tests/tf_auto_ref.py restates it)."""
+from a noise estimate of the picture and never read back (tests/tf_auto_ref.py restates it).  subpel 1 / 2: the vectors are refined
+to half / quarter pels and the blend interpolates its reference samples (csrc/dcvc_tf_subpel.hip, tests/tf_subpel_ref.py)."""
 import ctypes
 
 LEVELS = (1, 2, 3, 4, 5)                               # strength: T = 4 << level 10-bit codes
 RADII = (1, 2)
 MAX_REFS = 4
 AUTO = "auto"                                          # the level chosen per frame from the picture's noise
+SUBPELS = (0, 1, 2)                                    # the vectors' precision: whole, half, quarter pels
 
 
 def check_options(level, radius):
@@ -20,6 +22,13 @@ def check_options(level, radius):
     if isinstance(radius, bool) or radius not in RADII:
         raise ValueError(f"temporal filter radius {radius!r}: 1 or 2")
     return (AUTO if auto else level), int(radius)
+
+
+def check_subpel(subpel):
+    """subpel as an integer: 0 (whole-pel vectors), 1 (refined to half pels) or 2 (to quarter pels)"""
+    if isinstance(subpel, bool) or subpel not in SUBPELS:
+        raise ValueError(f"temporal filter subpel {subpel!r}: 0, 1 or 2")
+    return int(subpel)
 
 
 def window(n_frames, radius):
@@ -37,16 +46,18 @@ def _refs_of(t, n_frames, radius):
 
 class TemporalFilter:
     """The filter on `device` at strength `level` (1 .. 5, or "auto": chosen per frame from a noise estimate that stays on the
-    device) with references up to `radius` (1, 2) frames away.
+    device) with references up to `radius` (1, 2) frames away, at vectors of whole pels (`subpel` 0) or refined to half (1) or
+    quarter pels (2).
     filter() and motion() are stateless; push() / flush() run a sequence through a ring of 2 * radius + 1 source frames whose
     pyramids are made once per frame.  Everything is sized at the first frame (and again if the frames change shape) and
     nothing is allocated per frame; all work is enqueued on the current stream and nothing is waited for, except by
     weight_sum(), levels() and noise().  A frame push() / flush() returns lives in one of radius + 1 buffers of the object: it holds until radius + 1
     further frames have come out."""
 
-    def __init__(self, device="cuda:0", level=3, radius=2):
+    def __init__(self, device="cuda:0", level=3, radius=2, subpel=0):
         import torch
         level, radius = check_options(level, radius)
+        self.subpel = check_subpel(subpel)
         if level == 0:
             raise ValueError("temporal filter level 0 is 'off': make no TemporalFilter")
         self.device, self.level, self.radius = torch.device(device), level, radius
@@ -84,6 +95,9 @@ class TemporalFilter:
         self._ws = torch.empty(max(L.dcvc_tf_motion_ws_bytes(H, W), 1), dtype=torch.uint8, device=dev)
         self._mv = torch.empty((MAX_REFS, gh, gw, 2), dtype=torch.int16, device=dev)
         self._err = torch.empty((MAX_REFS, gh, gw), dtype=torch.int32, device=dev)
+        # what _noise() and _blend() read: the search's own outputs, or (subpel, filter()'s motions) these two
+        self._mvq = torch.empty_like(self._mv) if self.subpel else None
+        self._errq = torch.empty_like(self._err) if self.subpel else None
         if self._noise_ws is None:
             self._noise_ws = torch.empty(L.dcvc_tf_noise_ws_bytes(), dtype=torch.uint8, device=dev)
         self._key = key
@@ -109,13 +123,16 @@ class TemporalFilter:
         pyrs = (ctypes.c_void_p * n)(*[self._pyr[s].data_ptr() for s in ref_slots])
         _lib.check(_lib.lib().dcvc_tf_motion(L._p(self._pyr[cur_slot]), pyrs, n, size[0], size[1], L._p(self._mv), L._p(self._err),
                                              L._p(self._ws), L._stream()), "dcvc_tf_motion")
+        if self.subpel:
+            _lib.check(_lib.lib().dcvc_tf_refine(L._p(self._pyr[cur_slot]), pyrs, n, size[0], size[1], self.subpel, L._p(self._mv),
+                                                 L._p(self._err), L._p(self._mvq), L._p(self._errq), L._stream()), "dcvc_tf_refine")
 
     def _noise(self, cur_slot, dists, size, totals):
         """the estimate of the frame whose pyramid is in cur_slot, after _motion() on its references -> self._result"""
         from . import _lib
         from . import nn as L
         n = len(dists)
-        _lib.check(_lib.lib().dcvc_tf_noise(L._p(self._pyr[cur_slot]), L._p(self._err), (ctypes.c_int * max(n, 1))(*dists), n, size[0],
+        _lib.check(_lib.lib().dcvc_tf_noise(L._p(self._pyr[cur_slot]), L._p(self._errq if self.subpel else self._err), (ctypes.c_int * max(n, 1))(*dists), n, size[0],
                                             size[1], L._p(self._noise_ws), L._p(self._result), L._p(self._levels) if totals else None,
                                             L._stream()), "dcvc_tf_noise")
 
@@ -126,8 +143,14 @@ class TemporalFilter:
         n = len(refs)
         ptrs = (ctypes.c_void_p * max(n, 1))(*[r.data_ptr() for r in refs])
         code, cur_p, Hp, Wp, H, W = L.frame_args(cur, size)
-        head = (code, cur_p, ptrs, (ctypes.c_int * max(n, 1))(*dists), n, Hp, Wp, H, W, L._p(self._mv), L._p(self._err))
         tail = (L._p(out), L._p(self._total), L._stream())
+        if self.subpel:
+            auto = self.level == AUTO and n
+            _lib.check(_lib.lib().dcvc_tf_blend_subpel(code, cur_p, ptrs, (ctypes.c_int * max(n, 1))(*dists), n, Hp, Wp, H, W,
+                                                       L._p(self._mvq), L._p(self._errq), LEVELS[0] if self.level == AUTO else self.level,
+                                                       L._p(self._result) if auto else None, *tail), "dcvc_tf_blend_subpel")
+            return
+        head = (code, cur_p, ptrs, (ctypes.c_int * max(n, 1))(*dists), n, Hp, Wp, H, W, L._p(self._mv), L._p(self._err))
         if self.level == AUTO and n:
             _lib.check(_lib.lib().dcvc_tf_blend_auto(*head, L._p(self._result), *tail), "dcvc_tf_blend_auto")
         else:
@@ -146,13 +169,17 @@ class TemporalFilter:
         return cur, refs, dists, tuple(int(v) for v in size)
 
     # ------------------------------------------------------------------------------ stateless
-    def filter(self, cur, refs, dists, size, out=None):
+    def filter(self, cur, refs, dists, size, out=None, motions=None):
         """cur filtered against refs (accumulated in the order given; dists: their distances, +-1 / +-2) on its
         size = (H, W) picture, replicate-padded to cur's shape.  out: None (a new tensor) or a contiguous tensor like cur that
         overlaps no input.  Adds to the weight sum (level "auto": and to the levels' totals).  Frames of another shape, type or
-        picture size than the object's current ones make it size its buffers anew, which is a reset()."""
+        picture size than the object's current ones make it size its buffers anew, which is a reset().  motions: None, or per
+        reference the (vectors, errors) to use instead of searching - tensors like motion()'s of a subpel 0 object,
+        like motion_subpel()'s (quarter pels) otherwise."""
         import torch
         cur, refs, dists, size = self._check(cur, refs, dists, size)
+        if motions is not None and len(motions) != len(refs):
+            raise ValueError(f"{len(motions)} motions for {len(refs)} references")
         if out is None:
             out = torch.empty_like(cur)
         elif out.shape != cur.shape or out.dtype != cur.dtype or not out.is_contiguous():
@@ -160,10 +187,17 @@ class TemporalFilter:
         self._size(cur, size)
         n = 2 * self.radius + 1
         if refs:
-            self._pyramid(cur, size, n)
-            for i, r in enumerate(refs):
-                self._pyramid(r, size, n + 1 + i)
-            self._motion(n, [n + 1 + i for i in range(len(refs))], size)
+            if motions is None or self.level == AUTO:
+                self._pyramid(cur, size, n)
+            if motions is None:
+                for i, r in enumerate(refs):
+                    self._pyramid(r, size, n + 1 + i)
+                self._motion(n, [n + 1 + i for i in range(len(refs))], size)
+            else:
+                mv, err = (self._mvq, self._errq) if self.subpel else (self._mv, self._err)
+                for i, (v, e) in enumerate(motions):
+                    mv[i].copy_(v)
+                    err[i].copy_(e)
             if self.level == AUTO:
                 self._noise(n, dists, size, True)
         self._blend(cur, refs, dists, size, out)
@@ -194,6 +228,14 @@ class TemporalFilter:
         self._pyramid(ref, size, n + 1)
         self._motion(n, [n + 1], size)
         return self._mv[0].clone(), self._err[0].clone()
+
+    def motion_subpel(self, cur, ref, size):
+        """the refined vectors and errors of one reference (a subpel 1 or 2 object): (mvq int16 [gh, gw, 2] as (y, x) in
+        quarter pels, errq int32 [gh, gw]), new tensors"""
+        if not self.subpel:
+            raise ValueError("motion_subpel() needs an object made with subpel 1 or 2")
+        self.motion(cur, ref, size)
+        return self._mvq[0].clone(), self._errq[0].clone()
 
     def pyramid(self, x, size):
         """Q0 | Q1 | Q2 of x's luma as one int16 tensor holding the uint16 codes (a new tensor)"""
