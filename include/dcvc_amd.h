@@ -600,6 +600,27 @@ int64_t dcvc_frame_analysis_ws_bytes(int H, int W);
 int dcvc_frame_analyze(int dtype, const void* luma, int64_t ld, int H, int W, const uint16_t* lowres_prev,
                        uint16_t* lowres_out, void* workspace, uint64_t* out_host, void* stream);
 /* ------------------------------------------------------------------------------------------
+ * Pair cost of the frame lookahead (csrc/dcvc_lookahead.hip; docs/lookahead.md is the normative text; no reference
+ * counterpart).  cur, ref: two low-resolution planes as dcvc_frame_analyze writes them, uint16 [bh][bw], rows contiguous
+ * (any uint16 values are taken).  Integers throughout, so the result does not depend on the reduction order.  With
+ * n = bh * bw, per plane mean = (sum L + n / 2) / n and ac = sum |L - mean|;
+ *   w = ac_ref == 0 ? 64 : clamp((64 * ac_cur + ac_ref / 2) / ac_ref, 0, 255)
+ *   o = mean_cur - ((mean_ref * w + 32) >> 6)
+ *   wp(r) = clamp(((r * w + 32) >> 6) + o, 0, 65535)
+ * Tiles are 8 x 8 plane samples (partial at the right and bottom edge: the samples that exist), candidates (dy, dx) in
+ * [-3, 3]^2 with the reference coordinates clamped to the plane:
+ *   mc = sum over the tiles of the smallest over the candidates of sum |cur[y][x] - ref[y + dy][x + dx]|
+ *   wp = the same with wp(ref[..]) in place of ref[..]
+ * out_host (dcvc_host_alloc memory, 8 words): mc, wp, w, o (two's complement), mean_cur, ac_cur, mean_ref, ac_ref - written
+ * by the last of the three kernels, valid for the host once the stream has passed that point; the call does not wait for the
+ * device, and w and o are derived on the device (no host read between the moments and the search).  workspace: device, 8-byte
+ * aligned, dcvc_lookahead_ws_bytes(bh, bw) bytes (< 0: bad size).  cur and ref may be the same plane.  Argument errors
+ * (checked before any device work, nothing is launched; the message names the operand): bh or bw below 1 or more than
+ * 2^24 samples in all; a null or misaligned cur, ref, workspace or out_host. */
+int64_t dcvc_lookahead_ws_bytes(int bh, int bw);
+int dcvc_lookahead_cost(const uint16_t* cur, const uint16_t* ref, int bh, int bw, void* workspace, uint64_t* out_host,
+                        void* stream);
+/* ------------------------------------------------------------------------------------------
  * Payload size estimate for rate control (csrc/dcvc_rate.hip; no reference counterpart).  The sum of the code lengths of
  * one frame's symbols under the quantised CDF tables, in Q16 bits, all in integer arithmetic (independent of the
  * reduction order).  Cost tables (device, uint32, built on the host in fp64 - entropy.cost_table):

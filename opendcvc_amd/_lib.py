@@ -172,6 +172,8 @@ _SIGS = {
     "dcvc_tf_blend_subpel": (_I, [_I, _P, POINTER(_P), POINTER(_I), _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "dcvc_frame_analysis_ws_bytes": (_L, [_I, _I]),
     "dcvc_frame_analyze": (_I, [_I, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
+    "dcvc_lookahead_ws_bytes": (_L, [_I, _I]),
+    "dcvc_lookahead_cost": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "dcvc_rate_estimate_ws_bytes": (_L, [_I, _I, _I]),
     "dcvc_rate_estimate": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "dcvc_state_digest_ws_bytes": (_L, [_L]),

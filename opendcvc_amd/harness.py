@@ -409,15 +409,20 @@ def make_source(src_type, path, width, height):
 
 
 # ---------------------------------------------------------------------------------- one rate point
-def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, tf_level=0, tf_radius=2, tf_subpel=0):
+def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, tf_level=0, tf_radius=2, tf_subpel=0,
+                 lookahead=0):
     """every frame of `src` through a SequenceEncoder(**enc_kw) into the container; coded: None or the (height, width) the
     frames are resampled down to first; grain: None, a GrainParams, or "auto" (estimated at every I frame from the full-size
     input against the reconstruction at that size, the unit's seed the frame's index); tf_level 1 .. 5 or "auto": the frames pass
     a prefilter.TemporalFilter (vectors refined to half / quarter pels with tf_subpel 1 / 2) at source size first, which reads
     tf_radius frames ahead - grain "auto" is still given the UNFILTERED
     input of the frame being coded.  The clock of a frame spans loader, temporal filter, down-resample, encode and
-    write_frame; the file read and the copy to the device stay outside.
-    -> (encoder, stream bytes, frame types, bits, times, the Resampler, the FilmGrain and the TemporalFilter made here or None)"""
+    write_frame; the file read and the copy to the device stay outside.  lookahead N > 0: the frames the encoder is to see
+    (filtered, resampled) pass a lookahead.Lookahead of depth N, which holds N of them back and hands each to the encoder with
+    its cut decision; its delay adds to the temporal filter's, and a frame's clock and its unfiltered input follow it through
+    both queues.
+    -> (encoder, stream bytes, frame types, bits, times, the Resampler, the FilmGrain and the TemporalFilter made here or None;
+    with lookahead the Lookahead as a ninth)"""
     import torch
     from .grain import FilmGrain
     from .resize import Resampler
@@ -439,12 +444,30 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
     writer = StreamWriter(out, display=size + (scale_filter,) if coded else None)
     two = use_two_entropy_coders(ch, cw)
 
+    la = None
+    if lookahead:
+        from .lookahead import Lookahead
+        la = Lookahead(dev, lookahead, enc.scenecut)
+        held = []                                        # (unfiltered input, seconds on the clock so far) of the frames held back
+
     def code(x_source, x, t0):
         """x (the frame as the encoder is to see it at source size) from the clock reading t0 on"""
-        source[:] = [x_source]                           # "auto": the full-size unfiltered input of the frame being coded
         if scaler:
             x = scaler.resample(x, size, (ch, cw), scale_filter)
-        pkt = enc.encode(x)
+        if la is None:
+            return emit(x_source, x, t0)
+        if tf is not None and not scaler:
+            x = x.clone()                                # (the filter's output buffers come round again before the frame is coded)
+        done = la.push(x)
+        torch.cuda.synchronize(dev)
+        held.append((x_source, time.time() - t0))
+        for y, cut in done:
+            y_source, spent = held.pop(0)
+            emit(y_source, y, time.time() - spent, cut)
+
+    def emit(x_source, x, t0, cut=None):
+        source[:] = [x_source]                           # "auto": the full-size unfiltered input of the frame being coded
+        pkt = enc.encode(x) if cut is None else enc.encode(x, cut=cut)
         bits.append(8 * writer.write_frame(ch, cw, two, pkt))
         torch.cuda.synchronize(dev)
         times.append(time.time() - t0)
@@ -475,8 +498,14 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
             x_source, spent = waiting.pop(0)
             code(x_source, y, t0 - spent)
             t0 = time.time()
+    if la is not None:
+        t0 = time.time()
+        for y, cut in la.flush():
+            y_source, spent = held.pop(0)
+            emit(y_source, y, t0 - spent, cut)
+            t0 = time.time()
     reader.close()
-    return enc, out.getvalue(), frame_types, bits, times, scaler, grainer, tf
+    return (enc, out.getvalue(), frame_types, bits, times, scaler, grainer, tf) + ((la,) if la is not None else ())
 
 
 def _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, device_metrics, rec_path, scaler, grainer):
@@ -525,7 +554,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
                   src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
                   target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3", film_grain=None,
-                  temporal_filter=0, tf_radius=2, tf_subpel=0):
+                  temporal_filter=0, tf_radius=2, tf_subpel=0, lookahead=0):
     """Encodes `frame_num` frames of a source (src_type: SRC_TYPES - a planar 8-bit YUV 4:2:0 file, a directory of PNGs, a raw
     file in a pipeline.PIXEL_FORMATS format) into the reference's container (optionally written to bin_path), decodes the
     container again and returns the reference-schema log (summarize) plus one group of keys per extension switched on.
@@ -541,8 +570,10 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
       film_grain                   docs/film_grain.md (None, "auto", a GrainParams)   log: grain_units, grain_scale_y, grain_corr
       temporal_filter, tf_radius   docs/temporal_filter.md (level 0 = off .. 5; 1, 2)  log: tf_level, tf_radius, tf_mean_weight
                                    level "auto": chosen per frame from a noise estimate   log: + tf_levels, tf_noise
-      tf_subpel                    its vectors in whole (0), half (1) or quarter pels (2)     log: + tf_subpel where not 0"""
+      tf_subpel                    its vectors in whole (0), half (1) or quarter pels (2)     log: + tf_subpel where not 0
+      lookahead                    docs/lookahead.md (0 = off .. 16 frames; needs scenecut)   log: lookahead, flashes, fades"""
     from .grain import GrainParams
+    from .lookahead import check_depth
     from .prefilter import check_options, check_subpel
     from .resize import FILTERS, check_coded_size
     for name, value, choices in (("metrics", metrics, ("host", "device")), ("entropy", entropy, ("host", "device")),
@@ -554,6 +585,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         raise ValueError(f"film_grain {film_grain!r}: None, 'auto' or a GrainParams")
     temporal_filter, tf_radius = check_options(temporal_filter, tf_radius)
     tf_subpel = check_subpel(tf_subpel)
+    if check_depth(lookahead) and not scenecut:
+        raise ValueError("lookahead decides the scene cuts of scenecut: give scenecut too")
     src = make_source(src_type, src_path, width, height)
     import torch
     dev, nets = torch.device(device), (i_net, p_net)
@@ -571,10 +604,10 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         i_net.rate_estimate = p_net.rate_estimate = False       # (one pair codes every point)
     if digest:
         enc_kw["digest"] = True
-    enc, stream, frame_types, bits, enc_time, scaler, grainer, tf = _encode_pass(nets, src, frame_num, dev, coded_size,
-                                                                                 scale_filter, film_grain, enc_kw,
-                                                                                 temporal_filter, tf_radius,
-                                                                                 **({"tf_subpel": tf_subpel} if tf_subpel else {}))
+    extra = dict({"tf_subpel": tf_subpel} if tf_subpel else {}, **({"lookahead": lookahead} if lookahead else {}))
+    enc, stream, frame_types, bits, enc_time, scaler, grainer, tf, *la = _encode_pass(nets, src, frame_num, dev, coded_size,
+                                                                                      scale_filter, film_grain, enc_kw,
+                                                                                      temporal_filter, tf_radius, **extra)
     if bin_path:
         with open(bin_path, "wb") as f:
             f.write(stream)
@@ -587,6 +620,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                     avg_decoding_time=sum(dec_time[10:]) / len(dec_time[10:]) if timed else None)
     if scenecut:
         log["scene_cuts"] = list(enc.scene_cuts)
+    if la:
+        log.update(lookahead=lookahead, flashes=list(la[0].flashes), fades=list(la[0].fades))
     if target_bpp:
         log.update(_rate_log(enc, float(target_bpp), frame_num, height * width, verbose_json))
     if digest:
@@ -612,7 +647,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
 # manifest_options all go through point_kwargs, so a new option is one row here, one build_parser line under the same name and
 # its hook in run_one_point.  target_bpp is not one of them: it is worked out per sequence (target_bpp()).  Nor
 # are temporal_filter / tf_radius / tf_subpel: they act in front of the encoder, not on a rate point, and the table's names are pinned
-# (tests/test_harness_options.py), so they travel target_bpp's way - prefilter_kwargs(), passed beside point_kwargs().
+# (tests/test_harness_options.py), so they travel target_bpp's way - prefilter_kwargs(), passed beside point_kwargs().  lookahead goes the same way: lookahead_kwargs().
 POINT_OPTIONS = (("verbose", 0, None), ("verbose_json", False, bool), ("calc_ssim", False, bool), ("metrics", "host", None),
                  ("entropy", "host", None), ("scenecut", 0, None), ("min_keyint", 4, None), ("digest", False, bool),
                  ("coded_size", None, None), ("scale_filter", "lanczos3", None), ("film_grain", None, None))
@@ -632,6 +667,12 @@ def prefilter_kwargs(opts):
     if opts.get("tf_subpel"):
         kw["tf_subpel"] = opts["tf_subpel"]
     return kw
+
+
+def lookahead_kwargs(opts):
+    """an options mapping -> run_one_point's keyword of the frame lookahead; missing or None: 0, off.  Like the pre-filter's it
+    acts in front of the encoder and travels beside point_kwargs()"""
+    return {"lookahead": opts.get("lookahead") or 0}
 
 
 def run_sweep(make_nets, src_path, width, height, frame_num, rate_num=4, qp_i=None, qp_p=None, bin_prefix=None, **kw):
@@ -834,7 +875,7 @@ def run_job(nets, job, opts):
                         job["qp_i"], job["qp_p"], intra_period=job["intra_period"], reset_interval=job["reset_interval"],
                         bin_path=bin_path, rec_path=rec_path, device="cuda:0", src_type=job.get("src_type", "yuv420"),
                         target_bpp=target_bpp(opts, job["src_width"], job["src_height"]), **prefilter_kwargs(opts),
-                        **point_kwargs(opts))
+                        **lookahead_kwargs(opts), **point_kwargs(opts))
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -889,6 +930,11 @@ def check_rate_options(args, ap):
     args.rate_num = 1
 
 
+def check_lookahead_options(args, ap):
+    if args.lookahead and not args.scenecut:
+        ap.error("--lookahead decides the scene cuts of --scenecut: give --scenecut too (150 is recommended)")
+
+
 def _str2bool(v):
     """the reference's str2bool (test_video.py:24-28): --flag 1 / true / yes / y / t"""
     if isinstance(v, bool):
@@ -902,7 +948,7 @@ def _str2bool(v):
 
 def _add_extension_options(ap, flag):
     """this project's options beyond the reference's: adaptive I frames, rate control, digests, reduced resolution, film grain,
-    the temporal pre-filter"""
+    the temporal pre-filter, the frame lookahead"""
     from .resize import FILTERS, parse_size
     ap.add_argument("--scenecut", type=int, default=0, metavar="PCT",
                     help="adaptive I frames: a frame whose low-resolution difference to its predecessor is at least PCT percent "
@@ -910,6 +956,10 @@ def _add_extension_options(ap, flag):
                          "--intra-period and --reset-interval then count from the most recent I frame")
     ap.add_argument("--min-keyint", "--min_keyint", type=int, default=4, metavar="N",
                     help="with --scenecut: a cut fewer than N frames after the last I frame is coded as a P frame")
+    ap.add_argument("--lookahead", type=int, default=0, choices=range(0, 17), metavar="N",
+                    help="with --scenecut: decide every frame's cut with N more frames in view (0 = off, up to 16; 4 is "
+                         "recommended): a flash, a fade and a pan no longer cost an I frame (docs/lookahead.md).  Encoder side "
+                         "only, the stream format is unchanged; the encoder reads N frames ahead")
     ap.add_argument("--target-bpp", "--target_bpp", type=float, default=None, metavar="X",
                     help="target-bitrate control: aim at X bits per pixel (one rate point; --qp-i / --qp-p give the starting qp)")
     ap.add_argument("--target-kbps", "--target_kbps", type=float, default=None, metavar="K",
@@ -1027,7 +1077,7 @@ def manifest_options(args, ap):
     opts = {k: getattr(args, k) for k in ("rate_num", "qp_i", "qp_p", "force_root_path", "force_frame_num", "force_intra_period",
                                           "reset_interval", "model_i", "model_p", "force_zero_thres", "fp32", "target_bpp",
                                           "target_kbps", "fps", "force_intra", "check_existing", "save_decoded_frame",
-                                          "temporal_filter", "tf_radius", "tf_subpel")}
+                                          "temporal_filter", "tf_radius", "tf_subpel", "lookahead")}
     opts.update(gpu_ids=gpu_ids, stream_path=stream_path, **point_kwargs(vars(args)))
     return opts, gpus
 
@@ -1036,6 +1086,7 @@ def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
     check_rate_options(args, ap)
+    check_lookahead_options(args, ap)
     if args.test_config:
         with open(args.test_config) as f:
             config = json.load(f)
@@ -1060,7 +1111,7 @@ def main(argv=None):
                     args.src, args.width, args.height, args.frames, args.rate_num, args.qp_i or None, args.qp_p or None,
                     bin_prefix=args.bin_prefix, intra_period=args.intra_period, reset_interval=args.reset_interval,
                     src_type=args.src_type, target_bpp=target_bpp(vars(args), args.width, args.height),
-                    **prefilter_kwargs(vars(args)), **point_kwargs(vars(args)))
+                    **prefilter_kwargs(vars(args)), **lookahead_kwargs(vars(args)), **point_kwargs(vars(args)))
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:

@@ -43,6 +43,9 @@ class SequenceEncoder:
     whose cut was honoured with an I frame (also where the period asked for one at the same frame).  encode(x, ready):
     `ready` is a torch.cuda.Event recorded where x became ready, so the analysis need not wait for the kernels of the
     previous frame that defer_stream keeps in flight.  analyzer: any object with analyze(x, ready) -> FrameStats.
+    encode(x, cut=True / False) takes the caller's word in place of is_cut(stats, scenecut) and runs no analyzer for that
+    frame (lookahead.Lookahead decides with later frames in view); g, min_keyint, intra_period, reset_interval and scene_cuts
+    stay the encoder's.  cut=None is the analysis above; without scenecut a cut= is refused (ValueError).
 
     rate (a ratecontrol.RateController, None = off: the fixed qp_i / qp_p above, nothing launched): target-bitrate control.
     Both models then estimate every frame's payload size on the device (their rate_estimate attribute is set); before a
@@ -96,11 +99,13 @@ class SequenceEncoder:
             i_net.rate_estimate = p_net.rate_estimate = True
         p_net.set_curr_poc(0)
 
-    def encode(self, x_padded, ready=None):
+    def encode(self, x_padded, ready=None, cut=None):
         from .models import CAPTURE_GUARD
+        if cut is not None and not self.scenecut:
+            raise ValueError("encode(cut=...) places adaptive I frames: it needs an encoder made with scenecut")
         with CAPTURE_GUARD.frame():          # (a HIP graph capture on another thread waits for / holds back this frame)
             if self.scenecut:
-                return self._sized(self._encode_adaptive(x_padded, ready))
+                return self._sized(self._encode_adaptive(x_padded, ready, cut))
             return self._sized(self._encode(x_padded))
 
     def _sized(self, pkts):
@@ -165,16 +170,20 @@ class SequenceEncoder:
         self.frame_idx += 1
         return self._code(x_padded, fi == 0 or (self.intra_period > 0 and fi % self.intra_period == 0), fi)
 
-    def _encode_adaptive(self, x_padded, ready):
-        from .analysis import is_cut
-        if self._analyzer is None:
-            from .analysis import FrameAnalyzer
-            self._analyzer = FrameAnalyzer(x_padded.device)
+    def _encode_adaptive(self, x_padded, ready, cut=None):
         fi = self.frame_idx
         self.frame_idx += 1
-        stats = self._analyzer.analyze(x_padded, ready)          # every frame: the next one needs this one's plane
+        if cut is None:
+            from .analysis import is_cut
+            if self._analyzer is None:
+                from .analysis import FrameAnalyzer
+                self._analyzer = FrameAnalyzer(x_padded.device)
+            stats = self._analyzer.analyze(x_padded, ready)      # every frame: the next one needs this one's plane
+            looks_cut = is_cut(stats, self.scenecut)
+        else:
+            looks_cut = bool(cut)                                # the caller's word (lookahead.Lookahead): no analyzer runs
         g = self._gop_pos + 1
-        cut = fi > 0 and g >= self.min_keyint and is_cut(stats, self.scenecut)
+        cut = fi > 0 and g >= self.min_keyint and looks_cut
         is_i = fi == 0 or cut or (self.intra_period > 0 and g == self.intra_period)
         if cut:
             self.scene_cuts.append(fi)
