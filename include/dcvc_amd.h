@@ -70,7 +70,10 @@ void dcvc_dcb_destroy(dcvc_dcb* h);
 size_t dcvc_dcb_scratch_bytes(const dcvc_dcb* h, int H, int W);
 /* x = concat(x0[:, :c0], x1[:, :c1]) (x1 may be NULL, c1 = 0); quant: device float[C] or NULL
  * (forward_with_quant_step, impl.cpp:91-97); out row stride ldo (forward_with_cat, impl.cpp:99-121:
- * the caller points `out` at the channel offset inside the concat buffer). */
+ * the caller points `out` at the channel offset inside the concat buffer).
+ * Sources and outputs of every forward entry below (blocks and convolutions) are read and written in 16-byte vectors:
+ * x0, x1, out 16-byte aligned, ld0, ld1, ldo a multiple of 16 bytes and at least the channels they hold - any channel
+ * slice of a wider map that keeps to this is taken; anything else is an argument error and launches nothing. */
 int dcvc_dcb_forward(const dcvc_dcb* h, const void* x0, int64_t ld0, int c0, const void* x1,
                      int64_t ld1, int c1, int H, int W, const float* quant, void* out, int64_t ldo,
                      void* scratch, void* stream);

@@ -1744,7 +1744,8 @@ int dcvc_dcb_forward_chained(const dcvc_dcb* h, const void* x0, int64_t ld0, int
                      "adaptor there, no shortcut / quant step here)");
     const SrcPair src{x0, (long)ld0, c0, x1, (long)ld1, c1};
     if (int rc = check_src("dcvc_dcb_forward", src, h->cin_p, h->adapt != 0, h->dtype, H, W, head_done != 0)) return rc;
-    DCVC_REQUIRE(ldo >= h->c_p, "dcvc_dcb_forward: output row stride too small");
+    DCVC_REQUIRE(ldo >= h->c_p && ((uintptr_t)out % 16) == 0 && (ldo * dcvc::elem_size(h->dtype)) % 16 == 0,
+                 "dcvc_dcb_forward: output row stride too small or not 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     ChainArgs ch;
     ch.head_done = head_done;
@@ -1928,7 +1929,9 @@ int dcvc_conv_forward_scaled(const dcvc_conv* h, const void* x0, int64_t ld0, in
     cp.epi = h->epi;
     cp.out = out;
     cp.ldo = ldo;
-    DCVC_REQUIRE(ldo >= (h->epi == DCVC_EPI_SHUFFLE2 ? h->cs_p : h->n_p), "dcvc_conv_forward: output row stride too small");
+    DCVC_REQUIRE(ldo >= (h->epi == DCVC_EPI_SHUFFLE2 ? h->cs_p : h->n_p) && ((uintptr_t)out % 16) == 0 &&
+                     (ldo * dcvc::elem_size(h->dtype)) % 16 == 0,
+                 "dcvc_conv_forward: output row stride too small or not 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     return run_conv(h, cp, st);
 }
