@@ -27,54 +27,15 @@
 //                       global ones at the end: no result depends on the order of arrival.
 //   tf_level_kernel     part two, one workgroup: per table the number of positive values and the value of rank n_pos >> 2
 //                       among them (a prefix sum over the bins), the minimum over the tables, the level rule, the totals.
-// No allocation and no synchronisation in any entry point.
-#include "common.hpp"
-#include "frame_host.hpp"
-#include "plane_math.hpp"
+// tf_shared.hpp holds what dcvc_tf_subpel.hip (quarter-pel motion) has in common with this file: constants and argument
+// structs, the blend's arithmetic around its sample fetch, and the host check and launch of the blend entries.  This file owns
+// the gather, tf_blend_kernel's guard (memory is touched only inside the frame) and its loads of all references' vectors and
+// errors ahead of the gathers.  No allocation and no synchronisation in any entry point.
+#include "tf_shared.hpp"
 
 #include <cstdint>
 
 namespace {
-
-constexpr int TB = 256;          // threads per workgroup, every kernel
-constexpr int TW = 64;           // blend: columns of a tile
-constexpr int TH = 32;           // blend: rows of a tile (TB / (TW / 8) threads of 8 columns)
-constexpr int NB = 8;            // motion: blocks per workgroup (32 lanes each)
-constexpr int MAX_REFS = 4;
-constexpr float kScale = 1023.0f;
-
-__device__ __forceinline__ int quant10(float v)
-{
-    // (fmaxf returns the other operand for a NaN: a NaN sample counts as 0) - dcvc_frame_analyze's rule
-    return (int)fminf(fmaxf(rintf(v * kScale), 0.0f), kScale);
-}
-
-struct LevelDims {
-    int h[3], w[3];
-    int64_t off[3];              // first element of a level in a pyramid
-    int gh[3], gw[3];            // its grid of 8 x 8 blocks
-    int64_t elems;
-};
-
-inline LevelDims level_dims(int H, int W)
-{
-    LevelDims d;
-    d.h[0] = H;
-    d.w[0] = W;
-    for (int l = 1; l < 3; ++l) {
-        d.h[l] = (d.h[l - 1] + 1) >> 1;
-        d.w[l] = (d.w[l - 1] + 1) >> 1;
-    }
-    int64_t at = 0;
-    for (int l = 0; l < 3; ++l) {
-        d.off[l] = at;
-        at += (int64_t)d.h[l] * d.w[l];
-        d.gh[l] = (d.h[l] + 7) >> 3;
-        d.gw[l] = (d.w[l] + 7) >> 3;
-    }
-    d.elems = at;
-    return d;
-}
 
 // ---------------------------------------------------------------------------------- pyramid
 template <typename T>
@@ -113,22 +74,14 @@ __global__ __launch_bounds__(TB) void tf_pyramid_kernel(const T* __restrict__ x,
 }
 
 // ---------------------------------------------------------------------------------- motion
-struct TfPyramids {
-    const uint16_t* cur;
-    const uint16_t* ref[MAX_REFS];
-};
-
 struct alignas(16) U16x8 {
     uint16_t v[8];
-};
-struct alignas(16) U32x4 {
-    uint32_t v[4];
 };
 
 // R: the offsets' range (4 at level 2, 2 below).  parent: the coarser level's vectors [ref][ph * pw][2], or nullptr (centre 0).
 // mv [ref][gh * gw][2] as (y, x); err [ref][gh * gw] or nullptr.
 template <int R>
-__global__ __launch_bounds__(TB) void tf_motion_kernel(TfPyramids p, int64_t level_off, int Hl, int Wl, int gh, int gw,
+__global__ __launch_bounds__(TB) void tf_motion_kernel(TfPlanes p, int64_t level_off, int Hl, int Wl, int gh, int gw,
                                                        const int16_t* __restrict__ parent, int ph, int pw,
                                                        int16_t* __restrict__ mv, uint32_t* __restrict__ err)
 {
@@ -211,13 +164,7 @@ __global__ __launch_bounds__(TB) void tf_motion_kernel(TfPyramids p, int64_t lev
 }
 
 // ---------------------------------------------------------------------------------- blend
-struct TfRefs {
-    const void* ref[MAX_REFS];
-    int base[MAX_REFS];          // B: 102 at distance 1, 77 at distance 2
-};
-
-// VEC: cur and out are 16-byte aligned and the row length is a multiple of 16 bytes.  AUTO: the level is the word at level_dev
-// (a compile-time switch: the fixed-level kernel keeps its code; its level_dev is null and not looked at)
+// VEC: cur and out are 16-byte aligned and the row length is a multiple of 16 bytes.  AUTO: blend_level (tf_shared.hpp)
 template <typename T, bool VEC, bool AUTO>
 __global__ __launch_bounds__(TB) void tf_blend_kernel(const int32_t* __restrict__ level_dev, const T* __restrict__ cur, TfRefs refs, int nref, int Hp, int Wp, int H, int W,
                                                       const int16_t* __restrict__ mv, const uint32_t* __restrict__ err, int gh,
@@ -225,41 +172,20 @@ __global__ __launch_bounds__(TB) void tf_blend_kernel(const int32_t* __restrict_
 {
     __shared__ long long s_part[TB / 64];
     const int tid = threadIdx.x, plane = blockIdx.z;
-    if (AUTO) {
-        // One scalar load per workgroup, uniform.  level_dev is the kernel's FIRST parameter and this file is built with the
-        // first two dwords of the kernel arguments preloaded into registers (csrc/Makefile): the pointer is there when a wave
-        // starts, so the word's cold scalar-cache miss runs beside that of the other arguments and not behind it.  With the
-        // pointer fetched like any argument this kernel was 0.2 - 0.45 us slower than the fixed-level one.
-        L = *level_dev;
-        if (L < 1 || L > 5) L = nref = 0;                                    // level 0, or no level at all: every weight is 0
-    }
+    blend_level<AUTO>(level_dev, L, nref);
     const int y = blockIdx.y * TH + (tid >> 3), xc = blockIdx.x * TW + (tid & 7) * 8;
     long long stat = 0;
 
-    if (y < Hp && xc < Wp) {
+    if (y < Hp && xc < Wp) {                                       // (memory is touched only in here)
         const int ye = min(y, H - 1);
         const int by = ye >> 3, bx = min(xc, W - 1) >> 3;          // xc is a multiple of 8: the 8 clamped columns share a block
         const bool full = xc + 8 <= W;
         const int64_t plane_at = (int64_t)plane * Hp * Wp;
-        const T* crow = cur + plane_at + (int64_t)ye * Wp;
         Pix8<T> c;
-        if (VEC && full) {
-            c = *reinterpret_cast<const Pix8<T>*>(crow + xc);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) c.v[i] = crow[min(xc + i, W - 1)];
-        }
         float acc[8];
         int qc[8], wsum[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float f = (float)c.v[i];
-            qc[i] = quant10(f);
-            acc[i] = 256.0f * f;
-            wsum[i] = 256;
-        }
-        const int P = 1 << (3 + L);
-        const long long A = 1ll << (8 + L);
+        const auto col = [&](int i) { return min(xc + i, W - 1); };          // element i stands at this column; the gather adds its vector
+        blend_begin(cur + plane_at + (int64_t)ye * Wp, xc, VEC && full, col, c, acc, qc, wsum);
         const int64_t nblk = (int64_t)gh * gw;
         int mvys[MAX_REFS], mvxs[MAX_REFS], wbs[MAX_REFS];                 // (loaded together: the gathers wait for them)
 #pragma unroll
@@ -269,15 +195,14 @@ __global__ __launch_bounds__(TB) void tf_blend_kernel(const int32_t* __restrict_
                 const int64_t at = r * nblk + (int64_t)by * gw + bx;
                 mvys[r] = mv[2 * at];
                 mvxs[r] = mv[2 * at + 1];
-                const long long E = (long long)err[at];
-                wbs[r] = E < A ? (int)(((long long)refs.base[r] * (A * A - E * E)) >> (16 + 2 * L)) : 0;      // <= 102
+                wbs[r] = block_weight(refs.base[r], err[at], L);
             }
         }
 #pragma unroll
         for (int r = 0; r < MAX_REFS; ++r) {
             if (r >= nref) break;
-            const int mvy = mvys[r], mvx = mvxs[r], wb = wbs[r];
-            const T* rrow = (const T*)refs.ref[r] + plane_at + (int64_t)clampi(ye + mvy, 0, H - 1) * Wp;
+            const int mvx = mvxs[r];
+            const T* rrow = (const T*)refs.ref[r] + plane_at + (int64_t)clampi(ye + mvys[r], 0, H - 1) * Wp;
             const int xs = xc + mvx;
             Pix8<T> rv;
             if (full && xs >= 0 && xs + 8 <= W) {
@@ -289,50 +214,19 @@ __global__ __launch_bounds__(TB) void tf_blend_kernel(const int32_t* __restrict_
                 for (int i = 0; i < 8; ++i) rv.v[i] = row.v[i];
             } else {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) rv.v[i] = rrow[clampi(min(xc + i, W - 1) + mvx, 0, W - 1)];
+                for (int i = 0; i < 8; ++i) rv.v[i] = rrow[clampi(col(i) + mvx, 0, W - 1)];
             }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float f = (float)rv.v[i];
-                int d = qc[i] - quant10(f);
-                d = d < 0 ? -d : d;
-                const int w = d < P ? (wb * (P * P - d * d)) >> (6 + 2 * L) : 0;          // <= wb: 102 * 2^16 fits
-                acc[i] = acc[i] + (float)w * f;
-                wsum[i] += w;
-            }
+            blend_accumulate(rv.v, wbs[r], L, qc, acc, wsum);
         }
-        Pix8<T> o;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float q = acc[i] * (1.0f / (float)wsum[i]);                 // (IEEE division: the fp32 nearest to 1 / Wsum)
-            o.v[i] = wsum[i] == 256 ? c.v[i] : to_t<T>(q);
-        }
-        T* orow = out + plane_at + (int64_t)y * Wp;
-        if (VEC && xc + 8 <= Wp) {
-            *reinterpret_cast<Pix8<T>*>(orow + xc) = o;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (xc + i < Wp) orow[xc + i] = o.v[i];
-        }
-        if (plane == 0 && y < H) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (xc + i < W) stat += wsum[i] - 256;
-        }
+        stat = blend_finish<T, VEC>(c, acc, wsum, out + plane_at + (int64_t)y * Wp, xc, Wp, W, plane == 0 && y < H);
     }
-    if (plane == 0) {                                                        // (uniform over the workgroup)
-        stat = wave_sum(stat);
-        if ((tid & 63) == 0) s_part[tid >> 6] = stat;
-        __syncthreads();
-        if (tid == 0) {
-            long long s = 0;
-#pragma unroll
-            for (int i = 0; i < TB / 64; ++i) s += s_part[i];
-            if (s != 0) atomicAdd(total, (unsigned long long)s);
-        }
-    }
+    if (plane == 0) blend_total(stat, s_part, total);                        // (uniform over the workgroup)
 }
+
+struct GatherBlend {             // names the kernel for dcvc::blend
+    template <typename T, bool VEC, bool AUTO>
+    static auto kernel() { return &tf_blend_kernel<T, VEC, AUTO>; }
+};
 
 // ---------------------------------------------------------------------------------- noise estimate
 constexpr int BINS = 4096;       // a block value is clipped to BINS - 1
@@ -460,12 +354,6 @@ __global__ __launch_bounds__(TB) void tf_level_kernel(const uint32_t* __restrict
     }
 }
 
-bool overlaps(const void* a, const void* b, uint64_t bytes)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + bytes && pb < pa + bytes;
-}
-
 }  // namespace
 
 extern "C" {
@@ -504,16 +392,10 @@ int dcvc_tf_motion(const uint16_t* cur_pyramid, const uint16_t* const* ref_pyram
     const char* who = "dcvc_tf_motion";
     DCVC_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 30), "%s: bad size %d x %d", who, H, W);
     DCVC_REQUIRE(nref >= 1 && nref <= MAX_REFS, "%s: %d references, 1 .. %d are supported", who, nref, MAX_REFS);
-    DCVC_REQUIRE(cur_pyramid && ref_pyramids && mv && err && ws, "%s: null pointer", who);
-    TfPyramids p = {};
-    p.cur = cur_pyramid;
-    for (int r = 0; r < nref; ++r) {
-        DCVC_REQUIRE(ref_pyramids[r], "%s: null pointer", who);
-        DCVC_REQUIRE(((uintptr_t)ref_pyramids[r] & 1) == 0, "%s: a pyramid is not 2-byte aligned", who);
-        p.ref[r] = ref_pyramids[r];
-    }
-    DCVC_REQUIRE(((uintptr_t)cur_pyramid & 1) == 0 && ((uintptr_t)mv & 1) == 0 && ((uintptr_t)ws & 1) == 0,
-                 "%s: a pointer is not 2-byte aligned", who);
+    DCVC_REQUIRE(mv && err && ws, "%s: null pointer", who);
+    TfPlanes p;
+    if (int rc = dcvc::check_planes(who, cur_pyramid, ref_pyramids, nref, p)) return rc;
+    DCVC_REQUIRE(((uintptr_t)mv & 1) == 0 && ((uintptr_t)ws & 1) == 0, "%s: a pointer is not 2-byte aligned", who);
     DCVC_REQUIRE(((uintptr_t)err & 3) == 0, "%s: err is not 4-byte aligned", who);
     const LevelDims d = level_dims(H, W);
     int16_t* mv1 = (int16_t*)ws;                                             // [MAX_REFS][gh1 * gw1][2]
@@ -564,59 +446,10 @@ int dcvc_tf_noise(const uint16_t* cur_pyramid, const uint32_t* err, const int* d
     return 0;
 }
 
-}  // extern "C"
-
-namespace {
-
-// dcvc_tf_blend (level_dev null: the level is the argument) and dcvc_tf_blend_auto (level_dev checked there; level not looked at)
-int blend(const char* who, int dtype, const void* cur_nchw, const void* const* refs_nchw, const int* dists, int nref, int Hp, int Wp,
-          int H, int W, const int16_t* mv, const uint32_t* err, int level, const int32_t* level_dev, void* out_nchw,
-          uint64_t* weight_sum, void* stream)
-{
-    if (int rc = dcvc::check_frame(who, "the current frame", dtype, cur_nchw, Hp, Wp, H, W)) return rc;
-    if (int rc = dcvc::check_frame(who, "out", dtype, out_nchw, Hp, Wp, H, W)) return rc;
-    DCVC_REQUIRE(level_dev || (level >= 1 && level <= 5), "%s: level %d outside 1 .. 5", who, level);
-    DCVC_REQUIRE(nref >= 0 && nref <= MAX_REFS, "%s: %d references, at most %d are supported", who, nref, MAX_REFS);
-    DCVC_REQUIRE(weight_sum && (nref == 0 || (refs_nchw && dists && mv && err)), "%s: null pointer", who);
-    DCVC_REQUIRE((int64_t)H * W < ((int64_t)1 << 30), "%s: picture too large", who);
-    const size_t es = dcvc::elem_size(dtype);
-    const uint64_t bytes = (uint64_t)3 * Hp * Wp * es;
-    DCVC_REQUIRE(!overlaps(out_nchw, cur_nchw, bytes), "%s: out overlaps the current frame (neighbours are read)", who);
-    TfRefs refs = {};
-    for (int r = 0; r < nref; ++r) {
-        if (int rc = dcvc::check_frame(who, "a reference", dtype, refs_nchw[r], Hp, Wp, H, W)) return rc;
-        DCVC_REQUIRE(!overlaps(out_nchw, refs_nchw[r], bytes), "%s: out overlaps reference %d (neighbours are read)", who, r);
-        DCVC_REQUIRE(dists[r] == 1 || dists[r] == -1 || dists[r] == 2 || dists[r] == -2, "%s: distance %d is not +-1 or +-2", who,
-                     dists[r]);
-        refs.ref[r] = refs_nchw[r];
-        refs.base[r] = (dists[r] == 1 || dists[r] == -1) ? 102 : 77;
-    }
-    DCVC_REQUIRE(((uintptr_t)mv & 1) == 0 && ((uintptr_t)err & 3) == 0 && ((uintptr_t)weight_sum & 7) == 0,
-                 "%s: mv, err or the weight sum is not aligned to its element size", who);
-    dim3 grid;
-    if (int rc = dcvc::tile_grid(who, Wp, Hp, TW, TH, grid)) return rc;
-    const LevelDims d = level_dims(H, W);
-    const bool vec = dcvc::vec_ok(16 / (int)es, es, Wp, cur_nchw, out_nchw);
-    unsigned long long* total = reinterpret_cast<unsigned long long*>(weight_sum);
-    return dcvc::typed(dtype, [&](auto tag) {
-        using T = decltype(tag);
-        dcvc::with_flag(vec, [&](auto v) {
-            dcvc::with_flag(level_dev != nullptr, [&](auto a) {
-                tf_blend_kernel<T, decltype(v)::value, decltype(a)::value><<<grid, TB, 0, (hipStream_t)stream>>>(
-                    level_dev, (const T*)cur_nchw, refs, nref, Hp, Wp, H, W, mv, err, d.gh[0], d.gw[0], level, (T*)out_nchw, total);
-            });
-        });
-    });
-}
-
-}  // namespace
-
-extern "C" {
-
 int dcvc_tf_blend(int dtype, const void* cur_nchw, const void* const* refs_nchw, const int* dists, int nref, int Hp, int Wp, int H,
                   int W, const int16_t* mv, const uint32_t* err, int level, void* out_nchw, uint64_t* weight_sum, void* stream)
 {
-    return blend("dcvc_tf_blend", dtype, cur_nchw, refs_nchw, dists, nref, Hp, Wp, H, W, mv, err, level, nullptr, out_nchw,
+    return dcvc::blend("dcvc_tf_blend", GatherBlend{}, dtype, cur_nchw, refs_nchw, dists, nref, Hp, Wp, H, W, mv, err, level, nullptr, out_nchw,
                  weight_sum, stream);
 }
 
@@ -625,7 +458,7 @@ int dcvc_tf_blend_auto(int dtype, const void* cur_nchw, const void* const* refs_
                        uint64_t* weight_sum, void* stream)
 {
     DCVC_REQUIRE(level_dev && ((uintptr_t)level_dev & 3) == 0, "dcvc_tf_blend_auto: the level's word is null or not 4-byte aligned");
-    return blend("dcvc_tf_blend_auto", dtype, cur_nchw, refs_nchw, dists, nref, Hp, Wp, H, W, mv, err, 0, level_dev, out_nchw,
+    return dcvc::blend("dcvc_tf_blend_auto", GatherBlend{}, dtype, cur_nchw, refs_nchw, dists, nref, Hp, Wp, H, W, mv, err, 0, level_dev, out_nchw,
                  weight_sum, stream);
 }
 

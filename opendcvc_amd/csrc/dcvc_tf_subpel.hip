@@ -1,6 +1,7 @@
 // dcvc_tf_subpel.hip - quarter-pel motion for the temporal pre-filter (docs/temporal_filter.md, "Quarter-pel motion", the
 // normative text; tests/tf_subpel_ref.py restates it in numpy).  Opt-in: with the option off nothing of this file is launched
-// and dcvc_tf.hip's kernels, which this file does not touch, do all the work.  Encoder side only.
+// and dcvc_tf.hip's kernels do all the work.  Encoder side only.  Its own translation unit: dcvc_tf.hip is built with a kernarg
+// preload this file's kernels do not want; what the two share is tf_shared.hpp's.
 //   tf_refine_kernel        one launch, the reference in gridDim.z.  32 lanes per 8 x 8 block, eight blocks per workgroup, as in
 //                           the whole-pel search.  The block of the current Q0 and the 16 x 16 window of the reference's Q0
 //                           around the whole-pel vector (rows / columns -4 .. 11 of the block: every tap of every candidate of
@@ -16,28 +17,20 @@
 //                           all of whose blocks have a level-0 SAD of 0 writes its centres and leaves: nothing ranks below
 //                           R = 0 at distance 0 (static and clean integer-pel material costs a load per block).
 //   tf_blend_subpel_kernel  dcvc_tf_blend's launch shape (a workgroup per 32 x 64 tile of a plane, a thread per row of a block),
-//                           arithmetic and statistic, with the reference sample interpolated in fp32.  The eight threads of a
+//                           arithmetic and statistic (tf_shared.hpp's), with the reference sample interpolated in fp32.  The eight threads of a
 //                           block share its 15 source rows: each filters at most two of them horizontally (15 contiguous
 //                           samples -> 8 values, straight from memory: a source sample is loaded once per block) into LDS, and
 //                           after a barrier runs the vertical pass down its own column of 8 x 8 values.  A block with a whole
 //                           vertical part (fy == 0) needs its own row only and stays in registers; with fx == 0 too that is
 //                           the direct gather.  Multiplies and adds are separate fp32 operations in the document's order.
 // No allocation and no synchronisation in any entry point.
-#include "common.hpp"
-#include "frame_host.hpp"
-#include "plane_math.hpp"
+#include "tf_shared.hpp"
 
 #include <cstdint>
 
 namespace {
 
-constexpr int TB = 256;          // threads per workgroup
-constexpr int TW = 64;           // blend: columns of a tile
-constexpr int TH = 32;           // blend: rows of a tile
-constexpr int NB = 8;            // refinement: blocks per workgroup (32 lanes each)
 constexpr int RW = 16;           // refinement: side of the reference window
-constexpr int MAX_REFS = 4;
-constexpr float kScale = 1023.0f;
 
 // C[f][k]: the HEVC luma filters; tap k applies to the sample at offset k - 3
 #define DCVC_TF_TAPS {{0, 0, 0, 64, 0, 0, 0, 0}, {-1, 4, -10, 58, 17, -5, 1, 0}, {-1, 4, -11, 40, 40, -11, 4, -1}, {0, 1, -5, 17, 58, -10, 4, -1}}
@@ -48,24 +41,9 @@ constexpr int tap(int f, int k)                           // (the same table whe
     return C[f][k];
 }
 
-__device__ __forceinline__ int quant10(float v)
-{
-    // dcvc_tf.hip's, dcvc_frame_analyze's rule (a NaN counts as 0)
-    return (int)fminf(fmaxf(rintf(v * kScale), 0.0f), kScale);
-}
-
 // ---------------------------------------------------------------------------------- refinement
-struct alignas(16) U32x4 {
-    uint32_t v[4];
-};
-
-struct TfQ0 {
-    const uint16_t* cur;         // a pyramid begins with its Q0
-    const uint16_t* ref[MAX_REFS];
-};
-
 // stages: 1 (half pel) or 2 (then quarter pel).  mv / err: dcvc_tf_motion's; mvq [ref][gh * gw][2], errq [ref][gh * gw]
-__global__ __launch_bounds__(TB) void tf_refine_kernel(TfQ0 p, int H, int W, int gh, int gw, int stages,
+__global__ __launch_bounds__(TB) void tf_refine_kernel(TfPlanes p, int H, int W, int gh, int gw, int stages,
                                                        const int16_t* __restrict__ mv, const uint32_t* __restrict__ err,
                                                        int16_t* __restrict__ mvq, uint32_t* __restrict__ errq)
 {
@@ -209,11 +187,6 @@ __global__ __launch_bounds__(TB) void tf_refine_kernel(TfQ0 p, int H, int W, int
 }
 
 // ---------------------------------------------------------------------------------- blend
-struct TfRefs {
-    const void* ref[MAX_REFS];
-    int base[MAX_REFS];          // B: 102 at distance 1, 77 at distance 2
-};
-
 // the phase-F filter of v[0 .. 7]: the sum over the non-zero taps in rising order, begun with the first product, times 1 / 64
 template <int F>
 __device__ __forceinline__ float taps8(const float* v)
@@ -262,7 +235,7 @@ __device__ __forceinline__ void filter_row(const T* __restrict__ rrow, int xbase
         if (i > hx) g[i] = g[i - 1];
 }
 
-// VEC: cur and out are 16-byte aligned and the row length is a multiple of 16 bytes.  AUTO: the level is the word at level_dev
+// VEC, AUTO: as in tf_blend_kernel
 template <typename T, bool VEC, bool AUTO>
 __global__ __launch_bounds__(TB) void tf_blend_subpel_kernel(const int32_t* __restrict__ level_dev, const T* __restrict__ cur, TfRefs refs, int nref, int Hp, int Wp,
                                                              int H, int W, const int16_t* __restrict__ mvq, const uint32_t* __restrict__ errq,
@@ -271,10 +244,7 @@ __global__ __launch_bounds__(TB) void tf_blend_subpel_kernel(const int32_t* __re
     __shared__ long long s_part[TB / 64];
     __shared__ float s_g[TB / 8][15][8];                  // [block of the tile][source row][position column]
     const int tid = threadIdx.x, plane = blockIdx.z;
-    if (AUTO) {
-        L = *level_dev;                                   // one scalar load per workgroup, uniform
-        if (L < 1 || L > 5) L = nref = 0;                 // level 0, or no level at all: every weight is 0
-    }
+    blend_level<AUTO>(level_dev, L, nref);
     // Every thread works at clamped coordinates, also one whose row or columns lie outside the frame: the eight threads of a
     // block filter its source rows for each other.  Only the store and the statistic look at where the thread is.
     const int y = blockIdx.y * TH + (tid >> 3), xc = blockIdx.x * TW + (tid & 7) * 8;
@@ -284,31 +254,15 @@ __global__ __launch_bounds__(TB) void tf_blend_subpel_kernel(const int32_t* __re
     const bool full = xc + 8 <= W;
     const int slot = (tid >> 6) * 8 + (tid & 7), t = (tid >> 3) & 7;
     const int64_t plane_at = (int64_t)plane * Hp * Wp;
-    const T* crow = cur + plane_at + (int64_t)ye * Wp;
     Pix8<T> c;
-    if (VEC && full) {
-        c = *reinterpret_cast<const Pix8<T>*>(crow + xc);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) c.v[i] = crow[xe + min(i, hx)];
-    }
     float acc[8];
     int qc[8], wsum[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float f = (float)c.v[i];
-        qc[i] = quant10(f);
-        acc[i] = 256.0f * f;
-        wsum[i] = 256;
-    }
-    const int P = 1 << (3 + L);
-    const long long A = 1ll << (8 + L);
+    blend_begin(cur + plane_at + (int64_t)ye * Wp, xc, VEC && full, [&](int i) { return xe + min(i, hx); }, c, acc, qc, wsum);
     const int64_t nblk = (int64_t)gh * gw;
     for (int r = 0; r < nref; ++r) {                      // (nref is uniform over the workgroup: so are the barriers)
         const int64_t at = r * nblk + (int64_t)by * gw + bx;
         const int my = mvq[2 * at], mx = mvq[2 * at + 1];
-        const long long E = (long long)errq[at];
-        const int wb = E < A ? (int)(((long long)refs.base[r] * (A * A - E * E)) >> (16 + 2 * L)) : 0;      // <= 102
+        const int wb = block_weight(refs.base[r], errq[at], L);
         const int iy = my >> 2, fy = my & 3, ix = mx >> 2, fx = mx & 3;
         const T* rpl = (const T*)refs.ref[r] + plane_at;
         const int xbase = xe + ix - 3;
@@ -334,57 +288,18 @@ __global__ __launch_bounds__(TB) void tf_blend_subpel_kernel(const int32_t* __re
 #pragma unroll
             for (int i = 0; i < 8; ++i) rv[i] = taps8(fy, col[i]);
         }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float f = rv[i];
-            int d = qc[i] - quant10(f);
-            d = d < 0 ? -d : d;
-            const int w = d < P ? (wb * (P * P - d * d)) >> (6 + 2 * L) : 0;          // <= wb: 102 * 2^16 fits
-            acc[i] = acc[i] + (float)w * f;
-            wsum[i] += w;
-        }
+        blend_accumulate(rv, wb, L, qc, acc, wsum);
         __syncthreads();                                  // (the next reference writes s_g)
     }
     long long stat = 0;
-    if (y < Hp && xc < Wp) {
-        Pix8<T> o;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float q = acc[i] * (1.0f / (float)wsum[i]);                 // (IEEE division: the fp32 nearest to 1 / Wsum)
-            o.v[i] = wsum[i] == 256 ? c.v[i] : to_t<T>(q);
-        }
-        T* orow = out + plane_at + (int64_t)y * Wp;
-        if (VEC && xc + 8 <= Wp) {
-            *reinterpret_cast<Pix8<T>*>(orow + xc) = o;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (xc + i < Wp) orow[xc + i] = o.v[i];
-        }
-        if (plane == 0 && y < H) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (xc + i < W) stat += wsum[i] - 256;
-        }
-    }
-    if (plane == 0) {                                                        // (uniform over the workgroup)
-        stat = wave_sum(stat);
-        if ((tid & 63) == 0) s_part[tid >> 6] = stat;
-        __syncthreads();
-        if (tid == 0) {
-            long long s = 0;
-#pragma unroll
-            for (int i = 0; i < TB / 64; ++i) s += s_part[i];
-            if (s != 0) atomicAdd(total, (unsigned long long)s);
-        }
-    }
+    if (y < Hp && xc < Wp) stat = blend_finish<T, VEC>(c, acc, wsum, out + plane_at + (int64_t)y * Wp, xc, Wp, W, plane == 0 && y < H);
+    if (plane == 0) blend_total(stat, s_part, total);     // (uniform over the workgroup)
 }
 
-bool overlaps(const void* a, uint64_t abytes, const void* b, uint64_t bbytes)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + bbytes && pb < pa + abytes;
-}
+struct InterpolatingBlend {      // names the kernel for dcvc::blend
+    template <typename T, bool VEC, bool AUTO>
+    static auto kernel() { return &tf_blend_subpel_kernel<T, VEC, AUTO>; }
+};
 
 }  // namespace
 
@@ -397,18 +312,14 @@ int dcvc_tf_refine(const uint16_t* cur_pyramid, const uint16_t* const* ref_pyram
     DCVC_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 30), "%s: bad size %d x %d", who, H, W);
     DCVC_REQUIRE(nref >= 1 && nref <= MAX_REFS, "%s: %d references, 1 .. %d are supported", who, nref, MAX_REFS);
     DCVC_REQUIRE(subpel == 1 || subpel == 2, "%s: subpel %d is not 1 (half pel) or 2 (quarter pel)", who, subpel);
-    DCVC_REQUIRE(cur_pyramid && ref_pyramids && mv && err && mvq && errq, "%s: null pointer", who);
-    TfQ0 p = {};
-    p.cur = cur_pyramid;
-    for (int r = 0; r < nref; ++r) {
-        DCVC_REQUIRE(ref_pyramids[r], "%s: null pointer", who);
-        DCVC_REQUIRE(((uintptr_t)ref_pyramids[r] & 1) == 0, "%s: a pyramid is not 2-byte aligned", who);
-        p.ref[r] = ref_pyramids[r];
-    }
-    DCVC_REQUIRE(((uintptr_t)cur_pyramid & 1) == 0 && ((uintptr_t)mv & 1) == 0 && ((uintptr_t)mvq & 1) == 0,
-                 "%s: a pointer is not 2-byte aligned", who);
+    DCVC_REQUIRE(mv && err && mvq && errq, "%s: null pointer", who);
+    TfPlanes p;
+    if (int rc = dcvc::check_planes(who, cur_pyramid, ref_pyramids, nref, p)) return rc;
+    DCVC_REQUIRE(((uintptr_t)mv & 1) == 0 && ((uintptr_t)mvq & 1) == 0, "%s: a pointer is not 2-byte aligned", who);
     DCVC_REQUIRE(((uintptr_t)err & 3) == 0 && ((uintptr_t)errq & 3) == 0, "%s: err or errq is not 4-byte aligned", who);
-    const int gh = (H + 7) >> 3, gw = (W + 7) >> 3;
+    using dcvc::overlaps;
+    const LevelDims d = level_dims(H, W);
+    const int gh = d.gh[0], gw = d.gw[0];
     const uint64_t vbytes = (uint64_t)nref * gh * gw * 2 * sizeof(int16_t), ebytes = (uint64_t)nref * gh * gw * sizeof(uint32_t);
     DCVC_REQUIRE(!overlaps(mvq, vbytes, mv, vbytes) && !overlaps(mvq, vbytes, err, ebytes) && !overlaps(errq, ebytes, mv, vbytes) &&
                      !overlaps(errq, ebytes, err, ebytes) && !overlaps(mvq, vbytes, errq, ebytes),
@@ -423,42 +334,8 @@ int dcvc_tf_blend_subpel(int dtype, const void* cur_nchw, const void* const* ref
                          int H, int W, const int16_t* mvq, const uint32_t* errq, int level, const int32_t* level_dev, void* out_nchw,
                          uint64_t* weight_sum, void* stream)
 {
-    const char* who = "dcvc_tf_blend_subpel";
-    if (int rc = dcvc::check_frame(who, "the current frame", dtype, cur_nchw, Hp, Wp, H, W)) return rc;
-    if (int rc = dcvc::check_frame(who, "out", dtype, out_nchw, Hp, Wp, H, W)) return rc;
-    DCVC_REQUIRE(level_dev || (level >= 1 && level <= 5), "%s: level %d outside 1 .. 5", who, level);
-    DCVC_REQUIRE(((uintptr_t)level_dev & 3) == 0, "%s: the level's word is not 4-byte aligned", who);
-    DCVC_REQUIRE(nref >= 0 && nref <= MAX_REFS, "%s: %d references, at most %d are supported", who, nref, MAX_REFS);
-    DCVC_REQUIRE(weight_sum && (nref == 0 || (refs_nchw && dists && mvq && errq)), "%s: null pointer", who);
-    DCVC_REQUIRE((int64_t)H * W < ((int64_t)1 << 30), "%s: picture too large", who);
-    const size_t es = dcvc::elem_size(dtype);
-    const uint64_t bytes = (uint64_t)3 * Hp * Wp * es;
-    DCVC_REQUIRE(!overlaps(out_nchw, bytes, cur_nchw, bytes), "%s: out overlaps the current frame (neighbours are read)", who);
-    TfRefs refs = {};
-    for (int r = 0; r < nref; ++r) {
-        if (int rc = dcvc::check_frame(who, "a reference", dtype, refs_nchw[r], Hp, Wp, H, W)) return rc;
-        DCVC_REQUIRE(!overlaps(out_nchw, bytes, refs_nchw[r], bytes), "%s: out overlaps reference %d (neighbours are read)", who, r);
-        DCVC_REQUIRE(dists[r] == 1 || dists[r] == -1 || dists[r] == 2 || dists[r] == -2, "%s: distance %d is not +-1 or +-2", who,
-                     dists[r]);
-        refs.ref[r] = refs_nchw[r];
-        refs.base[r] = (dists[r] == 1 || dists[r] == -1) ? 102 : 77;
-    }
-    DCVC_REQUIRE(((uintptr_t)mvq & 1) == 0 && ((uintptr_t)errq & 3) == 0 && ((uintptr_t)weight_sum & 7) == 0,
-                 "%s: mvq, errq or the weight sum is not aligned to its element size", who);
-    dim3 grid;
-    if (int rc = dcvc::tile_grid(who, Wp, Hp, TW, TH, grid)) return rc;
-    const bool vec = dcvc::vec_ok(16 / (int)es, es, Wp, cur_nchw, out_nchw);
-    unsigned long long* total = reinterpret_cast<unsigned long long*>(weight_sum);
-    return dcvc::typed(dtype, [&](auto tag) {
-        using T = decltype(tag);
-        dcvc::with_flag(vec, [&](auto v) {
-            dcvc::with_flag(level_dev != nullptr, [&](auto a) {
-                tf_blend_subpel_kernel<T, decltype(v)::value, decltype(a)::value><<<grid, TB, 0, (hipStream_t)stream>>>(
-                    level_dev, (const T*)cur_nchw, refs, nref, Hp, Wp, H, W, mvq, errq, (H + 7) >> 3, (W + 7) >> 3, level, (T*)out_nchw,
-                    total);
-            });
-        });
-    });
+    return dcvc::blend("dcvc_tf_blend_subpel", InterpolatingBlend{}, dtype, cur_nchw, refs_nchw, dists, nref, Hp, Wp, H, W, mvq, errq,
+                       level, level_dev, out_nchw, weight_sum, stream);
 }
 
 }  // extern "C"

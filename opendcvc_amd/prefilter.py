@@ -127,6 +127,17 @@ class TemporalFilter:
             _lib.check(_lib.lib().dcvc_tf_refine(L._p(self._pyr[cur_slot]), pyrs, n, size[0], size[1], self.subpel, L._p(self._mv),
                                                  L._p(self._err), L._p(self._mvq), L._p(self._errq), L._stream()), "dcvc_tf_refine")
 
+    def _search(self, cur, refs, size):
+        """filter()'s own slots: the pyramid of cur into slot n = 2 * radius + 1, those of refs into n + 1 .., and _motion()
+        of cur on them (none without a reference) -> n"""
+        n = 2 * self.radius + 1
+        self._pyramid(cur, size, n)
+        for i, r in enumerate(refs):
+            self._pyramid(r, size, n + 1 + i)
+        if refs:
+            self._motion(n, [n + 1 + i for i in range(len(refs))], size)
+        return n
+
     def _noise(self, cur_slot, dists, size, totals):
         """the estimate of the frame whose pyramid is in cur_slot, after _motion() on its references -> self._result"""
         from . import _lib
@@ -187,13 +198,11 @@ class TemporalFilter:
         self._size(cur, size)
         n = 2 * self.radius + 1
         if refs:
-            if motions is None or self.level == AUTO:
-                self._pyramid(cur, size, n)
             if motions is None:
-                for i, r in enumerate(refs):
-                    self._pyramid(r, size, n + 1 + i)
-                self._motion(n, [n + 1 + i for i in range(len(refs))], size)
+                self._search(cur, refs, size)
             else:
+                if self.level == AUTO:
+                    self._pyramid(cur, size, n)
                 mv, err = (self._mvq, self._errq) if self.subpel else (self._mv, self._err)
                 for i, (v, e) in enumerate(motions):
                     mv[i].copy_(v)
@@ -210,23 +219,14 @@ class TemporalFilter:
         ones make it size its buffers anew, which is a reset(): a push() sequence under way and the totals are dropped"""
         cur, refs, dists, size = self._check(cur, refs, dists, size)
         self._size(cur, size)
-        n = 2 * self.radius + 1
-        self._pyramid(cur, size, n)
-        for i, r in enumerate(refs):
-            self._pyramid(r, size, n + 1 + i)
-        if refs:
-            self._motion(n, [n + 1 + i for i in range(len(refs))], size)
-        self._noise(n, dists, size, False)
+        self._noise(self._search(cur, refs, size), dists, size, False)
         return tuple(int(v) for v in self._result.tolist())
 
     def motion(self, cur, ref, size):
         """the level-0 vectors and errors of one reference: (mv int16 [gh, gw, 2] as (y, x), err int32 [gh, gw]), new tensors"""
         cur, (ref,), _, size = self._check(cur, [ref], [1], size)
         self._size(cur, size)
-        n = 2 * self.radius + 1
-        self._pyramid(cur, size, n)
-        self._pyramid(ref, size, n + 1)
-        self._motion(n, [n + 1], size)
+        self._search(cur, [ref], size)
         return self._mv[0].clone(), self._err[0].clone()
 
     def motion_subpel(self, cur, ref, size):

@@ -2,6 +2,7 @@
 numpy restatement (tests/tf_ref.py, held against the document's figures on the CPU by tests/test_tf_host.py) bit for bit,
 prefilter.TemporalFilter's sequence interface, and --temporal-filter end to end through the harness against a loop of the
 test's own."""
+import ctypes
 import io
 
 import numpy as np
@@ -9,8 +10,9 @@ import pytest
 import torch
 
 import tf_ref as R
-from opendcvc_amd import _lib, harness, weights
+from opendcvc_amd import _lib, harness
 from opendcvc_amd.prefilter import TemporalFilter, window
+from tf_utils import _bits, _padded_shape, _to_device, clip_fixture, tex  # noqa: F401 (tex: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,34 +23,6 @@ SIZES = [(16, 16),                 # every search window and every gather clamps
          (136, 200)]               # the document's texture: many blocks, vectors up to (4, 6)
 SHIFTS = {-2: (-4, 6), -1: (-2, 3), 0: (0, 0), 1: (2, -3), 2: (4, -6)}
 REF_SETS = {1: [1], 2: [1, 2], 3: [-1, 1, 2], 4: [-1, 1, -2, 2]}          # the windows at a sequence's start, and a full one
-
-
-def _pad(n, to=16):
-    return n + (-n) % to
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint16 if a.dtype == np.float16 else np.uint32)
-
-
-def _padded_shape(size):
-    return (48, 48) if size == (33, 40) else (_pad(size[0]), _pad(size[1]))
-
-
-def _to_device(host, misaligned):
-    if not misaligned:
-        return torch.from_numpy(np.array(host))[None].cuda()
-    flat = torch.empty(host.size + 8, dtype=torch.from_numpy(np.zeros(1, host.dtype)).dtype, device="cuda")
-    dev = flat[1:1 + host.size].view(1, *host.shape)
-    dev.copy_(torch.from_numpy(np.array(host))[None])
-    assert dev.data_ptr() % 16 == host.itemsize and dev.is_contiguous()
-    return dev
-
-
-@pytest.fixture(scope="module")
-def tex():
-    return R.texture()
 
 
 @pytest.fixture(scope="module")
@@ -220,6 +194,68 @@ def test_refused_calls_leave_out_untouched(frames, filters):
     assert bool((keep == 7.0).all())
 
 
+# ---------------------------------------------------------------------------------- the three blend entries, one host check
+# (entry, has a level word): dcvc_tf_blend_subpel is both forms
+BLEND_FORMS = [("dcvc_tf_blend", False), ("dcvc_tf_blend_auto", True), ("dcvc_tf_blend_subpel", False), ("dcvc_tf_blend_subpel", True)]
+
+
+@pytest.mark.parametrize("tdt,ndt", DTYPES)
+@pytest.mark.parametrize("size", [(33, 40), (16, 16)])          # the element-wise path (one element into an allocation); the vector path
+def test_blend_entries_refuse_alike_and_agree(frames, size, tdt, ndt):
+    """every refused call of every entry returns -1 with the entry's name first in the error text and launches nothing; the
+    accepted calls - at level 3 and through a device word of 3, dcvc_tf_blend_subpel with the whole-pel vectors times four -
+    give the restatement's bits and weight sum"""
+    from opendcvc_amd import nn as NN
+    host, dev, motions = frames(size, ndt)
+    L, (H, W), dists = _lib.lib(), size, [-1, 1]
+    gh, gw = R.grid(H, W)
+    code, _, Hp, Wp, _, _ = NN.frame_args(dev[0], size)
+    cur_p = dev[0].data_ptr()
+    assert (cur_p % 16 == 0) == (size == (16, 16))
+    mv = torch.zeros((4, gh, gw, 2), dtype=torch.int16, device="cuda")
+    err = torch.zeros((4 * gh * gw + 2,), dtype=torch.int32, device="cuda")
+    for i, d in enumerate(dists):
+        mv[i].copy_(torch.from_numpy(motions[d][0]))
+        err[i * gh * gw:(i + 1) * gh * gw].copy_(torch.from_numpy(motions[d][1].astype(np.int32).ravel()))
+    mvq = 4 * mv
+    word = torch.full((2,), 3, dtype=torch.int32, device="cuda")
+    total = torch.zeros(2, dtype=torch.int64, device="cuda")
+    keep = _to_device(np.full_like(host[0], 7.0), size == (33, 40))
+    ptrs = (ctypes.c_void_p * 4)(dev[-1].data_ptr(), dev[1].data_ptr(), 0, 0)
+    d4, bad = (ctypes.c_int * 4)(-1, 1, -2, 2), (ctypes.c_int * 4)(-1, 3, -2, 2)
+
+    def blend(entry, worded, **kw):
+        a = dict(dtype=code, cur=cur_p, refs=ptrs, dists=d4, nref=2, hp=Hp, h=H, mv=(mvq if "subpel" in entry else mv).data_ptr(),
+                 err=err.data_ptr(), level=3 if not worded else 0, level_dev=word.data_ptr() if worded else None,
+                 out=keep.data_ptr(), total=total.data_ptr())
+        a.update(kw)
+        head = (a["dtype"], a["cur"], a["refs"], a["dists"], a["nref"], a["hp"], Wp, a["h"], W, a["mv"], a["err"])
+        levels = {"dcvc_tf_blend": (a["level"],), "dcvc_tf_blend_auto": (a["level_dev"],)}.get(entry, (a["level"], a["level_dev"]))
+        return getattr(L, entry)(*head, *levels, a["out"], a["total"], None)
+
+    common = [dict(cur=None), dict(refs=None), dict(dists=None), dict(mv=None), dict(err=None), dict(out=None), dict(total=None),
+              dict(mv=mv.data_ptr() + 1), dict(err=err.data_ptr() + 2), dict(total=total.data_ptr() + 4),
+              dict(nref=-1), dict(nref=5), dict(nref=3), dict(dists=bad), dict(h=Hp + 1), dict(dtype=5), dict(out=cur_p),
+              dict(out=dev[1].data_ptr())]
+    for entry, worded in BLEND_FORMS:
+        own = [dict(level_dev=word.data_ptr() + 2)] if entry != "dcvc_tf_blend" else []
+        own += [dict(level_dev=None)] if entry == "dcvc_tf_blend_auto" else []
+        own += [dict(level=0), dict(level=6)] if not worded else []
+        for kw in common + own:
+            assert blend(entry, worded, **kw) == -1 and L.dcvc_last_error().startswith(entry.encode() + b":"), (entry, worded, kw)
+    torch.cuda.synchronize()
+    assert bool((keep == 7.0).all()) and int(total[0]) == 0
+    assert np.array_equal(_bits(dev[1][0].cpu().numpy()), _bits(host[1])) and np.array_equal(_bits(dev[0][0].cpu().numpy()), _bits(host[0]))
+    want, want_total, _ = R.filter_frame(host[0], [host[d] for d in dists], dists, size, 3, [motions[d] for d in dists])
+    for entry, worded in BLEND_FORMS:
+        out = _to_device(np.full_like(host[0], 7.0), size == (33, 40))
+        total.zero_()
+        assert blend(entry, worded, out=out.data_ptr()) == 0, L.dcvc_last_error()
+        got = out[0].cpu().numpy()
+        print(f"{entry} {'word' if worded else 'level'} {size} {ndt.__name__}: {int((_bits(got) != _bits(want)).sum())} differ, sum {int(total[0])}")
+        assert np.array_equal(_bits(got), _bits(want)) and int(total[0]) == want_total > 0 and int(total[1]) == 0
+
+
 # ---------------------------------------------------------------------------------- a sequence
 @pytest.mark.parametrize("n,radius", [(7, 2), (7, 1), (1, 2), (2, 2), (2, 1)])
 def test_push_and_flush_equal_filter_on_the_window(tex, filters, n, radius):
@@ -257,23 +293,7 @@ def test_push_and_flush_equal_filter_on_the_window(tex, filters, n, radius):
 H, W, N = 96, 128, 8
 
 
-@pytest.fixture(scope="module")
-def clip(tmp_path_factory):
-    """fp32 codecs with the synthetic weights and the 96 x 128, 8-frame clip of test_gpu_harness_options.py"""
-    from opendcvc_amd.models import DMC, DMCI
-    nets = []
-    for cls, name in ((DMCI, "dmci"), (DMC, "dmc")):
-        m = cls()
-        m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in weights.make_state_dict(name, 1234).items()})
-        m.to("cuda").eval()
-        m.update(0.12)
-        nets.append(m)
-    folder = tmp_path_factory.mktemp("tf")
-    with open(folder / "clip.yuv", "wb") as f:
-        for i in range(N):
-            for plane in weights.synthetic_frame_yuv420(H, W, i, 3):
-                f.write(plane.tobytes())
-    return nets, folder
+clip = clip_fixture(H, W, N, "tf")          # the 96 x 128, 8-frame clip of test_gpu_harness_options.py
 
 
 def _run(clip, name, **kw):

@@ -11,8 +11,9 @@ import torch
 
 import tf_auto_ref as A
 import tf_ref as R
-from opendcvc_amd import _lib, harness, weights
+from opendcvc_amd import _lib, harness
 from opendcvc_amd.prefilter import TemporalFilter, window
+from tf_utils import _bits, _to_device, clip_fixture, tex  # noqa: F401 (tex: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,20 +25,6 @@ SIZES = {(136, 200): (144, 208),   # the document's texture: 17 x 25 blocks, 5 x
 SHIFTS = {-2: (-4, 6), -1: (-2, 3), 0: (0, 0), 1: (2, -3), 2: (4, -6)}
 REF_SETS = [[], [1], [-1, 1], [-2, 2], [-1, 1, -2, 2]]          # none, a sequence's start, radius 1, no distance of one, a full window
 MATERIALS = ["noise 1", "noise 3", "static", "band", "cut"]
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint16 if a.dtype == np.float16 else np.uint32)
-
-
-def _to_device(host, misaligned=False):
-    if not misaligned:
-        return torch.from_numpy(np.array(host))[None].cuda()
-    flat = torch.empty(host.size + 8, dtype=torch.from_numpy(np.zeros(1, host.dtype)).dtype, device="cuda")
-    dev = flat[1:1 + host.size].view(1, *host.shape)
-    dev.copy_(torch.from_numpy(np.array(host))[None])
-    return dev
 
 
 def pictures(tex, material, size, seed):
@@ -84,11 +71,6 @@ def expected(host, size):
                                        [motions[d] for d in dists] if four[0] else None)
         want.append((four, out, total))
     return want
-
-
-@pytest.fixture(scope="module")
-def tex():
-    return R.texture()
 
 
 @pytest.fixture(scope="module")
@@ -289,19 +271,6 @@ def test_refused_calls_leave_result_and_out_untouched(cases):
     assert result[4:].tolist() == [-77, -77] and totals[0].item() == -77
     assert tuple(result[:4].tolist()) == tf.noise(dev[0], [dev[d] for d in dists], dists, size)
     assert L.dcvc_tf_noise(pyr, None, None, 0, H, W, ws, result.data_ptr(), None, None) == 0                    # no reference, no totals
-    # dcvc_tf_blend_auto
-    keep = torch.full_like(dev[0], 7.0)
-    head, tail = _blend_args(tf, dev, dists, size, keep)
-    word = torch.full((2,), 3, dtype=torch.int32, device="cuda")
-    assert L.dcvc_tf_blend_auto(*head, None, *tail) == -1 and b"level" in L.dcvc_last_error()
-    assert L.dcvc_tf_blend_auto(*head, word.data_ptr() + 2, *tail) == -1 and b"level" in L.dcvc_last_error()
-    assert L.dcvc_tf_blend_auto(*head[:2], None, *head[3:], word.data_ptr(), *tail) == -1
-    assert L.dcvc_tf_blend_auto(*head[:4], 5, *head[5:], word.data_ptr(), *tail) == -1
-    assert L.dcvc_tf_blend_auto(*head, word.data_ptr(), tail[0], None, None) == -1
-    assert L.dcvc_tf_blend_auto(*head, word.data_ptr(), dev[1].data_ptr(), tail[1], None) == -1 and b"overlaps" in L.dcvc_last_error()
-    assert L.dcvc_tf_blend_auto(*head[:3], bad, *head[4:], word.data_ptr(), *tail) == -1
-    torch.cuda.synchronize()
-    assert bool((keep == 7.0).all()) and np.array_equal(_bits(dev[1][0].cpu().numpy()), _bits(host[1]))
     with pytest.raises(ValueError):
         TemporalFilter("cuda:0", "Auto", 2)
     with pytest.raises(ValueError):
@@ -343,23 +312,7 @@ def test_push_and_flush_follow_the_noise(tex, radius):
 H, W, N = 96, 128, 8
 
 
-@pytest.fixture(scope="module")
-def clip(tmp_path_factory):
-    """fp32 codecs with the synthetic weights and the 96 x 128, 8-frame clip of test_gpu_tf.py"""
-    from opendcvc_amd.models import DMC, DMCI
-    nets = []
-    for cls, name in ((DMCI, "dmci"), (DMC, "dmc")):
-        m = cls()
-        m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in weights.make_state_dict(name, 1234).items()})
-        m.to("cuda").eval()
-        m.update(0.12)
-        nets.append(m)
-    folder = tmp_path_factory.mktemp("tf_auto")
-    with open(folder / "clip.yuv", "wb") as f:
-        for i in range(N):
-            for plane in weights.synthetic_frame_yuv420(H, W, i, 3):
-                f.write(plane.tobytes())
-    return nets, folder
+clip = clip_fixture(H, W, N, "tf_auto")     # the 96 x 128, 8-frame clip of test_gpu_tf.py
 
 
 def test_the_harness_codes_what_the_restatement_filters(clip):

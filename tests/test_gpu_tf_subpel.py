@@ -12,8 +12,9 @@ import torch
 import tf_auto_ref as A
 import tf_ref as R
 import tf_subpel_ref as S
-from opendcvc_amd import _lib, harness, weights
+from opendcvc_amd import _lib, harness
 from opendcvc_amd.prefilter import TemporalFilter, window
+from tf_utils import _bits, _padded_shape, _to_device, clip_fixture, tex  # noqa: F401 (tex: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,34 +26,6 @@ SIZES = [(5, 11),                  # smaller than a block in both directions: on
          (136, 200)]               # the document's texture: many blocks
 DISTS = (-1, 1, -2, 2)
 REF_SETS = {0: [], 1: [1], 2: [1, 2], 3: [-1, 1, 2], 4: [-1, 1, -2, 2]}
-
-
-def _pad(n, to=16):
-    return n + (-n) % to
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint16 if a.dtype == np.float16 else np.uint32)
-
-
-def _padded_shape(size):
-    return (48, 48) if size == (33, 40) else (_pad(size[0]), _pad(size[1]))
-
-
-def _to_device(host, misaligned=False):
-    if not misaligned:
-        return torch.from_numpy(np.array(host))[None].cuda()
-    flat = torch.empty(host.size + 8, dtype=torch.from_numpy(np.zeros(1, host.dtype)).dtype, device="cuda")
-    dev = flat[1:1 + host.size].view(1, *host.shape)
-    dev.copy_(torch.from_numpy(np.array(host))[None])
-    assert dev.data_ptr() % 16 == host.itemsize and dev.is_contiguous()
-    return dev
-
-
-@pytest.fixture(scope="module")
-def tex():
-    return R.texture()
 
 
 def displacement(i, band):
@@ -359,21 +332,12 @@ def test_refused_calls_leave_the_outputs_untouched(frames):
     # dcvc_tf_blend_subpel
     from opendcvc_amd import nn as NN
     code, cur_p, Hp, Wp, _, _ = NN.frame_args(dev[0], size)
-    ptrs, d2, bad = (ctypes.c_void_p * 4)(dev[-1].data_ptr(), dev[1].data_ptr(), 0, 0), (ctypes.c_int * 4)(-1, 1, 0, 0), (ctypes.c_int * 4)(-1, 3, 0, 0)
+    ptrs, d2 = (ctypes.c_void_p * 4)(dev[-1].data_ptr(), dev[1].data_ptr(), 0, 0), (ctypes.c_int * 4)(-1, 1, 0, 0)
     word = torch.full((2,), 3, dtype=torch.int32, device="cuda")
     o, tot = keep.data_ptr(), tf._total.data_ptr()
 
-    def blend(cur=cur_p, refs=ptrs, dists=d2, nref=2, hp=Hp, h=H, mvq=q, errq=e, level=3, level_dev=None, out=o, total=tot, dtype=code):
-        return L.dcvc_tf_blend_subpel(dtype, cur, refs, dists, nref, hp, Wp, h, W, mvq, errq, level, level_dev, out, total, None)
-    for kw in (dict(level=0), dict(level=6), dict(level_dev=word.data_ptr() + 2), dict(cur=None), dict(refs=None), dict(dists=None),
-               dict(mvq=None), dict(errq=None), dict(out=None), dict(total=None), dict(errq=e + 2), dict(mvq=q + 1), dict(total=tot + 4),
-               dict(nref=5), dict(nref=-1), dict(dists=bad), dict(h=Hp + 1), dict(dtype=5), dict(out=cur_p), dict(out=dev[1].data_ptr()),
-               dict(nref=3)):
-        assert blend(**kw) == -1 and L.dcvc_last_error().startswith(b"dcvc_tf_blend_subpel"), kw
-    torch.cuda.synchronize()
-    assert bool((keep == 7.0).all()) and np.array_equal(_bits(dev[1][0].cpu().numpy()), _bits(host[1]))
-    tf.reset()
-    assert blend(level=0, level_dev=word.data_ptr()) == 0, L.dcvc_last_error()           # with a word the level is not looked at
+    tf.reset()                                    # (the refused calls: test_gpu_tf.py's table)  With a word the level is not looked at:
+    assert L.dcvc_tf_blend_subpel(code, cur_p, ptrs, d2, 2, Hp, Wp, H, W, q, e, 0, word.data_ptr(), o, tot, None) == 0, L.dcvc_last_error()
     once = tf.weight_sum()
     again = tf.filter(dev[0], [dev[d] for d in dists], dists, size)
     assert torch.equal(keep.view(torch.int16), again.view(torch.int16)) and tf.weight_sum() == 2 * once > 0
@@ -383,23 +347,7 @@ def test_refused_calls_leave_the_outputs_untouched(frames):
 H, W, N = 136, 200, 4
 
 
-@pytest.fixture(scope="module")
-def clip(tmp_path_factory):
-    """fp32 codecs with the synthetic weights and a 136 x 200, 4-frame clip made like test_gpu_tf.py's"""
-    from opendcvc_amd.models import DMC, DMCI
-    nets = []
-    for cls, name in ((DMCI, "dmci"), (DMC, "dmc")):
-        m = cls()
-        m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in weights.make_state_dict(name, 1234).items()})
-        m.to("cuda").eval()
-        m.update(0.12)
-        nets.append(m)
-    folder = tmp_path_factory.mktemp("tf_subpel")
-    with open(folder / "clip.yuv", "wb") as f:
-        for i in range(N):
-            for plane in weights.synthetic_frame_yuv420(H, W, i, 3):
-                f.write(plane.tobytes())
-    return nets, folder
+clip = clip_fixture(H, W, N, "tf_subpel")   # a 136 x 200, 4-frame clip made like test_gpu_tf.py's
 
 
 def _run(clip, name, **kw):

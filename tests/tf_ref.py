@@ -109,34 +109,43 @@ def rcp(n):
     return np.float32(1.0) / np.asarray(n).astype(np.float32)          # (IEEE fp32 division: correctly rounded; n <= 614 is exact)
 
 
-def filter_frame(cur, refs, dists, size, level, motions=None):
-    """-> (out [3, Hp, Wp] in cur's dtype, weight sum (int), Wsum of the luma plane [H, W]).  refs / dists in accumulation
-    order.  motions: None or the (mv, err) of every reference, where they are known already."""
+def blend(cur, size, level, weighed):
+    """the accumulation: cur against `weighed`, per reference in accumulation order (distance, err [gh, gw] of its blocks,
+    r [3, H, W] float32: its samples at the blocks' vectors) -> (out [3, Hp, Wp] in cur's dtype, weight sum (int), Wsum of the
+    luma plane [H, W])"""
     h, w = size
-    dt = cur.dtype
-    pyr_c = pyramid(cur, size)
-    ys, xs = np.arange(h)[:, None], np.arange(w)[None, :]
+    by, bx = np.arange(h)[:, None] >> 3, np.arange(w)[None, :] >> 3
     c = cur[:, :h, :w].astype(np.float32)
     qc = quant(c)
     acc = np.float32(256.0) * c
     wsum = np.full((3, h, w), 256, np.int64)
-    for i, (ref, dist) in enumerate(zip(refs, dists)):
-        mv, err = motions[i] if motions is not None else motion(pyr_c, pyramid(ref, size))
-        wb = block_weight(err, dist, level)
-        by, bx = ys >> 3, xs >> 3
-        ry = np.clip(ys + mv[by, bx, 0], 0, h - 1)
-        rx = np.clip(xs + mv[by, bx, 1], 0, w - 1)
-        r = ref[:, ry, rx].astype(np.float32)
-        wgt = sample_weight(wb[by, bx][None], np.abs(qc - quant(r)), level)
+    for dist, err, r in weighed:
+        wgt = sample_weight(block_weight(err, dist, level)[by, bx][None], np.abs(qc - quant(r)), level)
         with np.errstate(invalid="ignore", over="ignore"):
             acc = acc + wgt.astype(np.float32) * r
         wsum = wsum + wgt
     with np.errstate(invalid="ignore", over="ignore"):
-        res = (acc * rcp(wsum)).astype(dt)
+        res = (acc * rcp(wsum)).astype(cur.dtype)
     pic = np.where(wsum == 256, cur[:, :h, :w], res)                 # no weight: the bits of c
     hp, wp = cur.shape[1:]
     out = pic[:, np.minimum(np.arange(hp), h - 1)][:, :, np.minimum(np.arange(wp), w - 1)]
     return np.ascontiguousarray(out), int((wsum[0] - 256).sum()), wsum[0]
+
+
+def filter_frame(cur, refs, dists, size, level, motions=None):
+    """-> blend()'s three.  refs / dists in accumulation order.  motions: None or the (mv, err) of every reference, where
+    they are known already."""
+    h, w = size
+    ys, xs = np.arange(h)[:, None], np.arange(w)[None, :]
+    by, bx = ys >> 3, xs >> 3
+    pyr_c = pyramid(cur, size) if motions is None else None
+    weighed = []
+    for i, (ref, dist) in enumerate(zip(refs, dists)):
+        mv, err = motions[i] if motions is not None else motion(pyr_c, pyramid(ref, size))
+        ry = np.clip(ys + mv[by, bx, 0], 0, h - 1)
+        rx = np.clip(xs + mv[by, bx, 1], 0, w - 1)
+        weighed.append((dist, err, ref[:, ry, rx].astype(np.float32)))
+    return blend(cur, size, level, weighed)
 
 
 def window(n_frames, radius):

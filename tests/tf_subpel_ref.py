@@ -126,31 +126,14 @@ def interp_f32(ref, size, mvq):
 
 
 def filter_frame(cur, refs, dists, size, level, subpel=2, motions=None, samples=None):
-    """tf_ref.filter_frame with the refined vectors: -> (out, weight sum, Wsum of the luma plane).  motions: None or the
-    (mvq, errq) of every reference; samples: None or interp_f32 of every reference at those vectors, where already made"""
-    h, w = size
-    dt = cur.dtype
-    ys, xs = np.arange(h)[:, None], np.arange(w)[None, :]
-    by, bx = ys >> 3, xs >> 3
-    c = cur[:, :h, :w].astype(np.float32)
-    qc = R.quant(c)
-    acc = np.float32(256.0) * c
-    wsum = np.full((3, h, w), 256, np.int64)
+    """tf_ref.filter_frame with the refined vectors: -> tf_ref.blend()'s three.  motions: None or the (mvq, errq) of every
+    reference; samples: None or interp_f32 of every reference at those vectors, where already made"""
     pyr_c = R.pyramid(cur, size) if motions is None else None
+    weighed = []
     for i, (ref, dist) in enumerate(zip(refs, dists)):
         mvq, errq = motions[i] if motions is not None else motion(pyr_c, R.pyramid(ref, size), subpel)
-        r = samples[i] if samples is not None else interp_f32(ref, size, mvq)
-        wb = R.block_weight(errq, dist, level)
-        wgt = R.sample_weight(wb[by, bx][None], np.abs(qc - R.quant(r)), level)
-        with np.errstate(invalid="ignore", over="ignore"):
-            acc = acc + wgt.astype(np.float32) * r
-        wsum = wsum + wgt
-    with np.errstate(invalid="ignore", over="ignore"):
-        res = (acc * R.rcp(wsum)).astype(dt)
-    pic = np.where(wsum == 256, cur[:, :h, :w], res)
-    hp, wp = cur.shape[1:]
-    out = pic[:, np.minimum(np.arange(hp), h - 1)][:, :, np.minimum(np.arange(wp), w - 1)]
-    return np.ascontiguousarray(out), int((wsum[0] - 256).sum()), wsum[0]
+        weighed.append((dist, errq, samples[i] if samples is not None else interp_f32(ref, size, mvq)))
+    return R.blend(cur, size, level, weighed)
 
 
 # ---------------------------------------------------------------------------------- the level from the picture

@@ -4,7 +4,7 @@ dcvc_tf_refine and dcvc_tf_blend_subpel at radius 1 (2 references) and 2 (4 refe
 run's dcvc_tf_motion, dcvc_tf_blend and dcvc_tf_blend_auto - measured like tools/tf_time.py: warm-up, then the variants
 alternated batch by batch, each batch of BATCH calls between two HIP events, medians and quartiles of the per-call time; every
 call works on the next of several buffer sets.  With a second library (parent=...: the build of another commit) its
-dcvc_tf_blend and dcvc_tf_blend_auto run in the same rotation.  Then what the harness pays: run_one_point on a synthetic 1080p
+dcvc_tf_motion, dcvc_tf_refine and three blend entries run in the same rotation.  Then what the harness pays: run_one_point on a synthetic 1080p
 clip with the filter off, at level 3, and at level 3 with --tf-subpel 0 / 1 / 2, alternated, two rounds; root=DIR measures the
 package of another checkout instead (its rows with --tf-subpel are left out where it has no such option).
     python tools/tf_subpel_time.py [batches=100] [out=profiles/r16_tf_subpel.txt] [frames=32, 0: kernels only] [kernels=1]
@@ -88,15 +88,16 @@ def variants(parent):
 
         def add(label, nbytes, call, data=data):
             group.append((f"{label}, {name.split()[0]}", nbytes, lambda k: call(data[k])))
+        libs = [("", L)] + ([(" (parent)", parent)] if parent is not None else [])
         for nref in (2, 4):
             radius = nref // 2
-            add(f"dcvc_tf_motion {nref} refs (3 launches)", (1 + nref) * pyr_elems * 2,
-                lambda s, nref=nref: L.dcvc_tf_motion(P(s["pyr"][0]), s["pyrs"], nref, H, W, P(s["mv"]), P(s["err"]), P(ws), st))
-            for sp in (1, 2):
-                add(f"dcvc_tf_refine {nref} refs subpel {sp}", (1 + nref) * H * W * 2,
-                    lambda s, nref=nref, sp=sp: L.dcvc_tf_refine(P(s["pyr"][0]), s["pyrs"], nref, H, W, sp, P(s["mv"]), P(s["err"]),
-                                                                 P(s["mvq"]), P(s["errq"]), st))
-            libs = [("", L)] + ([(" (parent)", parent)] if parent is not None else [])
+            for tag, lib in libs:
+                add(f"dcvc_tf_motion {nref} refs (3 launches){tag}", (1 + nref) * pyr_elems * 2,
+                    lambda s, nref=nref, lib=lib: lib.dcvc_tf_motion(P(s["pyr"][0]), s["pyrs"], nref, H, W, P(s["mv"]), P(s["err"]), P(ws), st))
+                for sp in (1, 2):
+                    add(f"dcvc_tf_refine {nref} refs subpel {sp}{tag}", (1 + nref) * H * W * 2,
+                        lambda s, nref=nref, sp=sp, lib=lib: lib.dcvc_tf_refine(P(s["pyr"][0]), s["pyrs"], nref, H, W, sp, P(s["mv"]),
+                                                                                P(s["err"]), P(s["mvq"]), P(s["errq"]), st))
             for tag, lib in libs:
                 add(f"dcvc_tf_blend radius {radius}{tag}", (2 + nref) * frame,
                     lambda s, nref=nref, lib=lib: lib.dcvc_tf_blend(code, P(s["f"][0]), s["refs"], s["dists"], nref, Hp, Wp, H, W, P(s["mv"]),
@@ -104,10 +105,11 @@ def variants(parent):
                 add(f"dcvc_tf_blend_auto radius {radius}{tag}", (2 + nref) * frame,
                     lambda s, nref=nref, lib=lib: lib.dcvc_tf_blend_auto(code, P(s["f"][0]), s["refs"], s["dists"], nref, Hp, Wp, H, W,
                                                                          P(s["mv"]), P(s["err"]), P(word), P(s["out"]), P(total), st))
-            for sp in (1, 2):
-                add(f"dcvc_tf_blend_subpel radius {radius} subpel {sp}", (2 + nref) * frame,
-                    lambda s, nref=nref, sp=sp: L.dcvc_tf_blend_subpel(code, P(s["f"][0]), s["refs"], s["dists"], nref, Hp, Wp, H, W,
-                                                                       P(s[f"mvq{sp}"]), P(s[f"errq{sp}"]), 3, None, P(s["out"]), P(total), st))
+                for sp in (1, 2):
+                    add(f"dcvc_tf_blend_subpel radius {radius} subpel {sp}{tag}", (2 + nref) * frame,
+                        lambda s, nref=nref, sp=sp, lib=lib: lib.dcvc_tf_blend_subpel(code, P(s["f"][0]), s["refs"], s["dists"], nref, Hp, Wp,
+                                                                                      H, W, P(s[f"mvq{sp}"]), P(s[f"errq{sp}"]), 3, None,
+                                                                                      P(s["out"]), P(total), st))
     return group, sets, notes, keep
 
 
@@ -138,7 +140,7 @@ if KERNELS:
     parent = None
     if "parent" in args:
         parent = ctypes.CDLL(os.path.abspath(args["parent"]))
-        for name in ("dcvc_tf_blend", "dcvc_tf_blend_auto"):
+        for name in ("dcvc_tf_blend", "dcvc_tf_blend_auto", "dcvc_tf_blend_subpel", "dcvc_tf_refine", "dcvc_tf_motion"):
             getattr(parent, name).restype, getattr(parent, name).argtypes = getattr(L, name).restype, getattr(L, name).argtypes
     group, sets, notes, keep = variants(parent)
     lines.append(f"fp16, {W}x{H} in a {Wp}x{Hp} tensor, {sets} buffer sets per material, {n} batches of {BATCH} calls per variant, level 3; "
@@ -147,7 +149,7 @@ if KERNELS:
     lines += ["  " + s for s in notes]
     for (name, nbytes, _), t in zip(group, measure(group, sets)):
         q1, med, q3 = np.percentile(t, [25, 50, 75])
-        lines.append(f"  {name:52s} median {med:8.2f} us  quartiles {q1:8.2f} .. {q3:8.2f}  min {t.min():8.2f}  "
+        lines.append(f"  {name:61s} median {med:8.2f} us  quartiles {q1:8.2f} .. {q3:8.2f}  min {t.min():8.2f}  "
                      f"{nbytes / 1e6:7.2f} MB  floor {nbytes / ACHIEVABLE * 1e6:6.2f} us")
     del group, keep
     torch.cuda.empty_cache()
