@@ -5,13 +5,14 @@
 //   row t = { meta, cost[0 .. stride - 2] },  meta = (max_value << 16) | (offset & 0xffff),  max_value = sizes[t] - 2
 //   cost[v] = rint(65536 * (16 - log2(cdf[v + 1] - cdf[v]))),  v = 0 .. max_value (max_value = the escape symbol)
 // A symbol inside its table costs cost[value]; any other one costs cost[max_value] + 2 bits for every 2-bit bypass group
-// encode_symbol of rans_host.cpp writes: n_bypass / 3 + 1 groups for the count, n_bypass for the value.  Everything is
-// integer arithmetic, so the result does not depend on the reduction order and equals tests/rate_ref.py bit for bit.
+// its escape takes in the stream (rans_core.hpp).  Everything is integer arithmetic, so the result does not depend on the
+// reduction order and equals tests/rate_ref.py bit for bit.
 // Two launches: per-thread -> per-wave -> per-workgroup uint64 partials (the y parts read 16 bytes per access against the
 // Gaussian cost tables in LDS, z against its qp's rows in global memory), then one small launch that sums the partials
 // into pinned host memory.  No atomics, no host read in between.
 #include "common.hpp"
 #include "plane_math.hpp"
+#include "rans_core.hpp"
 
 #include <algorithm>
 #include <cstdint>
@@ -36,9 +37,8 @@ __device__ __forceinline__ unsigned symbol_cost(const uint32_t* row, int sym, bo
     const int value = sym - offset;
     esc = (unsigned)value >= (unsigned)max_value;
     if (!esc) return row[1 + value];
-    const unsigned raw = value < 0 ? (unsigned)(-2 * value - 1) : (unsigned)(2 * (value - max_value));
-    const unsigned n_bypass = raw ? (unsigned)(33 - __clz((int)raw)) >> 1 : 0u;      // 2-bit groups that hold raw
-    return row[1 + max_value] + 2u * kOne * (n_bypass / 3u + 1u + n_bypass);
+    const unsigned groups = rans::escape_group_count(rans::bypass_groups(rans::escape_raw(value, max_value)));
+    return row[1 + max_value] + (unsigned)rans::kBypassBits * kOne * groups;
 }
 
 // partial[3 * workgroup + {0, 1, 2}] = the workgroup's Q16 bits, coded symbols, escapes

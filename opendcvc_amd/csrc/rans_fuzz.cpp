@@ -5,7 +5,9 @@
 // (src/cpp/py_rans/rans.cpp:356-429 reads past the vector's end through a raw pointer); the drop-in must not read out of
 // bounds and must say so: every decode call returns 0 or -4 (E_STREAM), dcvc_rans_dec_check_end() fails on every damaged
 // stream, and the sanitizers see no invalid access / undefined behaviour on the way.  The chunked y units
-// (dcvc_rans_chunked_encode_y / _decode_y) get the same treatment in chunked_round().
+// (dcvc_rans_chunked_encode_y / _decode_y) get the same treatment in chunked_round() - and so do the bodies the device coder
+// runs per lane (rans_lane.hpp: encode_chunk with its Emit, and the decoder's Reader), which are host-and-device functions:
+// every unit the host coder writes or reads there goes through them too, in exact-size heap blocks.
 //
 //   rans_fuzz_asan [rounds]      exit code 0 = all properties held
 #include <cstdint>
@@ -15,6 +17,7 @@
 #include <vector>
 
 #include "dcvc_amd.h"
+#include "rans_lane.hpp"
 
 namespace {
 
@@ -196,15 +199,83 @@ int decode(dcvc_rans_dec* d, const std::vector<uint8_t>& s, const Frame& f, int 
 }
 
 
+// ---- the device coder's lane bodies on the CPU.  Every buffer they touch is a heap block of exactly the size the kernels
+// guarantee, so ASan decides whether a write leaves the slot or a read leaves the payload.
+struct Block {                           // malloc: 16-byte aligned, and ASan knows the size to the byte
+    uint8_t* p;
+    explicit Block(size_t n) : p((uint8_t*)std::malloc(n ? n : 1)) {}
+    ~Block() { std::free(p); }
+    Block(const Block&) = delete;
+};
+
+// encode_chunk per chunk into a slot of `slot` bytes (chunk 0: slot0), assembled as enc_scan_kernel / enc_gather_kernel do;
+// false: a lane reported
+bool lane_encode(const rans::Tables& T, const std::vector<int16_t>& kept, int log2_s, int slot0, int slot, std::vector<uint8_t>& unit)
+{
+    const int64_t n = (int64_t)kept.size(), nch = rans::chunks(n, log2_s);
+    unit.assign((size_t)(2 * nch), 0);
+    for (int64_t c = 0; c < nch; ++c) {
+        const int64_t a = c << log2_s, b = std::min<int64_t>(n, a + ((int64_t)1 << log2_s));
+        const int sl = c == 0 ? slot0 : slot;
+        Block buf((size_t)sl);
+        auto fetch = [&](int64_t j0) {   // the kernel's entry-by-entry form
+            uint32_t w[4] = {0, 0, 0, 0};
+            for (int k = 0; k < 8; ++k)
+                if (j0 + k >= a && j0 + k < b) w[k >> 1] |= (uint32_t)(uint16_t)kept[(size_t)(j0 + k)] << ((k & 1) * 16);
+            return make_uint4(w[0], w[1], w[2], w[3]);
+        };
+        const uint32_t len = rans::encode_chunk(T, fetch, a, b, buf.p, sl);
+        if (!len) return false;
+        rans::put_chunk_len(unit.data(), c, len);
+        unit.insert(unit.end(), buf.p + sl - len, buf.p + sl);
+    }
+    return true;
+}
+
+// The device decoder's byte source on a unit `u` (damaged or not) at offset uoff of a payload buffer that starts 4-byte
+// aligned and ends unaligned: once the length table holds, as dec_scan_kernel checks it, every chunk is read through a
+// Reader whose staged window covers the chunk (as the kernel's does when the bodies fit) or only its first `window` bytes.
+// The Reader must hand out exactly the chunk's bytes, then zeros with the overrun flag - and never touch a byte outside the
+// two exact-size blocks, which ASan decides.  (The walk around it stays in dec_chunks_kernel: not run here.)
+void lane_read(const std::vector<uint8_t>& u, int64_t count, int log2_s, uint32_t window, int round)
+{
+    const uint32_t size = (uint32_t)u.size(), uoff = (5u - size % 4u) % 4u, cap = uoff + size;      // cap % 4 == 1
+    Block pay(cap);
+    std::memset(pay.p, 0xa5, uoff);
+    if (size) std::memcpy(pay.p + uoff, u.data(), size);
+    const int64_t nch = rans::chunks(count, log2_s);
+    if (2 * nch > size) return;                                 // DCVC_RANS_DEV_E_COUNT
+    const uint8_t* unit = pay.p + uoff;
+    uint64_t total = 2 * (uint64_t)nch;
+    for (int64_t c = 0; c < nch; ++c) total += rans::chunk_len(unit, c);
+    if (total != size) return;                                  // DCVC_RANS_DEV_E_TABLE
+    uint32_t begin = uoff + 2 * (uint32_t)nch;
+    for (int64_t c = 0; c < nch; ++c) {
+        const uint32_t len = rans::chunk_len(unit, c);
+        const uint32_t lo4 = begin & ~3u;
+        uint32_t hi4 = std::min((begin + len + 3) & ~3u, cap & ~3u);
+        hi4 = std::max(lo4, std::min(hi4, lo4 + (window & ~3u)));
+        Block staged(hi4 - lo4);
+        std::memcpy(staged.p, pay.p + lo4, hi4 - lo4);
+        rans::Reader r;
+        r.base = pay.p, r.staged = reinterpret_cast<const uint32_t*>(staged.p), r.lo4 = lo4, r.hi4 = hi4, r.cap = cap;
+        r.open(begin, len);
+        bool same = true;
+        for (uint32_t k = 0; k < len; ++k) same = r.next() == pay.p[begin + k] && same;
+        EXPECT(same && !r.overrun, "round %d: the Reader does not hand out chunk %lld's bytes (window %u)", round, (long long)c, window);
+        EXPECT(r.next() == 0 && r.next() == 0 && r.overrun && r.pos == r.end, "round %d: the Reader reads on past chunk %lld", round, (long long)c);
+        begin += len;
+    }
+}
+
 // The chunked y units (dcvc_rans_chunked_encode_y / _decode_y): exact round trip, every truncation, every bit of the length
 // table, bit flips in the bodies, a count that needs a longer table than the unit has - each damaged unit is refused with -4
 // (or, for a flip inside an escape's verbatim bits, decodes to other ESCAPED values only) and no read leaves the exact-size block.
-void chunked_round(Rng& r, dcvc_rans_enc* e, dcvc_rans_dec* d, const Tables& yt, const Frame& f, int yg, int round, long* n_cases)
+// The lane bodies see the same units: the encoder's walk writes the host's bytes and reports a slot that is too small without
+// writing outside it; the decoder's Reader hands out each chunk's bytes and nothing else.
+void chunked_round(Rng& r, dcvc_rans_enc* e, dcvc_rans_dec* d, const Tables& yt, const rans::Tables& T, const std::vector<int16_t>& kept,
+                   int log2_s, int yg, int round, long* n_cases)
 {
-    std::vector<int16_t> kept;
-    for (int16_t v : f.y[0])
-        if ((v & 0xff) != 0xff) kept.push_back(v);
-    const int log2_s = 8 + round % 3;
     const int64_t n = (int64_t)kept.size(), S = 1ll << log2_s, nch = (n + S - 1) / S;
     std::vector<uint8_t> unit((size_t)(4 * n + 6 * nch + 16));
     const int64_t ub = dcvc_rans_chunked_encode_y(e, kept.data(), n, yg, log2_s, unit.data(), (int64_t)unit.size());
@@ -213,6 +284,16 @@ void chunked_round(Rng& r, dcvc_rans_enc* e, dcvc_rans_dec* d, const Tables& yt,
     EXPECT(dcvc_rans_chunked_encode_y(e, kept.data(), n, yg, log2_s, unit.data(), ub - 1) == -1 || n == 0, "short output accepted");
     EXPECT(dcvc_rans_chunked_encode_y(e, kept.data(), n, yg, 7, unit.data(), ub) == -1, "chunk size 128 accepted");
     unit.resize((size_t)ub);
+    {
+        // (an int8 symbol takes at most 4 bytes: the host coder's own scratch bound)
+        const int slot = (int)(4 * S + 16);
+        std::vector<uint8_t> lane;
+        EXPECT(lane_encode(T, kept, log2_s, slot, slot, lane) && lane == unit, "round %d: the lane encoder's unit differs from the host's", round);
+        const int len0 = nch ? (int)rans::chunk_len(unit.data(), 0) : 0;
+        for (int small : {0, (len0 - 1) & ~3})          // no slot, and the largest one that is too small
+            EXPECT(nch == 0 || !lane_encode(T, kept, log2_s, small, slot, lane), "round %d: slot of %d bytes for a chunk of %d accepted", round,
+                   small, len0);
+    }
     std::vector<uint8_t> idx((size_t)n);
     for (int64_t i = 0; i < n; ++i) idx[(size_t)i] = (uint8_t)(kept[(size_t)i] & 0xff);
     std::vector<int8_t> out((size_t)n + 1);
@@ -227,6 +308,7 @@ void chunked_round(Rng& r, dcvc_rans_enc* e, dcvc_rans_dec* d, const Tables& yt,
                 const int want = (int8_t)(kept[(size_t)i] >> 8);
                 if (out[(size_t)i] != want && !is_escape(yt, idx[(size_t)i], want)) *plain = true;
             }
+        for (uint32_t window : {1u << 20, 8u}) lane_read(u, count, log2_s, window, round);      // the staged window covers the chunk / ends inside it
         ++*n_cases;
         return rc;
     };
@@ -244,6 +326,12 @@ void chunked_round(Rng& r, dcvc_rans_enc* e, dcvc_rans_dec* d, const Tables& yt,
         std::vector<uint8_t> t(unit);
         t[(size_t)(b >> 3)] ^= (uint8_t)(1u << (b & 7));
         EXPECT(run(t, n, &plain) == -4, "round %d: length table bit %lld flipped, accepted", round, (long long)b);
+    }
+    for (int dir = -1; dir <= 1 && nch > 1; dir += 2) {      // two chunks trade a byte: the table still adds up
+        std::vector<uint8_t> t(unit);
+        rans::put_chunk_len(t.data(), 0, rans::chunk_len(unit.data(), 0) + dir);
+        rans::put_chunk_len(t.data(), 1, rans::chunk_len(unit.data(), 1) - dir);
+        EXPECT(run(t, n, &plain) == -4, "round %d: chunks 0 and 1 trade a byte (%d), accepted", round, dir);
     }
     for (int k = 0; k < 200 && ub > 2 * nch; ++k) {
         std::vector<uint8_t> t(unit);
@@ -321,8 +409,21 @@ int main(int argc, char** argv)
             n_escape_only += end_rc == 0 && !same;
             ++n_flip;
         }
-        // 3b. the chunked units of the same symbols
-        chunked_round(r, e, d, yt, f, yg, round, &n_chunked);
+        // 3b. the chunked units of the same symbols, then of the counts around one chunk and of four chunks of 256
+        {
+            std::vector<uint32_t> words;
+            EXPECT(rans::build_tables("fuzz", yt.cdf.data(), yt.n, yt.stride, yt.sizes.data(), yt.offsets.data(), words), "tables");
+            const rans::Tables T = rans::tables_at(words.data(), yt.n, yt.stride);
+            std::vector<int16_t> kept;
+            for (int16_t v : f.y[0])
+                if ((v & 0xff) != 0xff) kept.push_back(v);
+            const int log2_s = 8 + round % 3, S = 1 << log2_s;
+            chunked_round(r, e, d, yt, T, kept, log2_s, yg, round, &n_chunked);
+            const int edge[5] = {1, S - 1, S, S + 1, 3 * 256 + 1 + r.below(255)};
+            kept.resize((size_t)edge[round % 5]);
+            for (int16_t& v : kept) v = (int16_t)((r.below(8) == 0 ? r.below(255) - 127 : r.below(9) - 4) * 256 + r.below(yt.n));
+            chunked_round(r, e, d, yt, T, kept, round % 5 == 4 ? 8 : log2_s, yg, round, &n_chunked);
+        }
         // 4. argument errors stay errors
         EXPECT(dcvc_rans_dec_set_stream(d, s.data(), 3) == -1, "short stream accepted");
         EXPECT(dcvc_rans_dec_set_stream(d, nullptr, 16) == -1, "null stream accepted");

@@ -1,10 +1,9 @@
 // rans_host.cpp - host entropy coder of the DCVC-RT path (stays on the CPU by design,
-// BASELINE.json north_star): byte-wise rANS with 32-bit state, 16-bit probabilities, escape
-// ("bypass") coding of out-of-range symbols and the two-coder split of large frames.
+// BASELINE.json north_star): the stream arithmetic of rans_core.hpp behind the reference's coder
+// interface, with the two-coder split of large frames.
 //
 // Own implementation; the byte stream is identical to the reference's
-//   src/cpp/py_rans/rans_byte.h:61-141  (state, renormalisation, flush)
-//   src/cpp/py_rans/rans.cpp:28-58,95-140,202-243,356-429  (bypass bits, task order, y/z cdf selection)
+//   src/cpp/py_rans/rans.cpp:95-140,202-243  (task order, y/z cdf selection)
 //   src/cpp/py_rans/py_rans.cpp:20-67,109-151,175-262     (split in two coders, stream merge)
 // which tests/ verify against golden streams produced by the reference and against oracle/_ref.
 // Differences that do not change the stream: per-symbol (start, freq) tables are flat arrays;
@@ -26,16 +25,11 @@
 #include <thread>
 #include <vector>
 
-#include "common.hpp"
+#include "rans_core.hpp"
 
 namespace {
 
-constexpr int kScaleBits = 16;
-constexpr uint32_t kRansL = 1u << 23;
-constexpr int kRenormShift = 23 - kScaleBits + 8;
-constexpr int kBypassBits = 2;
-constexpr int kBypassMax = (1 << kBypassBits) - 1;
-constexpr uint32_t kMask = (1u << kScaleBits) - 1;
+using namespace rans;
 
 // Per-table data laid out for the hot loops:
 //   encoder: per (table, value) the ryg_rans "fast encode" constants (reciprocal multiply instead of
@@ -63,27 +57,37 @@ struct alignas(64) DecTable {
 
 struct CdfGroup {
     int n = 0, stride = 0;
-    std::vector<int32_t> cdf, sizes, offsets;
+    std::vector<int32_t> sizes, offsets;
     std::vector<EncSym> esym;          // [n][stride]
     std::vector<DecTable> dtab;        // [n]
 };
 
-void build_fast_tables(CdfGroup& g)
+// checks the group (rans_core.hpp) and appends it with its fast tables; the group's index, or E_ARG
+int add_group(const char* who, std::vector<CdfGroup>& groups, const int32_t* cdf, int n, int stride, const int32_t* sizes,
+              const int32_t* offsets)
 {
-    g.esym.assign((size_t)g.n * g.stride, EncSym{0, 0, 0, 0, 0});
-    g.dtab.assign((size_t)g.n, DecTable{});
-    for (int t = 0; t < g.n; ++t) {
-        const int32_t* cdf = g.cdf.data() + (size_t)t * g.stride;
-        const int nsym = g.sizes[t] - 1;                 // symbols 0..max_value (max_value = escape)
+    if (!check_cdf_group(who, cdf, n, stride, sizes, offsets)) return dcvc::E_ARG;
+    CdfGroup g{n, stride, {sizes, sizes + n}, {offsets, offsets + n}, std::vector<EncSym>((size_t)n * stride), std::vector<DecTable>(n)};
+    for (int t = 0; t < n; ++t) {
+        const int32_t* c = cdf + (size_t)t * stride;
+        const int nsym = sizes[t] - 1;                   // symbols 0..max_value (max_value = escape)
+        DecTable& d = g.dtab[t];
+        d.offset = (int16_t)offsets[t];
+        d.max_value = (uint16_t)(nsym - 1);
+        fill_entries(c, nsym, d.sym);
+        fill_first_guess<kLutBits>(c, [&](int b, int v) {
+            d.lut[b] = (uint8_t)v;
+            d.lute[b] = d.sym[v];
+        });
         for (int v = 0; v < nsym; ++v) {
-            const uint32_t start = (uint32_t)cdf[v], freq = (uint32_t)(cdf[v + 1] - cdf[v]);
-            EncSym& e = g.esym[(size_t)t * g.stride + v];
-            e.x_max = ((1u << 23 >> 16) << 8) * freq;
-            e.cmpl_freq = (uint16_t)((1u << 16) - freq);
+            const uint32_t start = entry_start(d.sym[v]), freq = entry_freq(d.sym[v]);
+            EncSym& e = g.esym[(size_t)t * stride + v];
+            e.x_max = symbol_x_max(freq);
+            e.cmpl_freq = (uint16_t)((1u << kScaleBits) - freq);
             if (freq < 2) {
                 e.rcp_freq = ~0u;
                 e.rcp_shift = 0;
-                e.bias = start + (1u << 16) - 1;
+                e.bias = start + (1u << kScaleBits) - 1;
             } else {
                 uint32_t shift = 0;
                 while (freq > (1u << shift)) ++shift;
@@ -92,96 +96,46 @@ void build_fast_tables(CdfGroup& g)
                 e.bias = start;
             }
         }
-        DecTable& d = g.dtab[t];
-        d.offset = (int16_t)g.offsets[t];
-        d.max_value = (uint16_t)(nsym - 1);
-        for (int v = 0; v < nsym; ++v) d.sym[v] = (uint32_t)cdf[v] | ((uint32_t)(cdf[v + 1] - cdf[v]) << 16);
-        int v = 0;
-        for (int b = 0; b < (1 << kLutBits); ++b) {
-            const int32_t edge = b << (kScaleBits - kLutBits);
-            while (cdf[v + 1] <= edge) ++v;              // cdf[nsym] == 65536 > every edge
-            d.lut[b] = (uint8_t)v;
-            d.lute[b] = d.sym[v];
-        }
     }
-}
-
-int add_group(std::vector<CdfGroup>& groups, const int32_t* cdf, int n, int stride, const int32_t* sizes,
-              const int32_t* offsets)
-{
-    if (!cdf || !sizes || !offsets || n <= 0 || stride < 3 || stride > 34) {
-        dcvc::set_error("add_cdf: bad table (n=%d stride=%d, stride must be 3..34)", n, stride);
-        return dcvc::E_ARG;
-    }
-    CdfGroup g;
-    g.n = n;
-    g.stride = stride;
-    g.cdf.assign(cdf, cdf + (size_t)n * stride);
-    g.sizes.assign(sizes, sizes + n);
-    g.offsets.assign(offsets, offsets + n);
-    for (int i = 0; i < n; ++i) {
-        if (g.sizes[i] < 3 || g.sizes[i] > stride) {
-            dcvc::set_error("add_cdf: table %d has size %d (stride %d)", i, g.sizes[i], stride);
-            return dcvc::E_ARG;
-        }
-        const int32_t* c = g.cdf.data() + (size_t)i * stride;
-        bool ok = c[0] == 0 && c[g.sizes[i] - 1] == (1 << kScaleBits);
-        for (int j = 0; j + 1 < g.sizes[i]; ++j) ok = ok && c[j + 1] > c[j];
-        if (!ok) {
-            dcvc::set_error("add_cdf: table %d is not a strictly increasing 16-bit cdf", i);
-            return dcvc::E_ARG;
-        }
-    }
-    build_fast_tables(g);
     groups.push_back(std::move(g));
     return (int)groups.size() - 1;
 }
 
-
 // ---- sentinel scans: kept = entries whose (low) byte != 0xFF ------------------------------------
+// over uint8 table indexes or int16 packed symbols (index = low byte), 32 entries at a time
+#if defined(__AVX2__)
+inline __m256i low_bytes32(const uint8_t* p) { return _mm256_loadu_si256(reinterpret_cast<const __m256i*>(p)); }
+inline __m256i low_bytes32(const int16_t* p)
+{
+    const __m256i ff = _mm256_set1_epi16(0x00ff);
+    const __m256i a = _mm256_and_si256(_mm256_loadu_si256(reinterpret_cast<const __m256i*>(p)), ff);
+    const __m256i b = _mm256_and_si256(_mm256_loadu_si256(reinterpret_cast<const __m256i*>(p + 16)), ff);
+    return _mm256_permute4x64_epi64(_mm256_packus_epi16(a, b), 0xd8);      // packus interleaves 128-bit lanes: put them in order
+}
+#endif
+
 // 32-bit kept masks per chunk of 32 entries let the hot loops visit only the coded symbols.
-inline uint32_t kept_mask32_u8(const uint8_t* p, int64_t n_left)
+template <typename E>
+inline uint32_t kept_mask32(const E* p, int64_t n_left)
 {
 #if defined(__AVX2__)
-    if (n_left >= 32) {
-        const __m256i v = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(p));
-        return ~(uint32_t)_mm256_movemask_epi8(_mm256_cmpeq_epi8(v, _mm256_set1_epi8((char)0xff)));
-    }
+    if (n_left >= 32) return ~(uint32_t)_mm256_movemask_epi8(_mm256_cmpeq_epi8(low_bytes32(p), _mm256_set1_epi8((char)0xff)));
 #endif
     uint32_t m = 0;
-    const int k = (int)(n_left < 32 ? n_left : 32);
-    for (int i = 0; i < k; ++i) m |= (uint32_t)(p[i] != 0xff) << i;
+    for (int i = 0; i < 32 && i < n_left; ++i) m |= (uint32_t)((p[i] & 0xff) != 0xff) << i;
     return m;
 }
 
-inline uint32_t kept_mask32_i16(const int16_t* p, int64_t n_left)
-{
-#if defined(__AVX2__)
-    if (n_left >= 32) {
-        const __m256i ff = _mm256_set1_epi16(0x00ff);
-        const __m256i a = _mm256_and_si256(_mm256_loadu_si256(reinterpret_cast<const __m256i*>(p)), ff);
-        const __m256i b = _mm256_and_si256(_mm256_loadu_si256(reinterpret_cast<const __m256i*>(p + 16)), ff);
-        // packus interleaves 128-bit lanes: fix the order with a 64-bit permute
-        const __m256i lo = _mm256_permute4x64_epi64(_mm256_packus_epi16(a, b), 0xd8);
-        return ~(uint32_t)_mm256_movemask_epi8(_mm256_cmpeq_epi8(lo, _mm256_set1_epi8((char)0xff)));
-    }
-#endif
-    uint32_t m = 0;
-    const int k = (int)(n_left < 32 ? n_left : 32);
-    for (int i = 0; i < k; ++i) m |= (uint32_t)((p[i] & 0xff) != 0xff) << i;
-    return m;
-}
-
-// One pass over an index / packed-symbol array: kept entries per 32-entry chunk, their total and the
-// largest kept table index.  split_after(k) = the position just after the k-th kept entry (the first
-// position that belongs to the second coder when the first one takes k symbols).
+// One pass over an index / packed-symbol array: kept entries per 32-entry chunk, their total and the largest kept table index.
+// split_after(k) = the position just after the k-th kept entry (the second coder's first when the first one takes k symbols).
 struct KeptScan {
     std::vector<uint8_t> per_chunk;
     int64_t kept = 0, n = 0;
     int max_idx = 0;
 };
 
-inline void scan_kept_u8(const uint8_t* p, int64_t n, KeptScan& k)
+template <typename E>
+inline void scan_kept(const E* p, int64_t n, KeptScan& k)
 {
     k.per_chunk.resize((size_t)((n + 31) / 32));
     k.kept = 0;
@@ -192,7 +146,7 @@ inline void scan_kept_u8(const uint8_t* p, int64_t n, KeptScan& k)
     const __m256i ff = _mm256_set1_epi8((char)0xff);
     __m256i vmax = _mm256_setzero_si256();
     for (; i + 32 <= n; i += 32) {
-        const __m256i v = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(p + i));
+        const __m256i v = low_bytes32(p + i);
         const __m256i eq = _mm256_cmpeq_epi8(v, ff);
         vmax = _mm256_max_epu8(vmax, _mm256_andnot_si256(eq, v));
         const int c = __builtin_popcount(~(uint32_t)_mm256_movemask_epi8(eq));
@@ -203,59 +157,25 @@ inline void scan_kept_u8(const uint8_t* p, int64_t n, KeptScan& k)
     _mm256_store_si256(reinterpret_cast<__m256i*>(lanes), vmax);
     for (int j = 0; j < 32; ++j) mx = lanes[j] > mx ? lanes[j] : mx;
 #endif
-    for (; i < n; i += 32) {
-        int c = 0;
-        for (int64_t j = i; j < n && j < i + 32; ++j)
-            if (p[j] != 0xff) {
-                ++c;
-                mx = p[j] > mx ? p[j] : mx;
-            }
-        k.per_chunk[(size_t)(i >> 5)] = (uint8_t)c;
-        k.kept += c;
+    for (; i < n; i += 32) {             // the last, partial chunk (every chunk without AVX2)
+        const uint32_t m = kept_mask32(p + i, n - i);
+        for (uint32_t t = m; t; t &= t - 1) mx = std::max(mx, p[i + __builtin_ctz(t)] & 0xff);
+        k.per_chunk[(size_t)(i >> 5)] = (uint8_t)__builtin_popcount(m);
+        k.kept += __builtin_popcount(m);
     }
     k.max_idx = mx;
 }
 
-inline void scan_kept_i16(const int16_t* p, int64_t n, KeptScan& k)
+// the largest table index among entries that are all kept
+template <typename E>
+inline int max_index(const E* p, int64_t n)
 {
-    k.per_chunk.resize((size_t)((n + 31) / 32));
-    k.kept = 0;
-    k.n = n;
-    int64_t i = 0;
     int mx = 0;
-#if defined(__AVX2__)
-    const __m256i lo = _mm256_set1_epi16(0x00ff);
-    __m256i vmax = _mm256_setzero_si256();
-    for (; i + 32 <= n; i += 32) {
-        const __m256i a = _mm256_and_si256(_mm256_loadu_si256(reinterpret_cast<const __m256i*>(p + i)), lo);
-        const __m256i b = _mm256_and_si256(_mm256_loadu_si256(reinterpret_cast<const __m256i*>(p + i + 16)), lo);
-        const __m256i ea = _mm256_cmpeq_epi16(a, lo), eb = _mm256_cmpeq_epi16(b, lo);
-        vmax = _mm256_max_epi16(vmax, _mm256_max_epi16(_mm256_andnot_si256(ea, a), _mm256_andnot_si256(eb, b)));
-        const uint32_t skipped = (uint32_t)_mm256_movemask_epi8(_mm256_packs_epi16(ea, eb));   // lane order irrelevant
-        const int c = 32 - __builtin_popcount(skipped);
-        k.per_chunk[(size_t)(i >> 5)] = (uint8_t)c;
-        k.kept += c;
-    }
-    alignas(32) int16_t lanes[16];
-    _mm256_store_si256(reinterpret_cast<__m256i*>(lanes), vmax);
-    for (int j = 0; j < 16; ++j) mx = lanes[j] > mx ? lanes[j] : mx;
-#endif
-    for (; i < n; i += 32) {
-        int c = 0;
-        for (int64_t j = i; j < n && j < i + 32; ++j) {
-            const int v = p[j] & 0xff;
-            if (v != 0xff) {
-                ++c;
-                mx = v > mx ? v : mx;
-            }
-        }
-        k.per_chunk[(size_t)(i >> 5)] = (uint8_t)c;
-        k.kept += c;
-    }
-    k.max_idx = mx;
+    for (int64_t i = 0; i < n; ++i) mx = std::max(mx, p[i] & 0xff);
+    return mx;
 }
 
-template <typename E, uint32_t (*MASK)(const E*, int64_t)>
+template <typename E>
 inline int64_t split_after(const KeptScan& k, const E* p, int64_t take)
 {
     if (take <= 0) return 0;
@@ -263,7 +183,7 @@ inline int64_t split_after(const KeptScan& k, const E* p, int64_t take)
     int64_t seen = 0;
     size_t c = 0;
     while (seen + k.per_chunk[c] < take) seen += k.per_chunk[c++];
-    uint32_t m = MASK(p + (int64_t)c * 32, k.n - (int64_t)c * 32);
+    uint32_t m = kept_mask32(p + (int64_t)c * 32, k.n - (int64_t)c * 32);
     int pos = 0;
     for (int64_t need = take - seen; need > 0; --need) {
         pos = __builtin_ctz(m) + 1;
@@ -303,20 +223,16 @@ public:
 private:
     void run()
     {
+        std::unique_lock<std::mutex> lk(m_);
         for (;;) {
-            std::function<void()> f;
-            {
-                std::unique_lock<std::mutex> lk(m_);
-                cv_.wait(lk, [this] { return stop_ || !q_.empty(); });
-                if (q_.empty()) return;
-                f = std::move(q_.front());
-                q_.pop_front();
-            }
+            cv_.wait(lk, [this] { return stop_ || !q_.empty(); });
+            if (q_.empty()) return;
+            std::function<void()> f = std::move(q_.front());
+            q_.pop_front();
+            lk.unlock();
             f();
-            {
-                std::lock_guard<std::mutex> lk(m_);
-                --pending_;
-            }
+            lk.lock();
+            --pending_;
             done_.notify_all();
         }
     }
@@ -341,8 +257,7 @@ struct EncTask {
 
 inline void put_bits(uint32_t& r, uint8_t*& ptr, uint32_t val)
 {
-    constexpr uint32_t x_max = (1u << (kScaleBits - kBypassBits)) << kRenormShift;
-    while (r >= x_max) {
+    while (r >= kBitsXMax) {
         *(--ptr) = (uint8_t)(r & 0xff);
         r >>= 8;
     }
@@ -374,17 +289,15 @@ inline void encode_symbol(uint32_t& r, uint8_t*& ptr, int32_t symbol, const CdfG
         put_symbol(r, ptr, g.esym[(size_t)cdf_idx * g.stride + value]);
         return;
     }
-    uint32_t raw;
-    if (value < 0)
-        raw = (uint32_t)(-2 * value - 1);
-    else
-        raw = (uint32_t)(2 * (value - max_value));
+    // rans_core.hpp's put_escape, written out through an array, the count as a loop: this function's shape decides how gcc compiles
+    // the loops around it; with put_escape or bypass_groups in it they code 27 - 130 % slower (profiles/r19_rans_core_refactor.txt)
+    const uint32_t raw = escape_raw(value, max_value);
     uint8_t bins[48];
     int nb = 0;
     int n_bypass = 0;
     while ((raw >> (n_bypass * kBypassBits)) != 0) ++n_bypass;
     int v = n_bypass;
-    while (v >= kBypassMax) {
+    while (v >= (int)kBypassMax) {
         bins[nb++] = kBypassMax;
         v -= kBypassMax;
     }
@@ -392,6 +305,13 @@ inline void encode_symbol(uint32_t& r, uint8_t*& ptr, int32_t symbol, const CdfG
     for (int j = 0; j < n_bypass; ++j) bins[nb++] = (uint8_t)((raw >> (j * kBypassBits)) & kBypassMax);
     for (int i = nb - 1; i >= 0; --i) put_bits(r, ptr, bins[i]);
     put_symbol(r, ptr, g.esym[(size_t)cdf_idx * g.stride + max_value]);
+}
+
+// the flush: the state below everything else; returns the stream's first byte
+inline uint8_t* flush_state(uint32_t r, uint8_t* ptr)
+{
+    put_state(r, [&](uint32_t b) { *(--ptr) = (uint8_t)b; });
+    return ptr;
 }
 
 struct EncHalf {
@@ -422,7 +342,7 @@ struct EncHalf {
                 const int64_t len = it->end - it->begin;
                 for (int64_t c0 = ((len - 1) / 32) * 32; c0 >= 0 && len > 0; c0 -= 32) {
                     const int16_t* q = y + it->begin + c0;
-                    uint32_t m = kept_mask32_i16(q, len - c0);
+                    uint32_t m = kept_mask32(q, len - c0);
                     while (m) {
                         const int b = 31 - __builtin_clz(m);
                         m &= ~(1u << b);
@@ -432,12 +352,7 @@ struct EncHalf {
                 }
             }
         }
-        ptr -= 4;
-        ptr[0] = (uint8_t)(r >> 0);
-        ptr[1] = (uint8_t)(r >> 8);
-        ptr[2] = (uint8_t)(r >> 16);
-        ptr[3] = (uint8_t)(r >> 24);
-        stream.assign(ptr, end);
+        stream.assign(flush_state(r, ptr), end);
     }
 };
 
@@ -458,46 +373,19 @@ struct DecCursor {
         }
         return *cur++;
     }
-    inline uint32_t get_bits()
-    {
-        const uint32_t val = x & ((1u << kBypassBits) - 1);
-        x >>= kBypassBits;
-        if (x < kRansL) x = (x << 8) | next();
-        return val;
-    }
     inline int32_t decode(const DecTable& t)
     {
         const uint32_t cum = x & kMask;
         uint32_t s = t.lut[cum >> (kScaleBits - kLutBits)];
         uint32_t e = t.lute[cum >> (kScaleBits - kLutBits)];
-        uint32_t d = cum - (e & kMask);
-        while (d >= (e >> 16)) {              // cum lies past this value's range: walk up
+        uint32_t d = cum - entry_start(e);
+        while (d >= entry_freq(e)) {          // cum lies past this value's range: walk up
             e = t.sym[++s];
-            d = cum - (e & kMask);
+            d = cum - entry_start(e);
         }
-        x = (e >> 16) * (x >> kScaleBits) + d;
-        if (x < kRansL) {
-            x = (x << 8) | next();
-            if (x < kRansL) x = (x << 8) | next();
-        }
-        int32_t value = (int32_t)s;
-        if (s == t.max_value) {               // escape: Exp-Golomb-like bypass bits follow
-            // (a valid stream carries at most 16 groups - 32 bits - per escape; a corrupt one may claim any number: the
-            // count saturates, the value is assembled without signed overflow, and the decoder keeps its position rules)
-            uint32_t val = get_bits();
-            uint32_t n_bypass = val;
-            while (val == (uint32_t)kBypassMax && !overrun) {
-                val = get_bits();
-                n_bypass = n_bypass < 1024u ? n_bypass + val : n_bypass;
-            }
-            uint32_t raw = 0;
-            for (uint32_t j = 0; j < n_bypass && j < 16; ++j) raw |= get_bits() << (j * kBypassBits);
-            value = (int32_t)(raw >> 1);
-            if (raw & 1)
-                value = -value - 1;
-            else
-                value += t.max_value;
-        }
+        x = entry_freq(e) * (x >> kScaleBits) + d;
+        renorm_after_symbol(x, *this);
+        const int32_t value = s == t.max_value ? decode_escape(x, *this, t.max_value) : (int32_t)s;
         return value + t.offset;
     }
 };
@@ -516,9 +404,9 @@ struct DecHalf {
             std::reverse_copy(s, s + n, buf.begin());
         else
             std::copy(s, s + n, buf.begin());
-        state = (uint32_t)buf[0] | ((uint32_t)buf[1] << 8) | ((uint32_t)buf[2] << 16) | ((uint32_t)buf[3] << 24);
-        pos = 4;
-        overrun = n < 4;
+        DecCursor c{0, buf.data(), buf.data() + buf.size(), n < 4};      // (the 16 bytes of padding: the state is always there)
+        c.x = get_state(c);
+        close(c);
     }
     DecCursor open() const { return DecCursor{state, buf.data() + pos, buf.data() + buf.size(), overrun}; }
     void close(const DecCursor& c)
@@ -536,7 +424,7 @@ struct DecHalf {
         const DecTable* tab = g.dtab.data();
         DecCursor c = open();
         for (int64_t c0 = a; c0 < b; c0 += 32) {
-            uint32_t m = kept_mask32_u8(idx + c0, b - c0);
+            uint32_t m = kept_mask32(idx + c0, b - c0);
             decoded += __builtin_popcount(m);
             while (m) {
                 const int bit = __builtin_ctz(m);
@@ -595,41 +483,91 @@ struct dcvc_rans_dec {
     KeptScan scan;
 };
 
+namespace {
+
+template <typename Coder>
+void idle(Coder* c) { c->worker[0].wait_idle(), c->worker[1].wait_idle(); }
+
+// the coder's group `group`, or nullptr with the error text set
+const CdfGroup* group_of(const char* who, const std::vector<CdfGroup>& groups, int group)
+{
+    if (group >= 0 && group < (int)groups.size()) return &groups[group];
+    dcvc::set_error("%s: unknown cdf group %d", who, group);
+    return nullptr;
+}
+
+// E_STREAM with the error text set: `return stream_error(...)`
+template <typename... Args>
+int stream_error(const char* fmt, Args... args)
+{
+    dcvc::set_error(fmt, args...);
+    return dcvc::E_STREAM;
+}
+
+// true, with the error text set, when a coder of the decoder has read past its stream
+bool exhausted(const dcvc_rans_dec* d, const char* who)
+{
+    if (!d->half[0].overrun && !(d->two && d->half[1].overrun)) return false;
+    dcvc::set_error("%s: bit stream exhausted (corrupt or truncated stream)", who);
+    return true;
+}
+
+// the three calls both coders have
+template <typename Coder>
+int add_cdf(Coder* c, const char* who, const int32_t* cdf, int n, int stride, const int32_t* sizes, const int32_t* offsets)
+{
+    DCVC_REQUIRE(c, "%s: null coder", who);
+    return add_group(who, c->groups, cdf, n, stride, sizes, offsets);
+}
+
+template <typename Coder>
+int empty_cdf(Coder* c, const char* who)
+{
+    DCVC_REQUIRE(c, "%s: null coder", who);
+    idle(c);
+    c->groups.clear();
+    return 0;
+}
+
+template <typename Coder>
+void set_use_two(Coder* c, int two) { if (c) c->two = two != 0; }
+
+// one task for the first coder, or - with two coders - its two parts: positions [0, split) with count0 symbols and
+// [split, n) with the rest, the second part's first table being start1 (z only)
+void push_split(dcvc_rans_enc* e, EncTask t, int64_t split, int64_t n, int64_t count0, int64_t count, int start1 = 0)
+{
+    t.begin = 0;
+    t.end = split;
+    t.count = count0;
+    e->half[0].tasks.push_back(t);
+    if (!e->two) return;
+    t.begin = split;
+    t.end = n;
+    t.count = count - count0;
+    t.start_offset = start1;
+    e->half[1].tasks.push_back(std::move(t));
+}
+
+}  // namespace
+
 extern "C" {
 
 dcvc_rans_enc* dcvc_rans_enc_create(void) { return new (std::nothrow) dcvc_rans_enc(); }
 void dcvc_rans_enc_destroy(dcvc_rans_enc* e) { delete e; }
 
-int dcvc_rans_enc_add_cdf(dcvc_rans_enc* e, const int32_t* cdf, int n, int stride, const int32_t* sizes,
-                          const int32_t* offsets)
+int dcvc_rans_enc_add_cdf(dcvc_rans_enc* e, const int32_t* cdf, int n, int stride, const int32_t* sizes, const int32_t* offsets)
 {
-    DCVC_REQUIRE(e, "dcvc_rans_enc_add_cdf: null coder");
-    return add_group(e->groups, cdf, n, stride, sizes, offsets);
+    return add_cdf(e, "dcvc_rans_enc_add_cdf", cdf, n, stride, sizes, offsets);
 }
 
-int dcvc_rans_enc_empty_cdf(dcvc_rans_enc* e)
-{
-    DCVC_REQUIRE(e, "dcvc_rans_enc_empty_cdf: null coder");
-    e->worker[0].wait_idle();
-    e->worker[1].wait_idle();
-    e->groups.clear();
-    return 0;
-}
-
-void dcvc_rans_enc_set_use_two(dcvc_rans_enc* e, int two)
-{
-    if (e) e->two = two != 0;
-}
+int dcvc_rans_enc_empty_cdf(dcvc_rans_enc* e) { return empty_cdf(e, "dcvc_rans_enc_empty_cdf"); }
+void dcvc_rans_enc_set_use_two(dcvc_rans_enc* e, int two) { set_use_two(e, two); }
 
 int dcvc_rans_enc_reset(dcvc_rans_enc* e)
 {
     DCVC_REQUIRE(e, "dcvc_rans_enc_reset: null coder");
-    e->worker[0].wait_idle();
-    e->worker[1].wait_idle();
-    e->half[0].tasks.clear();
-    e->half[1].tasks.clear();
-    e->half[0].stream.clear();
-    e->half[1].stream.clear();
+    idle(e);
+    for (EncHalf& h : e->half) h.tasks.clear(), h.stream.clear();
     e->merged.clear();
     e->flushed = false;
     return 0;
@@ -638,37 +576,24 @@ int dcvc_rans_enc_reset(dcvc_rans_enc* e)
 static int enc_add_y(dcvc_rans_enc* e, const int16_t* symbols, int64_t n, int group, bool copy, const char* who)
 {
     DCVC_REQUIRE(e && (symbols || n == 0) && n >= 0, "%s: bad arguments", who);
-    DCVC_REQUIRE(group >= 0 && group < (int)e->groups.size(), "%s: unknown cdf group %d", who, group);
-    const CdfGroup& g = e->groups[group];
+    const CdfGroup* g = group_of(who, e->groups, group);
+    if (!g) return dcvc::E_ARG;
     std::shared_ptr<std::vector<int16_t>> own;
     const int16_t* y = symbols;
     if (copy) {
         own = std::make_shared<std::vector<int16_t>>(symbols, symbols + n);
         y = own->data();
     }
-    scan_kept_i16(y, n, e->scan);
-    DCVC_REQUIRE(e->scan.max_idx < g.n, "%s: cdf index %d out of range (%d tables)", who, e->scan.max_idx, g.n);
+    scan_kept(y, n, e->scan);
+    DCVC_REQUIRE(e->scan.max_idx < g->n, "%s: cdf index %d out of range (%d tables)", who, e->scan.max_idx, g->n);
     const int64_t kept = e->scan.kept;
     const int64_t n0 = e->two ? kept / 2 : kept;
-    const int64_t split = e->two ? split_after<int16_t, kept_mask32_i16>(e->scan, y, n0) : n;
-    EncTask t0;
-    t0.group = group;
-    t0.y = y;
-    t0.y_own = own;
-    t0.begin = 0;
-    t0.end = split;
-    t0.count = n0;
-    e->half[0].tasks.push_back(std::move(t0));
-    if (e->two) {
-        EncTask t1;
-        t1.group = group;
-        t1.y = y;
-        t1.y_own = own;
-        t1.begin = split;
-        t1.end = n;
-        t1.count = kept - n0;
-        e->half[1].tasks.push_back(std::move(t1));
-    }
+    const int64_t split = e->two ? split_after(e->scan, y, n0) : n;
+    EncTask t;
+    t.group = group;
+    t.y = y;
+    t.y_own = own;
+    push_split(e, std::move(t), split, n, n0, kept);
     return 0;
 }
 
@@ -682,38 +607,22 @@ int dcvc_rans_enc_encode_y_borrowed(dcvc_rans_enc* e, const int16_t* symbols, in
     return enc_add_y(e, symbols, n, group, false, "dcvc_rans_enc_encode_y_borrowed");
 }
 
-int dcvc_rans_enc_encode_z(dcvc_rans_enc* e, const int8_t* symbols, int64_t n, int group, int start_offset,
-                           int per_channel_size)
+int dcvc_rans_enc_encode_z(dcvc_rans_enc* e, const int8_t* symbols, int64_t n, int group, int start_offset, int per_channel_size)
 {
-    DCVC_REQUIRE(e && (symbols || n == 0) && n >= 0 && per_channel_size > 0, "dcvc_rans_enc_encode_z: bad arguments");
-    DCVC_REQUIRE(group >= 0 && group < (int)e->groups.size(), "dcvc_rans_enc_encode_z: unknown cdf group %d", group);
-    const CdfGroup& g = e->groups[group];
-    DCVC_REQUIRE(start_offset >= 0 && start_offset + (n + per_channel_size - 1) / per_channel_size <= g.n,
-                 "dcvc_rans_enc_encode_z: channels exceed the cdf group");
-    auto buf = std::make_shared<std::vector<int8_t>>(symbols, symbols + n);
+    const char* who = "dcvc_rans_enc_encode_z";
+    DCVC_REQUIRE(e && (symbols || n == 0) && n >= 0 && per_channel_size > 0, "%s: bad arguments", who);
+    const CdfGroup* g = group_of(who, e->groups, group);
+    if (!g) return dcvc::E_ARG;
+    DCVC_REQUIRE(start_offset >= 0 && start_offset + (n + per_channel_size - 1) / per_channel_size <= g->n,
+                 "%s: channels exceed the cdf group", who);
     const int64_t n0 = e->two ? n / 2 : n;
-    EncTask t0;
-    t0.is_z = true;
-    t0.group = group;
-    t0.start_offset = start_offset;
-    t0.per_channel = per_channel_size;
-    t0.z = buf;
-    t0.begin = 0;
-    t0.end = n0;
-    t0.count = n0;
-    e->half[0].tasks.push_back(std::move(t0));
-    if (e->two) {
-        EncTask t1;
-        t1.is_z = true;
-        t1.group = group;
-        t1.start_offset = start_offset + (int)(n0 / per_channel_size);
-        t1.per_channel = per_channel_size;
-        t1.z = buf;
-        t1.begin = n0;
-        t1.end = n;
-        t1.count = n - n0;
-        e->half[1].tasks.push_back(std::move(t1));
-    }
+    EncTask t;
+    t.is_z = true;
+    t.group = group;
+    t.start_offset = start_offset;
+    t.per_channel = per_channel_size;
+    t.z = std::make_shared<std::vector<int8_t>>(symbols, symbols + n);
+    push_split(e, std::move(t), n0, n, n0, n, start_offset + (int)(n0 / per_channel_size));
     return 0;
 }
 
@@ -728,16 +637,9 @@ int dcvc_rans_enc_flush(dcvc_rans_enc* e)
 
 int64_t dcvc_rans_enc_get_stream(dcvc_rans_enc* e, const uint8_t** data)
 {
-    if (!e || !data) {
-        dcvc::set_error("dcvc_rans_enc_get_stream: null pointer");
-        return dcvc::E_ARG;
-    }
-    if (!e->flushed) {
-        dcvc::set_error("dcvc_rans_enc_get_stream: flush() has not been called");
-        return dcvc::E_STREAM;
-    }
-    e->worker[0].wait_idle();
-    e->worker[1].wait_idle();
+    DCVC_REQUIRE(e && data, "dcvc_rans_enc_get_stream: null pointer");
+    if (!e->flushed) return stream_error("dcvc_rans_enc_get_stream: flush() has not been called");
+    idle(e);
     const std::vector<uint8_t>& s0 = e->half[0].stream;
     if (!e->two) {
         *data = s0.data();
@@ -762,32 +664,18 @@ int64_t dcvc_rans_enc_get_stream(dcvc_rans_enc* e, const uint8_t** data)
 dcvc_rans_dec* dcvc_rans_dec_create(void) { return new (std::nothrow) dcvc_rans_dec(); }
 void dcvc_rans_dec_destroy(dcvc_rans_dec* d) { delete d; }
 
-int dcvc_rans_dec_add_cdf(dcvc_rans_dec* d, const int32_t* cdf, int n, int stride, const int32_t* sizes,
-                          const int32_t* offsets)
+int dcvc_rans_dec_add_cdf(dcvc_rans_dec* d, const int32_t* cdf, int n, int stride, const int32_t* sizes, const int32_t* offsets)
 {
-    DCVC_REQUIRE(d, "dcvc_rans_dec_add_cdf: null coder");
-    return add_group(d->groups, cdf, n, stride, sizes, offsets);
+    return add_cdf(d, "dcvc_rans_dec_add_cdf", cdf, n, stride, sizes, offsets);
 }
 
-int dcvc_rans_dec_empty_cdf(dcvc_rans_dec* d)
-{
-    DCVC_REQUIRE(d, "dcvc_rans_dec_empty_cdf: null coder");
-    d->worker[0].wait_idle();
-    d->worker[1].wait_idle();
-    d->groups.clear();
-    return 0;
-}
-
-void dcvc_rans_dec_set_use_two(dcvc_rans_dec* d, int two)
-{
-    if (d) d->two = two != 0;
-}
+int dcvc_rans_dec_empty_cdf(dcvc_rans_dec* d) { return empty_cdf(d, "dcvc_rans_dec_empty_cdf"); }
+void dcvc_rans_dec_set_use_two(dcvc_rans_dec* d, int two) { set_use_two(d, two); }
 
 int dcvc_rans_dec_set_stream(dcvc_rans_dec* d, const uint8_t* data, int64_t n)
 {
     DCVC_REQUIRE(d && data && n >= 4, "dcvc_rans_dec_set_stream: stream of %lld bytes is too short", (long long)n);
-    d->worker[0].wait_idle();
-    d->worker[1].wait_idle();
+    idle(d);
     d->half[0].init(data, (size_t)n, false);
     if (d->two) d->half[1].init(data, (size_t)n, true);
     return 0;
@@ -795,14 +683,13 @@ int dcvc_rans_dec_set_stream(dcvc_rans_dec* d, const uint8_t* data, int64_t n)
 
 // common part of the two y entry points: scan, split, run coder 1 on its worker and coder 0 either
 // on its worker (asynchronous form) or on the calling thread (synchronous form)
-static int dec_run_y(dcvc_rans_dec* d, const uint8_t* ip, int64_t n, int group, int8_t* out, bool inline0,
-                     const char* who)
+static int dec_run_y(dcvc_rans_dec* d, const uint8_t* ip, int64_t n, int group, int8_t* out, bool inline0, const char* who)
 {
-    DCVC_REQUIRE(group >= 0 && group < (int)d->groups.size(), "%s: unknown cdf group %d", who, group);
-    const CdfGroup* g = &d->groups[group];
-    scan_kept_u8(ip, n, d->scan);
+    const CdfGroup* g = group_of(who, d->groups, group);
+    if (!g) return dcvc::E_ARG;
+    scan_kept(ip, n, d->scan);
     DCVC_REQUIRE(d->scan.max_idx < g->n, "%s: cdf index %d out of range (%d tables)", who, d->scan.max_idx, g->n);
-    const int64_t split = d->two ? split_after<uint8_t, kept_mask32_u8>(d->scan, ip, d->scan.kept / 2) : n;
+    const int64_t split = d->two ? split_after(d->scan, ip, d->scan.kept / 2) : n;
     if (d->two) d->worker[1].post([=] { d->half[1].decode_range(*g, ip, out, split, n); });
     if (inline0)
         d->half[0].decode_range(*g, ip, out, 0, split);
@@ -814,8 +701,7 @@ static int dec_run_y(dcvc_rans_dec* d, const uint8_t* ip, int64_t n, int group, 
 int dcvc_rans_dec_decode_y(dcvc_rans_dec* d, const uint8_t* indexes, int64_t n, int group)
 {
     DCVC_REQUIRE(d && (indexes || n == 0) && n >= 0, "dcvc_rans_dec_decode_y: bad arguments");
-    d->worker[0].wait_idle();
-    d->worker[1].wait_idle();
+    idle(d);
     d->idx.assign(indexes, indexes + n);          // inputs are copied on entry
     d->out.resize((size_t)n);
     return dec_run_y(d, d->idx.data(), n, group, d->out.data(), false, "dcvc_rans_dec_decode_y");
@@ -824,51 +710,41 @@ int dcvc_rans_dec_decode_y(dcvc_rans_dec* d, const uint8_t* indexes, int64_t n, 
 int dcvc_rans_dec_decode_and_get_y(dcvc_rans_dec* d, const uint8_t* indexes, int64_t n, int group, int8_t* out)
 {
     DCVC_REQUIRE(d && ((indexes && out) || n == 0) && n >= 0, "dcvc_rans_dec_decode_and_get_y: bad arguments");
-    d->worker[0].wait_idle();
-    d->worker[1].wait_idle();
+    idle(d);
     d->out.clear();
     const int rc = dec_run_y(d, indexes, n, group, out, true, "dcvc_rans_dec_decode_and_get_y");
     if (rc) return rc;
     d->worker[1].wait_idle();
-    if (d->half[0].overrun || (d->two && d->half[1].overrun)) {
-        dcvc::set_error("dcvc_rans_dec_decode_and_get_y: bit stream exhausted (corrupt or truncated stream)");
-        return dcvc::E_STREAM;
-    }
-    return 0;
+    return exhausted(d, "dcvc_rans_dec_decode_and_get_y") ? dcvc::E_STREAM : 0;
 }
 
 int dcvc_rans_dec_decode_compact(dcvc_rans_dec* d, const uint8_t* indexes, int64_t count, int group, int8_t* out)
 {
-    DCVC_REQUIRE(d && ((indexes && out) || count == 0) && count >= 0, "dcvc_rans_dec_decode_compact: bad arguments");
-    DCVC_REQUIRE(group >= 0 && group < (int)d->groups.size(), "dcvc_rans_dec_decode_compact: unknown cdf group %d", group);
-    d->worker[0].wait_idle();
-    d->worker[1].wait_idle();
+    const char* who = "dcvc_rans_dec_decode_compact";
+    DCVC_REQUIRE(d && ((indexes && out) || count == 0) && count >= 0, "%s: bad arguments", who);
+    const CdfGroup* g = group_of(who, d->groups, group);
+    if (!g) return dcvc::E_ARG;
+    idle(d);
     d->out.clear();
-    const CdfGroup* g = &d->groups[group];
-    int mx = 0;
-    for (int64_t i = 0; i < count; ++i) mx = indexes[i] > mx ? indexes[i] : mx;
-    DCVC_REQUIRE(mx < g->n, "dcvc_rans_dec_decode_compact: cdf index %d out of range (%d tables)", mx, g->n);
+    const int mx = max_index(indexes, count);
+    DCVC_REQUIRE(mx < g->n, "%s: cdf index %d out of range (%d tables)", who, mx, g->n);
     // the same split as dec_run_y: the first coder takes floor(count / 2) symbols, the second the rest
     const int64_t k0 = d->two ? count / 2 : count;
     if (d->two) d->worker[1].post([=] { d->half[1].decode_packed(*g, indexes, out, k0, count); });
     d->half[0].decode_packed(*g, indexes, out, 0, k0);
     d->worker[1].wait_idle();
-    if (d->half[0].overrun || (d->two && d->half[1].overrun)) {
-        dcvc::set_error("dcvc_rans_dec_decode_compact: bit stream exhausted (corrupt or truncated stream)");
-        return dcvc::E_STREAM;
-    }
-    return 0;
+    return exhausted(d, who) ? dcvc::E_STREAM : 0;
 }
 
 int dcvc_rans_dec_decode_z(dcvc_rans_dec* d, int64_t total, int group, int start_offset, int per_channel_size)
 {
-    DCVC_REQUIRE(d && total >= 0 && per_channel_size > 0, "dcvc_rans_dec_decode_z: bad arguments");
-    DCVC_REQUIRE(group >= 0 && group < (int)d->groups.size(), "dcvc_rans_dec_decode_z: unknown cdf group %d", group);
-    const CdfGroup* g = &d->groups[group];
+    const char* who = "dcvc_rans_dec_decode_z";
+    DCVC_REQUIRE(d && total >= 0 && per_channel_size > 0, "%s: bad arguments", who);
+    const CdfGroup* g = group_of(who, d->groups, group);
+    if (!g) return dcvc::E_ARG;
     DCVC_REQUIRE(start_offset >= 0 && start_offset + (total + per_channel_size - 1) / per_channel_size <= g->n,
-                 "dcvc_rans_dec_decode_z: channels exceed the cdf group");
-    d->worker[0].wait_idle();
-    d->worker[1].wait_idle();
+                 "%s: channels exceed the cdf group", who);
+    idle(d);
     d->out.assign((size_t)total, 0);
     int8_t* out = d->out.data();
     const int64_t n0 = d->two ? total / 2 : total;
@@ -882,21 +758,11 @@ int dcvc_rans_dec_decode_z(dcvc_rans_dec* d, int64_t total, int group, int start
 
 int64_t dcvc_rans_dec_get(dcvc_rans_dec* d, int8_t* out, int64_t capacity)
 {
-    if (!d || !out) {
-        dcvc::set_error("dcvc_rans_dec_get: null pointer");
-        return dcvc::E_ARG;
-    }
-    d->worker[0].wait_idle();
-    d->worker[1].wait_idle();
-    if (d->half[0].overrun || (d->two && d->half[1].overrun)) {
-        dcvc::set_error("dcvc_rans_dec_get: bit stream exhausted (corrupt or truncated stream)");
-        return dcvc::E_STREAM;
-    }
-    if ((int64_t)d->out.size() > capacity) {
-        dcvc::set_error("dcvc_rans_dec_get: output buffer too small (%lld > %lld)", (long long)d->out.size(),
-                        (long long)capacity);
-        return dcvc::E_ARG;
-    }
+    DCVC_REQUIRE(d && out, "dcvc_rans_dec_get: null pointer");
+    idle(d);
+    if (exhausted(d, "dcvc_rans_dec_get")) return dcvc::E_STREAM;
+    DCVC_REQUIRE((int64_t)d->out.size() <= capacity, "dcvc_rans_dec_get: output buffer too small (%lld > %lld)",
+                 (long long)d->out.size(), (long long)capacity);
     std::memcpy(out, d->out.data(), d->out.size());
     return (int64_t)d->out.size();
 }
@@ -904,46 +770,35 @@ int64_t dcvc_rans_dec_get(dcvc_rans_dec* d, int8_t* out, int64_t capacity)
 int dcvc_rans_dec_check_end(dcvc_rans_dec* d)
 {
     DCVC_REQUIRE(d, "dcvc_rans_dec_check_end: null coder");
-    d->worker[0].wait_idle();
-    d->worker[1].wait_idle();
+    idle(d);
+    if (exhausted(d, "dcvc_rans_dec_check_end")) return dcvc::E_STREAM;
     const int halves = d->two ? 2 : 1;
     int64_t consumed = 0, used = 0;
     for (int h = 0; h < halves; ++h) {
         const DecHalf& c = d->half[h];
         if (c.buf.size() < 16) continue;                     // set_stream() not called
-        if (c.overrun) {
-            dcvc::set_error("dcvc_rans_dec_check_end: bit stream exhausted (corrupt or truncated stream)");
-            return dcvc::E_STREAM;
-        }
         if (c.decoded == 0) continue;                        // an empty half has no stream of its own
         // decoding undoes the encoder step by step: after the last symbol the state is the encoder's initial one
-        if (c.state != kRansL) {
-            dcvc::set_error("dcvc_rans_dec_check_end: coder %d does not end in its initial state (corrupt or truncated "
-                            "stream, or not every symbol of the frame has been decoded)", h);
-            return dcvc::E_STREAM;
-        }
+        if (c.state != kRansL)
+            return stream_error("dcvc_rans_dec_check_end: coder %d does not end in its initial state (corrupt or truncated "
+                                "stream, or not every symbol of the frame has been decoded)", h);
         consumed += (int64_t)c.pos;
         ++used;
     }
     if (used == halves) {
         // every byte belongs to a coder: the two halves share at most 8 bytes (merge rule of get_encoded_stream)
         const int64_t n = (int64_t)d->half[0].buf.size() - 16;
-        if (consumed < n || consumed > n + (d->two ? 8 : 0)) {
-            dcvc::set_error("dcvc_rans_dec_check_end: %lld of %lld stream bytes consumed (trailing or missing bytes)",
-                            (long long)consumed, (long long)n);
-            return dcvc::E_STREAM;
-        }
+        if (consumed < n || consumed > n + (d->two ? 8 : 0))
+            return stream_error("dcvc_rans_dec_check_end: %lld of %lld stream bytes consumed (trailing or missing bytes)",
+                                (long long)consumed, (long long)n);
     }
     return 0;
 }
 
 // ------------------------------------------------------------------ chunked y units (this project's stream extension)
-// One y unit = ceil(count / S) little-endian uint16 chunk byte lengths, then the chunk bodies.  A chunk is S kept symbols
-// (the last one fewer) coded as an independent stream of the arithmetic above: state kRansL, symbols pushed in reverse,
-// 4-byte flush - byte for byte what reset(); encode_y(chunk); flush() of ONE coder writes.  Independent chunks are what
-// lets csrc/dcvc_rans_dev.hip code a unit with one GPU lane per chunk; this is the format's normative implementation, the
-// encoder's fallback and what decodes such a stream on a machine without a GPU.  docs/chunked_stream.md has the layout.
-static bool chunked_args_ok(int log2_s) { return log2_s >= 8 && log2_s <= 12; }
+// The unit of rans_core.hpp; a chunk is byte for byte what reset(); encode_y(chunk); flush() of ONE coder writes.
+// Independent chunks are what lets csrc/dcvc_rans_dev.hip code a unit with one GPU lane per chunk; this is the format's
+// normative implementation, the encoder's fallback and what decodes such a stream on a machine without a GPU.
 
 int64_t dcvc_rans_chunked_encode_y(dcvc_rans_enc* e, const int16_t* symbols, int64_t count, int group, int log2_s,
                                    uint8_t* out, int64_t capacity)
@@ -951,12 +806,11 @@ int64_t dcvc_rans_chunked_encode_y(dcvc_rans_enc* e, const int16_t* symbols, int
     const char* who = "dcvc_rans_chunked_encode_y";
     DCVC_REQUIRE(e && (symbols || count == 0) && count >= 0 && (out || capacity == 0) && capacity >= 0, "%s: bad arguments", who);
     DCVC_REQUIRE(chunked_args_ok(log2_s), "%s: log2 of the chunk size is %d (8 .. 12)", who, log2_s);
-    DCVC_REQUIRE(group >= 0 && group < (int)e->groups.size(), "%s: unknown cdf group %d", who, group);
-    const CdfGroup& g = e->groups[group];
-    int mx = 0;
-    for (int64_t i = 0; i < count; ++i) mx = std::max(mx, symbols[i] & 0xff);
-    DCVC_REQUIRE(mx < g.n, "%s: cdf index %d out of range (%d tables; the symbols must be the kept ones only)", who, mx, g.n);
-    const int64_t S = (int64_t)1 << log2_s, nch = (count + S - 1) / S;
+    const CdfGroup* g = group_of(who, e->groups, group);
+    if (!g) return dcvc::E_ARG;
+    const int mx = max_index(symbols, count);
+    DCVC_REQUIRE(mx < g->n, "%s: cdf index %d out of range (%d tables; the symbols must be the kept ones only)", who, mx, g->n);
+    const int64_t S = (int64_t)1 << log2_s, nch = chunks(count, log2_s);
     DCVC_REQUIRE(capacity >= 2 * nch, "%s: output buffer of %lld bytes is too small", who, (long long)capacity);
     // an int8 symbol costs at most 30 bits (16 for the escape symbol, 14 bypass bits): 4 bytes each, 4 for the flush, and
     // put_symbol's unconditional store below the pointer - 16 KB for S = 4096, so a chunk length always fits its uint16
@@ -970,18 +824,13 @@ int64_t dcvc_rans_chunked_encode_y(dcvc_rans_enc* e, const int16_t* symbols, int
         uint32_t r = kRansL;
         for (int64_t i = b - 1; i >= a; --i) {
             const int32_t cs = symbols[i];
-            encode_symbol(r, ptr, cs >> 8, g, cs & 0xff);
+            encode_symbol(r, ptr, cs >> 8, *g, cs & 0xff);
         }
-        ptr -= 4;
-        ptr[0] = (uint8_t)(r >> 0);
-        ptr[1] = (uint8_t)(r >> 8);
-        ptr[2] = (uint8_t)(r >> 16);
-        ptr[3] = (uint8_t)(r >> 24);
+        ptr = flush_state(r, ptr);
         const int64_t len = end - ptr;
         DCVC_REQUIRE(len <= 0xffff, "%s: chunk %lld takes %lld bytes (the length field has 16 bits)", who, (long long)c, (long long)len);
         DCVC_REQUIRE(pos + len <= capacity, "%s: output buffer of %lld bytes is too small", who, (long long)capacity);
-        out[2 * c] = (uint8_t)(len & 0xff);
-        out[2 * c + 1] = (uint8_t)(len >> 8);
+        put_chunk_len(out, c, (uint32_t)len);
         std::memcpy(out + pos, ptr, (size_t)len);
         pos += len;
     }
@@ -995,41 +844,31 @@ int dcvc_rans_chunked_decode_y(dcvc_rans_dec* d, const uint8_t* unit, int64_t un
     DCVC_REQUIRE(d && (unit || unit_bytes == 0) && unit_bytes >= 0 && ((indexes && out) || count == 0) && count >= 0,
                  "%s: bad arguments", who);
     DCVC_REQUIRE(chunked_args_ok(log2_s), "%s: log2 of the chunk size is %d (8 .. 12)", who, log2_s);
-    DCVC_REQUIRE(group >= 0 && group < (int)d->groups.size(), "%s: unknown cdf group %d", who, group);
-    const CdfGroup& g = d->groups[group];
-    int mx = 0;
-    for (int64_t i = 0; i < count; ++i) mx = indexes[i] > mx ? indexes[i] : mx;
-    DCVC_REQUIRE(mx < g.n, "%s: cdf index %d out of range (%d tables)", who, mx, g.n);
-    const int64_t S = (int64_t)1 << log2_s, nch = (count + S - 1) / S;
-    if (2 * nch > unit_bytes) {
-        dcvc::set_error("%s: %lld symbols need a length table of %lld bytes, the unit has %lld", who, (long long)count,
-                        (long long)(2 * nch), (long long)unit_bytes);
-        return dcvc::E_STREAM;
-    }
+    const CdfGroup* g = group_of(who, d->groups, group);
+    if (!g) return dcvc::E_ARG;
+    const int mx = max_index(indexes, count);
+    DCVC_REQUIRE(mx < g->n, "%s: cdf index %d out of range (%d tables)", who, mx, g->n);
+    const int64_t S = (int64_t)1 << log2_s, nch = chunks(count, log2_s);
+    if (2 * nch > unit_bytes)
+        return stream_error("%s: %lld symbols need a length table of %lld bytes, the unit has %lld", who, (long long)count,
+                            (long long)(2 * nch), (long long)unit_bytes);
     int64_t total = 2 * nch;
-    for (int64_t c = 0; c < nch; ++c) total += (int64_t)unit[2 * c] | ((int64_t)unit[2 * c + 1] << 8);
-    if (total != unit_bytes) {
-        dcvc::set_error("%s: the length table adds up to %lld bytes, the unit has %lld", who, (long long)total, (long long)unit_bytes);
-        return dcvc::E_STREAM;
-    }
-    const DecTable* tab = g.dtab.data();
+    for (int64_t c = 0; c < nch; ++c) total += chunk_len(unit, c);
+    if (total != unit_bytes)
+        return stream_error("%s: the length table adds up to %lld bytes, the unit has %lld", who, (long long)total,
+                            (long long)unit_bytes);
+    const DecTable* tab = g->dtab.data();
     const uint8_t* p = unit + 2 * nch;
     for (int64_t c = 0; c < nch; ++c) {
-        const int64_t len = (int64_t)unit[2 * c] | ((int64_t)unit[2 * c + 1] << 8);
-        bool ok = len >= 4;
-        if (ok) {
-            DecCursor cur{(uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24), p + 4, p + len,
-                          false};
-            const int64_t a = c * S, b = std::min(count, a + S);
-            for (int64_t i = a; i < b; ++i) out[i] = (int8_t)cur.decode(tab[indexes[i]]);
-            // done with a chunk = exactly its bytes consumed and the state back at the encoder's initial one
-            ok = !cur.overrun && cur.cur == cur.end && cur.x == kRansL;
-        }
-        if (!ok) {
-            dcvc::set_error("%s: chunk %lld of %lld does not end on its last byte in the initial state (damaged payload)", who,
-                            (long long)c, (long long)nch);
-            return dcvc::E_STREAM;
-        }
+        const int64_t len = chunk_len(unit, c);
+        DecCursor cur{0, p, p + len, len < 4};
+        if (len >= 4) cur.x = get_state(cur);
+        const int64_t a = c * S, b = std::min(count, a + S);
+        for (int64_t i = a; i < b && len >= 4; ++i) out[i] = (int8_t)cur.decode(tab[indexes[i]]);
+        // done with a chunk = exactly its bytes consumed and the state back at the encoder's initial one
+        if (cur.overrun || cur.cur != cur.end || cur.x != kRansL)
+            return stream_error("%s: chunk %lld of %lld does not end on its last byte in the initial state (damaged payload)", who,
+                                (long long)c, (long long)nch);
         p += len;
     }
     return 0;

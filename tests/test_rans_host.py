@@ -175,6 +175,8 @@ def test_errors_are_reported():
         c.set_stream(b"\x00")                          # too short
     with pytest.raises(_lib.DcvcError):
         c.get_encoded_stream()                         # flush() not called
+    with pytest.raises(_lib.DcvcError):                # an offset no decoder table can hold (int16): refused, as by the device coder
+        c.add_cdf(np.array([[0, 30000, 65536]], np.int32), np.array([3], np.int32), np.array([40000], np.int32))
 
 
 @pytest.mark.parametrize("two", [0, 1])
