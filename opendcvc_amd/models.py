@@ -592,6 +592,17 @@ class DMC(CompressionModel):
         outs = L.dcb_chain(blocks + self._layers["fe2"], self._fe_input(variant, ref_buf), return_all=True)
         return outs[len(blocks) - 1], outs[-1]
 
+    def _encoder(self, xin, ctx, q_encoder):
+        """contextual encoder (video_model.py:52-78) on the unshuffled frame xin and the context: y"""
+        n = self._layers
+        e = L.dcb_chain(n["enc_conv2"] + [n["enc_conv3"]], n["enc_conv1"](xin), ctx, quant=q_encoder)
+        return n["enc_down"](e)
+
+    def _hyper_encoder(self, y):
+        """y, replicate-padded to a multiple of 4 -> z (before rounding)"""
+        n = self._layers
+        return n["hyper_enc"][2](n["hyper_enc"][1](n["hyper_enc"][0](self._pad_for_y(y))))
+
     def _branch_stream(self, device):
         """second stream of this model for branches inside a run.  One per model instance, like the scratch its kernels
         use (nn.Scratch is per stream): safe because one instance is inside one frame call at a time (_ModelScope) - the
@@ -716,7 +727,6 @@ class DMC(CompressionModel):
         host only codes z and concatenates; the returned dict then carries chunked=True (write it as NAL_P_CHUNKED)."""
         dtype, device = self._ensure_layers()
         form = handoff.encoder_form(self, chunked)
-        n = self._layers
         C = arch.DMC_CH_Y
         x = x.to(device=device, dtype=dtype)
         _, _, H, W = x.shape
@@ -735,10 +745,9 @@ class DMC(CompressionModel):
                 x1, ctx = ahead[2], ahead[3]
             else:
                 x1, ctx = self._extractor_both(variant, ref_buf)
-            e = L.dcb_chain(n["enc_conv2"] + [n["enc_conv3"]], n["enc_conv1"](xin), ctx, quant=q["q_encoder"])
-            y = n["enc_down"](e)
+            y = self._encoder(xin, ctx, q["q_encoder"])
             yh, yw = y.shape[0], y.shape[1]
-            z = n["hyper_enc"][2](n["hyper_enc"][1](n["hyper_enc"][0](self._pad_for_y(y))))
+            z = self._hyper_encoder(y)
             z_hat, z8 = self._quantize_z(z)
             params = self._prior_params(z_hat, x1, q["q_feature"], yh, yw)
             nsym = (C // 2) * yh * yw
@@ -928,6 +937,11 @@ class DMCI(CompressionModel):
         o = L.dcb_chain(n["dec_1"], n["dec_up"](y_hat), quant=q)
         return n["dec_2"](o)             # (the picture: _picture_out)
 
+    def _hyper_encoder(self, y):
+        """y, replicate-padded to a multiple of 4 -> z (before rounding)"""
+        n = self._layers
+        return n["hyper_enc"][2](n["hyper_enc"][1](n["hyper_enc"][0](self._pad_for_y(y))))
+
     def _prior_params(self, z_hat, yh, yw):
         n = self._layers
         p = n["hyper_dec"][2](n["hyper_dec"][1](n["hyper_dec"][0](z_hat)))
@@ -956,7 +970,7 @@ class DMCI(CompressionModel):
         def front():
             y = n["enc_down"](L.dcb_chain(n["enc_2"], n["enc_1"](xin, quant=q["q_scale_enc"])))
             yh, yw = y.shape[0], y.shape[1]
-            z = n["hyper_enc"][2](n["hyper_enc"][1](n["hyper_enc"][0](self._pad_for_y(y))))
+            z = self._hyper_encoder(y)
             z_hat, z8 = self._quantize_z(z)
             params = self._prior_params(z_hat, yh, yw)
             common = n["reduction"](params)

@@ -133,13 +133,23 @@ def hwc_to_nchw(x):
 class Net:
     """Weight dictionary + the layer primitives built on it."""
 
-    def __init__(self, sd):
+    def __init__(self, sd, f16=False):
+        """f16: conv / dcb (and subpel, res_down, res_up built on them) are the fp16-storage emulations conv_f16 / dcb_f16
+        below; the codec classes then also round at the model's own stores (scale / conv_q / dcb_q)."""
         self.sd = {k: _f32(np.asarray(v)) for k, v in sd.items()}
+        self.f16 = bool(f16)
+        if self.f16:
+            # the fp16 model's parameters are the .half() ones: CompressionModel._ensure_layers (models.py:352-355) builds its layers
+            # and its q_* tables from state_dict().float() of the converted module, so every weight, bias and quant step is
+            # rounded to fp16 once BEFORE dcvc_dcb_create / dcvc_conv_create pre-scale and round the packed weights again
+            self.sd = {k: self._rh(v) for k, v in self.sd.items()}
 
     def has(self, k):
         return k in self.sd
 
     def conv(self, x, prefix, stride=1, pad=0):
+        if self.f16:
+            return self.conv_f16(x, prefix, stride, pad)
         w = self.sd[prefix + ".weight"]
         b = self.sd[prefix + ".bias"]
         if w.shape[2] == 1 and stride == 1:
@@ -148,6 +158,8 @@ class Net:
 
     def dcb(self, x, prefix, shortcut=False, q=None):
         """DepthConvBlock.forward_torch (layers.py:92-106); q is a per-channel vector."""
+        if self.f16:
+            return self.dcb_f16(x, prefix, shortcut=shortcut, q=q)
         sd = self.sd
         H, W, Cin = x.shape
         C = sd[prefix + ".dc.0.weight"].shape[0]
@@ -209,11 +221,7 @@ class Net:
         else:
             xi = x
         a = rh(self._gate16(conv1x1(xi, rh(ka * g(".dc.0.weight")), ka * g(".dc.0.bias"))))   # kAct * wsilu(.)
-        H, W, _ = a.shape
-        d = np.empty((H, W, C), np.float32)
-        wd = rh(g(".dc.2.weight") / ka)
-        lib().orc_dw3x3(_ptr(_f32(a)), H, W, C, _ptr(_f32(wd)), _ptr(_f32(g(".dc.2.bias"))), _ptr(d))
-        d = rh(d)
+        d = rh(self._dw16(a, rh(g(".dc.2.weight") / ka), g(".dc.2.bias"), prefix))
         o = rh(rh(conv1x1(d, rh(g(".dc.3.weight")), g(".dc.3.bias"))) + xi)
         u = conv1x1(o, rh(ka * g(".ffn.0.weight")), ka * g(".ffn.0.bias"))
         v = rh(self._gate16(u[:, :, :2 * C]) + self._gate16(u[:, :, 2 * C:]))
@@ -223,6 +231,35 @@ class Net:
         if q is not None:
             r = r * _f32(q).reshape(1, 1, -1)
         return rh(r)
+
+    def _dw16(self, a, wd, bd, prefix):
+        """the depthwise 3x3 of dcb_f16 in fp32 (its own method: tests/test_oracle_f16_model.py seeds a halo fault here)"""
+        H, W, C = a.shape
+        d = np.empty((H, W, C), np.float32)
+        lib().orc_dw3x3(_ptr(_f32(a)), H, W, C, _ptr(_f32(wd)), _ptr(_f32(bd)), _ptr(d))
+        return d
+
+    # ---- the model's own stores: what opendcvc_amd/models.py adds to the layers' roundings in fp16 mode --------------
+    def scale(self, x, q):
+        """x * q per channel.  fp16: the product is rounded once - Conv2d(in_scale=q) stages x * q in the element type
+        (opendcvc_amd/nn.py:244-245 Conv2d.__call__; models.py:627,636 DMC._prior_params: n["temporal"](x1, in_scale=q_feature))"""
+        y = _f32(x) * _f32(q).reshape(1, 1, -1)
+        return self._rh(y) if self.f16 else y
+
+    def conv_q(self, x, prefix, q):
+        """conv, then * q.  fp16: the conv's quant epilogue, one rounding at the store (models.py:529 DMC._build_layers:
+        dec_conv2 = Conv2d(..., epilogue=EPI_BIAS_QUANT); models.py:645 DMC._decoder passes conv_quant=q_decoder)"""
+        if self.f16:
+            return self.conv_f16(x, prefix, epilogue="quant", q=q)
+        return self.conv(x, prefix) * q
+
+    def dcb_q(self, x, prefix, q):
+        """block, then * q.  fp16: q is folded into the block's final store, one rounding (nn.py:192 dcb_chain hands `quant` to the
+        last block; models.py:598 DMC._encoder: quant=q_encoder on encoder.conv3, models.py:650 DMC._recon_head: quant=q_recon;
+        DMCI: models.py:932 enc_1 and models.py:937 dec_1.12 take their q the same way, through Net.dcb(q=...))"""
+        if self.f16:
+            return self.dcb_f16(x, prefix, q=q)
+        return self.dcb(x, prefix) * q
 
     def subpel(self, x, prefix, pad):
         """SubpelConv2x (layers.py:29-52): conv -> PixelShuffle(2)."""
@@ -442,8 +479,8 @@ def _chw_flat(x):
 
 
 class CodecBase:
-    def __init__(self, sd, z_channel, qp_total):
-        self.net = Net(sd)
+    def __init__(self, sd, z_channel, qp_total, f16=False):
+        self.net = Net(sd, f16=f16)
         self.sd = self.net.sd
         self.z_channel = z_channel
         self.qp_total = qp_total
@@ -516,8 +553,10 @@ class CodecBase:
 class OracleDMC(CodecBase):
     QP_SHIFT = (0, 8, 4)
 
-    def __init__(self, sd):
-        super().__init__(sd, 128, 64 + 8)
+    def __init__(self, sd, f16=False):
+        """f16=True: the sub-network methods below run the fp16-storage emulation (Net(sd, f16=True)) and round where
+        opendcvc_amd/models.py stores in fp16 mode; the frame API (compress / decompress) is an fp32 restatement only."""
+        super().__init__(sd, 128, 64 + 8, f16=f16)
         self.ref_feature = None     # [H/8, W/8, 256]
         self.ref_frame = None       # [H, W, 3]
         self.trace = {}
@@ -555,7 +594,7 @@ class OracleDMC(CodecBase):
     def extractor_part1(self, f, q_feature):
         n = self.net
         x1 = n.dcb(n.dcb(f, "feature_extractor.conv1.0"), "feature_extractor.conv1.1")
-        return x1, x1 * q_feature
+        return x1, n.scale(x1, q_feature)
 
     def extractor_part2(self, x1):
         for i in range(4):
@@ -567,8 +606,7 @@ class OracleDMC(CodecBase):
         f = n.conv(pixel_unshuffle(x, 8), "encoder.conv1")
         f = n.dcb(np.concatenate([f, ctx], 2), "encoder.conv2.0")
         f = n.dcb(f, "encoder.conv2.1")
-        f = n.dcb(f, "encoder.conv3")
-        f = f * q_enc
+        f = n.dcb_q(f, "encoder.conv3", q_enc)
         return n.conv(f, "encoder.down", 2, 1)
 
     def hyper_encoder(self, y):
@@ -597,15 +635,20 @@ class OracleDMC(CodecBase):
         f = n.subpel(y_hat, "decoder.up", 1)
         f = n.dcb(np.concatenate([f, ctx], 2), "decoder.conv1.0")
         f = n.dcb(n.dcb(f, "decoder.conv1.1"), "decoder.conv1.2")
-        return n.conv(f, "decoder.conv2") * q_dec
+        return n.conv_q(f, "decoder.conv2", q_dec)
 
-    def recon(self, feature, q_recon):
+    def recon_head(self, feature, q_recon):
+        """recon_generation_net up to its last conv.  The head's bias is added in the conv (models.py:651 DMC._recon_head:
+        n["recon_head"](o); models.py:391 _picture_out calls _shuffle8_clamp with bias=None), so fp16 rounds after the bias; shuffle and clamp move data only."""
         n = self.net
         o = n.dcb(feature, "recon_generation_net.conv.0")
-        for i in range(1, 4):
+        for i in range(1, 3):
             o = n.dcb(o, f"recon_generation_net.conv.{i}")
-        o = n.conv(o * q_recon, "recon_generation_net.head")
-        return np.clip(pixel_shuffle(o, 8), np.float32(0), np.float32(1))
+        o = n.dcb_q(o, "recon_generation_net.conv.3", q_recon)
+        return n.conv(o, "recon_generation_net.head")
+
+    def recon(self, feature, q_recon):
+        return np.clip(pixel_shuffle(self.recon_head(feature, q_recon), 8), np.float32(0), np.float32(1))
 
     # -- frame API
     def compress(self, x, qp):
@@ -678,8 +721,8 @@ class OracleDMC(CodecBase):
 # --------------------------------------------------------------------------- DMCI (I frames)
 
 class OracleDMCI(CodecBase):
-    def __init__(self, sd):
-        super().__init__(sd, 128, 64)
+    def __init__(self, sd, f16=False):
+        super().__init__(sd, 128, 64, f16=f16)
         self.trace = {}
 
     def q(self, name, qp):
@@ -692,14 +735,17 @@ class OracleDMCI(CodecBase):
             o = n.dcb(o, f"enc.enc_2.{i}")
         return n.conv(o, "enc.enc_2.6", 2, 1)
 
-    def dec(self, y_hat, q):
+    def dec_head(self, y_hat, q):
+        """the synthesis transform up to dec_2 (what models.py DMCI._dec returns; the picture is shuffle + clamp of it)"""
         n = self.net
         o = n.res_up(y_hat, "dec.dec_1.0")
         for i in range(1, 12):
             o = n.dcb(o, f"dec.dec_1.{i}")
         o = n.dcb(o, "dec.dec_1.12", q=q)
-        o = n.dcb(o, "dec.dec_2")
-        return np.clip(pixel_shuffle(o, 8), np.float32(0), np.float32(1))
+        return n.dcb(o, "dec.dec_2")
+
+    def dec(self, y_hat, q):
+        return np.clip(pixel_shuffle(self.dec_head(y_hat, q), 8), np.float32(0), np.float32(1))
 
     def hyper_enc(self, y):
         n = self.net
@@ -712,6 +758,9 @@ class OracleDMCI(CodecBase):
             p = n.dcb(p, f"y_prior_fusion.{i}")
         p = n.conv(p, "y_prior_fusion.3")
         return np.ascontiguousarray(p[:yh, :yw])
+
+    def reduction(self, params):
+        return self.net.conv(params, "y_spatial_prior_reduction")
 
     def spatial_prior(self, x, step):
         n = self.net
@@ -736,7 +785,7 @@ class OracleDMCI(CodecBase):
         yh, yw, C = y.shape
         params = self.prior_params(z_hat, yh, yw)
         q_enc, q_dec, scales, means = self._separate(params)
-        common = n.conv(params, "y_spatial_prior_reduction")
+        common = self.reduction(params)
         masks = masks_4x(yh, yw, C)
         yq = y * q_enc
         w4 = lambda a: (a[:, :, :C // 4] + a[:, :, C // 4:C // 2]) + (a[:, :, C // 2:3 * C // 4] + a[:, :, 3 * C // 4:])
@@ -772,7 +821,7 @@ class OracleDMCI(CodecBase):
         params = self.prior_params(z_hat, yh, yw)
         _, q_dec, scales, means = self._separate(params)
         C = scales.shape[2]
-        common = n.conv(params, "y_spatial_prior_reduction")
+        common = self.reduction(params)
         masks = masks_4x(yh, yw, C)
         w4 = lambda a: (a[:, :, :C // 4] + a[:, :, C // 4:C // 2]) + (a[:, :, C // 2:3 * C // 4] + a[:, :, 3 * C // 4:])
         so_far = None
