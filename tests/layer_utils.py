@@ -23,6 +23,11 @@ def make_dcb_weights(rng, prefix, cin, c, adaptor):
     return sd
 
 
+# the block's parameters in the order DepthConvProxy.set_param takes them (set_param_with_adaptor: then the adaptor's two)
+DCB_PROXY_PARAMS = ["dc.0.weight", "dc.0.bias", "dc.2.weight", "dc.2.bias", "dc.3.weight", "dc.3.bias", "ffn.0.weight",
+                    "ffn.0.bias", "ffn.2.weight", "ffn.2.bias"]
+
+
 def make_conv_weights(rng, prefix, cout, cin, k):
     return {f"{prefix}.weight": (rng.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32),
             f"{prefix}.bias": (rng.standard_normal(cout) * 0.1).astype(np.float32)}
