@@ -481,6 +481,43 @@ int dcvc_resize_frame(int dtype, const void* x_nchw, int Hp, int Wp, int H, int 
                       int WO, const int32_t* first_h, const float* coef_h, int taps_h, const int32_t* first_v,
                       const float* coef_v, int taps_v, void* stream);
 /* ------------------------------------------------------------------------------------------
+ * Active-area coding (csrc/dcvc_bars.hip; docs/active_area.md is the normative text; no reference counterpart): the
+ * letterbox / pillarbox bars of a sequence are found on the device, the encoder codes the window between them and the
+ * decode side pastes the window back.  Frames are model frames [3][Hp][Wp] (DCVC_F16 / DCVC_F32), the picture H x W at the
+ * top left.  Every comparison runs on the ORDERED KEY of a sample: u = the bits of (float)x, key = u ^ 0x80000000 if the
+ * sign bit is clear, else ~u - monotonic over all non-NaN floats (-0 below +0); a NaN is the largest or the smallest key
+ * of its line and fails every test below.
+ *
+ * Envelope (workspace: device, 4-byte aligned, dcvc_bars_ws_bytes(H, W) = 24 (H + W) bytes, < 0: bad size): uint32 keys
+ * rowmin[3][H], colmin[3][W], rowmax[3][H], colmax[3][W] in that order.  dcvc_bars_reset fills the mins with 0xFF bytes and
+ * the maxes with 0x00 bytes; dcvc_bars_scan folds the valid H x W region of one frame into it with integer atomicMin /
+ * atomicMax (order independent: the result is exact), any number of frames, no read-back.  Each sample is read once, 16
+ * bytes per access where the tensor's address and row length allow it; nothing outside H x W is read.
+ *
+ * dcvc_bars_extent: one workgroup on the stream writes 8 int32 words into out8 (dcvc_host_alloc memory, valid for the host
+ * once the stream has passed that point; the call does not wait): {found, top, bottom, left, right, c0, c1, c2}, c as fp32
+ * bits.  With min / max decoded from the keys and every operation in fp32: a line (row or column) is FLAT iff on all three
+ * planes max - min <= tol.  The candidates are row 0, row H - 1, column 0, column W - 1 in that order; the first flat one
+ * sets c_p = its min_p and found = 1; none flat: found = 0 and every other word 0.  A line is a BAR iff on all planes
+ * max_p <= c_p + tol and min_p >= c_p - tol.  top / bottom / left / right: the numbers of leading / trailing bar rows /
+ * columns, 0 .. H or 0 .. W (an all-bar picture: top = bottom = H).
+ *
+ * dcvc_frame_window: the valid HO x WO region of out is x[top : top + HO, left : left + WO], the rest of out its replicate
+ * pad.  dcvc_frame_paste: every element of out is written once - x where the H x W window lies at (top, left) of the
+ * HO x WO picture, (T)colour[p] elsewhere inside HO x WO, the replicate pad of that beyond.  Stores are 16 bytes per
+ * access, loads the widest (16 bytes .. one element) that the source's address, its row length and `left` allow.
+ * Argument errors (checked before any device work, nothing is launched): dtype; a size that is not positive or a tensor
+ * that does not hold its picture; a NULL or misaligned pointer; H or W above 2^20 (envelope entries); tol < 0 or NaN;
+ * the window not inside the picture; out not 16-byte aligned or WOp no multiple of 8; paste: x and out overlap. */
+int64_t dcvc_bars_ws_bytes(int H, int W);
+int dcvc_bars_reset(void* workspace, int H, int W, void* stream);
+int dcvc_bars_scan(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, void* workspace, void* stream);
+int dcvc_bars_extent(const void* workspace, int H, int W, float tol, int32_t* out8, void* stream);
+int dcvc_frame_window(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, int top, int left, void* out_nchw, int HOp,
+                      int WOp, int HO, int WO, void* stream);
+int dcvc_frame_paste(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, void* out_nchw, int HOp, int WOp, int HO,
+                     int WO, int top, int left, const float* colour, void* stream);
+/* ------------------------------------------------------------------------------------------
  * Film-grain synthesis and estimation on model frames (csrc/dcvc_grain.hip; docs/film_grain.md is the normative text; no
  * reference counterpart).  The parameters of a grain unit, passed by value: strengths are standard deviations in units of
  * 2^-11 of full scale, scale_y[k] the luma strength at intensity band k (centred at (k + 0.5) / 8). */

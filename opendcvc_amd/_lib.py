@@ -157,6 +157,12 @@ _SIGS = {
     "dcvc_frame_to_planes": (_I, [_I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _L, _P]),
     "dcvc_frame_to_metric_planes": (_I, [_I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dcvc_resize_frame": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
+    "dcvc_bars_ws_bytes": (_L, [_I, _I]),
+    "dcvc_bars_reset": (_I, [_P, _I, _I, _P]),
+    "dcvc_bars_scan": (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
+    "dcvc_bars_extent": (_I, [_P, _I, _I, _F, _P, _P]),
+    "dcvc_frame_window": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
+    "dcvc_frame_paste": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, POINTER(c_float), _P]),
     "dcvc_grain_apply": (_I, [_I, _P, _I, _I, _I, _I, _P, GrainParamsC, c_uint32, _P]),
     "dcvc_grain_stats": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "dcvc_tf_pyramid_bytes": (_L, [_I, _I]),

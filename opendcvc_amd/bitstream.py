@@ -21,6 +21,11 @@ Layout:  NAL header byte = type(4 bits) | sps_id(4 bits)
          the next grain unit; all strengths 0 switches it off.  Written in front of an I frame, in front of its digest unit
          if it has one.  This project's extension (docs/film_grain.md): the reference's reader rejects type 7, streams
          written without it are unchanged.
+  ACTIVE: header (type 8), full height, full width, top, left (varints), the bars' colour (3 x 4 bytes: Y, U, V as
+         little-endian fp32): the pictures of this SPS - at their display size if the SPS has a display unit, else at the
+         SPS's size - are the window at (top, left) of a full height x full width picture that is `colour` everywhere else.
+         Written behind an SPS, after its display unit.  This project's extension (docs/active_area.md): the reference's
+         reader rejects type 8, streams written without it are unchanged.
 varint:  0xxxxxxx                      value < 2**7
          10xxxxxx xxxxxxxx             value < 2**14   (big endian)
          11xxxxxx + 3 bytes            value < 2**30   (big endian)
@@ -45,6 +50,9 @@ class NalType(enum.IntEnum):
     # this project's extension (docs/film_grain.md), not readable by the reference: the film grain to synthesise on the
     # displayed pictures from the next frame on
     NAL_GRAIN = 7
+    # this project's extension (docs/active_area.md), not readable by the reference: the full picture the pictures of an SPS
+    # are a window of, and the colour of the rest
+    NAL_ACTIVE = 8
 
 
 DISPLAY_FILTERS = ("bilinear", "bicubic", "lanczos3")       # filter id = position (resize.FILTERS)
@@ -209,6 +217,39 @@ def read_display_remaining(f):
     return height, width, DISPLAY_FILTERS[fid]
 
 
+def write_active(f, sps_id, area):
+    """area: a bars.ActiveArea (only the full size, the offsets and the colour are written: the window's size is the
+    display unit's, else the SPS's)"""
+    import struct
+    if not 0 <= sps_id < 16:
+        raise ValueError(f"bad sps_id {sps_id}")
+    f.write(bytes(((int(NalType.NAL_ACTIVE) << 4) | sps_id,)))
+    n = 1 + sum(write_uint_adaptive(f, v) for v in (area.full_height, area.full_width, area.top, area.left))
+    f.write(struct.pack("<3f", *area.colour))
+    return n + 12
+
+
+def read_active_remaining(f):
+    """-> (full_height, full_width, top, left, colour); ValueError for a unit cut short"""
+    import struct
+    try:
+        full_h, full_w, top, left = (read_uint_adaptive(f) for _ in range(4))
+    except EOFError:
+        raise ValueError("truncated DCVC-RT active-area unit") from None
+    data = f.read(12)
+    if len(data) != 12:
+        raise ValueError("truncated DCVC-RT active-area unit")
+    return full_h, full_w, top, left, struct.unpack("<3f", data)
+
+
+def _active_area(unit, size):
+    """the bars.ActiveArea of a unit's fields around a window of size = (height, width); ValueError where the window leaves
+    the full picture or starts at an odd offset"""
+    from .bars import ActiveArea
+    full_h, full_w, top, left, colour = unit
+    return ActiveArea(full_h, full_w, top, left, size[0], size[1], tuple(colour))
+
+
 def frame_overhead_bytes(payload_len):
     """bytes write_ip puts in front of a payload of that length: NAL header, qp, the varint of the length (an SPS, written
     when a frame's parameters are new to the stream - twice in a typical one - is not counted)"""
@@ -228,9 +269,12 @@ class StreamWriter:
     """What test_video.py:166,216-224 does per frame: SPS dedup + NAL writing; returns bytes written.  display =
     (height, width, filter_name): the size the decoded pictures are to be resampled to; where it differs from a frame's
     size a display unit follows every SPS the writer emits (None, or equal sizes: the stream of the reference).  A packet
-    whose `grain` is a grain.GrainParams gets a grain unit in front of its digest unit / its frame."""
+    whose `grain` is a grain.GrainParams gets a grain unit in front of its digest unit / its frame.  active = a
+    bars.ActiveArea: the frames are the window of a larger picture (docs/active_area.md); an active-area unit follows every
+    SPS the writer emits, after the display unit; its window must be the display size where there is one, else the frame's
+    size (None: no unit, the stream of before)."""
 
-    def __init__(self, f, display=None):
+    def __init__(self, f, display=None, active=None):
         self.f = f
         self.sps_helper = SPSHelper()
         if display is not None:
@@ -238,6 +282,7 @@ class StreamWriter:
             if display[2] not in DISPLAY_FILTERS:
                 raise ValueError(f"display filter {display[2]!r}: one of {', '.join(DISPLAY_FILTERS)}")
         self.display = display
+        self.active = active
 
     def write_frame(self, height, width, use_two_entropy_coders, pkt):
         sps = {"sps_id": -1, "height": height, "width": width, "ec_part": 1 if use_two_entropy_coders else 0,
@@ -250,6 +295,13 @@ class StreamWriter:
         n = write_sps(self.f, sps) if is_new else 0
         if is_new and scaled:
             n += write_display(self.f, sps_id, *self.display)
+        if self.active is not None:
+            shown = self.display[:2] if scaled else (height, width)
+            if self.active.size != shown:
+                raise ValueError(f"the active area's window {self.active.width}x{self.active.height} is not the pictures' "
+                                 f"{shown[1]}x{shown[0]}")
+            if is_new:
+                n += write_active(self.f, sps_id, self.active)
         if getattr(pkt, "grain", None) is not None:
             n += write_grain(self.f, sps_id, pkt.grain)
         if getattr(pkt, "digest", None) is not None:
@@ -263,7 +315,8 @@ class StreamReader:
     the frame came without one), `display` the (height, width, filter_name) of the display unit that belongs to that
     frame's SPS (None until a display unit was read), `grain` the grain.GrainParams in force for that frame (None: no grain
     unit so far, or the last one switched grain off) and `grain_t` the frame's counter since that unit (0 for the frame the
-    unit stands in front of).  read_packet() is read_frame() with the frame as a pipeline.FramePacket."""
+    unit stands in front of), `active` the bars.ActiveArea of the active-area unit that belongs to that frame's SPS (None until
+    such a unit was read; it follows the SPS exactly as `display` does).  read_packet() is read_frame() with the frame as a pipeline.FramePacket."""
 
     def __init__(self, f):
         self.f = f
@@ -275,28 +328,43 @@ class StreamReader:
         self._display_seen = False
         self.grain = None
         self.grain_t = 0
+        self.active = None
+        self._actives = {}           # sps_id -> the active area behind that SPS
+        self._active_seen = False
 
     def read_frame(self):
         header = read_header(self.f)
         digest = None
         grain = None
-        while header["nal_type"] in (NalType.NAL_SPS, NalType.NAL_DIGEST, NalType.NAL_DISPLAY, NalType.NAL_GRAIN):
+        while header["nal_type"] in (NalType.NAL_SPS, NalType.NAL_DIGEST, NalType.NAL_DISPLAY, NalType.NAL_GRAIN,
+                                     NalType.NAL_ACTIVE):
             if digest is not None:
                 raise ValueError(f"a digest unit is followed by {header['nal_type'].name}, not by the frame it describes")
             if header["nal_type"] == NalType.NAL_SPS:
                 self.sps_helper.add_sps_by_id(read_sps_remaining(self.f, header["sps_id"]))
                 self._displays.pop(header["sps_id"], None)          # (a new SPS under this id: its display unit follows, if any)
+                self._actives.pop(header["sps_id"], None)
             elif header["nal_type"] == NalType.NAL_DISPLAY:
                 display = read_display_remaining(self.f)
                 sps = self.sps_helper.get_sps_by_id(header["sps_id"])
                 if sps is None:
                     raise ValueError(f"display unit refers to unknown SPS {header['sps_id']}")
+                if header["sps_id"] in self._actives:                # (the active-area unit took its window's size from what stood before it)
+                    raise ValueError(f"a display unit follows the active-area unit of SPS {header['sps_id']}: it belongs in front of it")
                 if display[0] < sps["height"] or display[1] < sps["width"]:
                     raise ValueError(f"display {display[1]}x{display[0]} below the coded size {sps['width']}x{sps['height']}")
                 self._displays[header["sps_id"]] = display
                 self._display_seen = True
             elif header["nal_type"] == NalType.NAL_GRAIN:
                 grain = read_grain_remaining(self.f)
+            elif header["nal_type"] == NalType.NAL_ACTIVE:
+                unit = read_active_remaining(self.f)
+                sps = self.sps_helper.get_sps_by_id(header["sps_id"])
+                if sps is None:
+                    raise ValueError(f"active-area unit refers to unknown SPS {header['sps_id']}")
+                shown = self._displays.get(header["sps_id"], (sps["height"], sps["width"]))[:2]
+                self._actives[header["sps_id"]] = _active_area(unit, shown)
+                self._active_seen = True
             else:
                 digest = read_digest_remaining(self.f)
             header = read_header(self.f)
@@ -311,6 +379,8 @@ class StreamReader:
             self.grain_t += 1
         if self._display_seen:
             self.display = self._displays.get(header["sps_id"])
+        if self._active_seen:
+            self.active = self._actives.get(header["sps_id"])
         self.chunked = header["nal_type"] in (NalType.NAL_I_CHUNKED, NalType.NAL_P_CHUNKED)
         return sps, header["nal_type"] in (NalType.NAL_I, NalType.NAL_I_CHUNKED), qp, payload
 

@@ -409,8 +409,56 @@ def make_source(src_type, path, width, height):
 
 
 # ---------------------------------------------------------------------------------- one rate point
+def parse_crop(text):
+    """--crop: 'auto', or T:B:L:R[:Y:U:V] - the rows / columns to leave out at the top, bottom, left and right and the bars'
+    colour in 8-bit codes (default 16:128:128) -> 'auto' or (top, bottom, left, right, (y, u, v))"""
+    if text == "auto":
+        return text
+    parts = str(text).split(":")
+    if len(parts) not in (4, 7) or not all(p.isdigit() for p in parts):
+        raise ValueError(f"crop {text!r}: auto or TOP:BOTTOM:LEFT:RIGHT[:Y:U:V], e.g. 138:138:0:0")
+    vals = [int(p) for p in parts]
+    colour = tuple(vals[4:]) if len(vals) == 7 else (16, 128, 128)
+    if any(v % 2 for v in vals[:4]) or any(c > 255 for c in colour):
+        raise ValueError(f"crop {text!r}: even extents (4:2:0 chroma) and a colour in 8-bit codes")
+    return (*vals[:4], colour)
+
+
+def check_crop(crop, crop_tol, height, width):
+    """run_one_point's crop / crop_tol -> (None | 'auto' | the bars.ActiveArea of a manual crop, tol as the kernels take it:
+    crop_tol 8-bit codes as an fp32 fraction of 255)"""
+    tol = float(np.float32(crop_tol) / np.float32(255.0))
+    if not tol >= 0.0:
+        raise ValueError(f"crop_tol {crop_tol!r}: 8-bit codes, >= 0")
+    if tol and crop != "auto":
+        raise ValueError(f"crop_tol {crop_tol!r} is the tolerance of crop='auto': it has no effect on crop {crop!r}")
+    if crop is None or crop == "auto":
+        return crop, tol
+    from .bars import ActiveArea
+    if isinstance(crop, str):
+        crop = parse_crop(crop)
+    if len(crop) != 5 or len(crop[4]) != 3:
+        raise ValueError(f"crop {crop!r}: None, 'auto' or (top, bottom, left, right, (y, u, v))")
+    colour = [float(np.float32(c) / np.float32(255.0)) for c in crop[4]]
+    return ActiveArea.from_manual(height, width, crop[:4], colour), tol
+
+
+def _detect_area(src, frame_num, dev, dtype, tol):
+    """--crop auto: every frame of the run through the loader into one bars.BarDetector envelope, then ONE read-back ->
+    the bars.ActiveArea to code, or None.  With the envelope over all frames and tol 0 no content can lie outside it."""
+    from .bars import ActiveArea, BarDetector
+    size = (src.h, src.w)
+    det = BarDetector(dev)
+    det.reset(size)
+    reader = src.reader()
+    for _ in range(frame_num):
+        det.scan(src.to_input(_to_device(reader.read(), dev), dtype), size)
+    reader.close()
+    return ActiveArea.from_extents(*size, det.extents(tol))
+
+
 def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, tf_level=0, tf_radius=2, tf_subpel=0,
-                 lookahead=0):
+                 lookahead=0, area=None):
     """every frame of `src` through a SequenceEncoder(**enc_kw) into the container; coded: None or the (height, width) the
     frames are resampled down to first; grain: None, a GrainParams, or "auto" (estimated at every I frame from the full-size
     input against the reconstruction at that size, the unit's seed the frame's index); tf_level 1 .. 5 or "auto": the frames pass
@@ -420,13 +468,14 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
     write_frame; the file read and the copy to the device stay outside.  lookahead N > 0: the frames the encoder is to see
     (filtered, resampled) pass a lookahead.Lookahead of depth N, which holds N of them back and hands each to the encoder with
     its cut decision; its delay adds to the temporal filter's, and a frame's clock and its unfiltered input follow it through
-    both queues.
+    both queues.  area (a bars.ActiveArea, docs/active_area.md): every frame is cut down to the area's window right behind the
+    loader, everything above then works at the window's size, and the stream says what the window is a window of.
     -> (encoder, stream bytes, frame types, bits, times, the Resampler, the FilmGrain and the TemporalFilter made here or None;
     with lookahead the Lookahead as a ninth)"""
     import torch
     from .grain import FilmGrain
     from .resize import Resampler
-    size = (src.h, src.w)
+    size = area.size if area is not None else (src.h, src.w)
     ch, cw = coded or size
     dtype = next(nets[1].parameters()).dtype
     scaler = Resampler(dev) if coded else None
@@ -441,7 +490,9 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
         enc_kw = dict(enc_kw, grain=estimate if grain == "auto" else grain)
     enc = SequenceEncoder(*nets, **enc_kw)
     out = io.BytesIO()
-    writer = StreamWriter(out, display=size + (scale_filter,) if coded else None)
+    if area is not None:
+        from .bars import window
+    writer = StreamWriter(out, display=size + (scale_filter,) if coded else None, active=area)
     two = use_two_entropy_coders(ch, cw)
 
     la = None
@@ -483,6 +534,8 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
         torch.cuda.synchronize(dev)
         t0 = time.time()
         x = src.to_input(planes, dtype)
+        if area is not None:
+            x = window(x, (src.h, src.w), area)
         if tf is None:
             code(x, x, t0)
             continue
@@ -526,8 +579,15 @@ def _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, device_metrics, r
         torch.cuda.synchronize(dev)
         t0 = time.time()
         frame = decoder.next()
-        if frame.display is not None and frame.display[:2] != (src.h, src.w):       # the stream's word, not the arguments'
-            raise ValueError(f"the stream's display size {frame.display[1]}x{frame.display[0]} is not the source's {src.w}x{src.h}")
+        shown_size = (src.h, src.w)                                                  # the stream's word, not the arguments'
+        if frame.active is not None:
+            if frame.active.full_size != shown_size:
+                raise ValueError(f"the stream's full picture {frame.active.full_width}x{frame.active.full_height} is not the "
+                                 f"source's {src.w}x{src.h}")
+            shown_size = frame.active.size
+        if frame.display is not None and frame.display[:2] != shown_size:
+            raise ValueError(f"the stream's display size {frame.display[1]}x{frame.display[0]} is not the source's "
+                             f"{shown_size[1]}x{shown_size[0]}")
         torch.cuda.synchronize(dev)
         decoder.check_digests()
         times.append(time.time() - t0)
@@ -554,7 +614,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
                   src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
                   target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3", film_grain=None,
-                  temporal_filter=0, tf_radius=2, tf_subpel=0, lookahead=0):
+                  temporal_filter=0, tf_radius=2, tf_subpel=0, lookahead=0, crop=None, crop_tol=0.0):
     """Encodes `frame_num` frames of a source (src_type: SRC_TYPES - a planar 8-bit YUV 4:2:0 file, a directory of PNGs, a raw
     file in a pipeline.PIXEL_FORMATS format) into the reference's container (optionally written to bin_path), decodes the
     container again and returns the reference-schema log (summarize) plus one group of keys per extension switched on.
@@ -571,7 +631,9 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
       temporal_filter, tf_radius   docs/temporal_filter.md (level 0 = off .. 5; 1, 2)  log: tf_level, tf_radius, tf_mean_weight
                                    level "auto": chosen per frame from a noise estimate   log: + tf_levels, tf_noise
       tf_subpel                    its vectors in whole (0), half (1) or quarter pels (2)     log: + tf_subpel where not 0
-      lookahead                    docs/lookahead.md (0 = off .. 16 frames; needs scenecut)   log: lookahead, flashes, fades"""
+      lookahead                    docs/lookahead.md (0 = off .. 16 frames; needs scenecut)   log: lookahead, flashes, fades
+      crop, crop_tol               docs/active_area.md (None, "auto", (top, bottom, left, right, (y, u, v)) or its --crop spelling;
+                                   the colour and crop_tol in 8-bit codes)             log: active_area, bar_colour"""
     from .grain import GrainParams
     from .lookahead import check_depth
     from .prefilter import check_options, check_subpel
@@ -580,7 +642,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                                  ("src_type", src_type, SRC_TYPES), ("scale_filter", scale_filter, FILTERS)):
         if value not in choices:
             raise ValueError(f"{name} {value!r}: one of {', '.join(choices)}")
-    coded_size = check_coded_size(coded_size, height, width)
+    area, tol = check_crop(crop, crop_tol, height, width)
+    coded_size = check_coded_size(coded_size, *(area.size if area not in (None, "auto") else (height, width)))
     if not (film_grain is None or film_grain == "auto" or isinstance(film_grain, GrainParams)):
         raise ValueError(f"film_grain {film_grain!r}: None, 'auto' or a GrainParams")
     temporal_filter, tf_radius = check_options(temporal_filter, tf_radius)
@@ -590,10 +653,14 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     src = make_source(src_type, src_path, width, height)
     import torch
     dev, nets = torch.device(device), (i_net, p_net)
-    for m in nets:
-        m.set_use_two_entropy_coders(use_two_entropy_coders(*(coded_size or (height, width))))     # what the SPS and the models see
-        m.entropy = entropy
     t_start = time.time()
+    if area == "auto":               # a pass of its own over every frame of the run, outside the per-frame clocks
+        area = _detect_area(src, frame_num, dev, next(p_net.parameters()).dtype, tol)
+        if area is not None:
+            coded_size = check_coded_size(coded_size, *area.size)
+    for m in nets:
+        m.set_use_two_entropy_coders(use_two_entropy_coders(*(coded_size or (area.size if area else (height, width)))))     # what the SPS and the models see
+        m.entropy = entropy
     enc_kw = dict(qp_i=qp_i, qp_p=qp_p, intra_period=intra_period, reset_interval=reset_interval)
     if scenecut:
         enc_kw.update(scenecut=scenecut, min_keyint=min_keyint)
@@ -605,6 +672,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     if digest:
         enc_kw["digest"] = True
     extra = dict({"tf_subpel": tf_subpel} if tf_subpel else {}, **({"lookahead": lookahead} if lookahead else {}))
+    if area is not None:
+        extra["area"] = area
     enc, stream, frame_types, bits, enc_time, scaler, grainer, tf, *la = _encode_pass(nets, src, frame_num, dev, coded_size,
                                                                                       scale_filter, film_grain, enc_kw,
                                                                                       temporal_filter, tf_radius, **extra)
@@ -634,12 +703,15 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                    grain_corr=last.corr if last else 0)
     if tf is not None:
         log.update(tf_level=temporal_filter, tf_radius=tf_radius,
-                   tf_mean_weight=tf.weight_sum() / (256.0 * height * width * frame_num))
+                   tf_mean_weight=tf.weight_sum() / (256.0 * (area.height * area.width if area else height * width) * frame_num))
         if temporal_filter == "auto":                     # frames per level 0 .. 5; the mean N as white noise's sigma in 8-bit codes
             totals = tf.levels()
             log.update(tf_levels=totals[:6], tf_noise=totals[6] / max(totals[7], 1) * (255.0 / (68.0 * 1023.0)))
         if tf_subpel:
             log["tf_subpel"] = tf_subpel
+    if crop is not None:
+        log["active_area"] = area.extents if area is not None else [0, 0, 0, 0]
+        log["bar_colour"] = list(area.colour) if area is not None else None
     return log
 
 
@@ -647,7 +719,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
 # manifest_options all go through point_kwargs, so a new option is one row here, one build_parser line under the same name and
 # its hook in run_one_point.  target_bpp is not one of them: it is worked out per sequence (target_bpp()).  Nor
 # are temporal_filter / tf_radius / tf_subpel: they act in front of the encoder, not on a rate point, and the table's names are pinned
-# (tests/test_harness_options.py), so they travel target_bpp's way - prefilter_kwargs(), passed beside point_kwargs().  lookahead goes the same way: lookahead_kwargs().
+# (tests/test_harness_options.py), so they travel target_bpp's way - prefilter_kwargs(), passed beside point_kwargs().  lookahead goes the same way: lookahead_kwargs().  So does crop / crop_tol: crop_kwargs(), which hands on nothing at all where the option is not set.
 POINT_OPTIONS = (("verbose", 0, None), ("verbose_json", False, bool), ("calc_ssim", False, bool), ("metrics", "host", None),
                  ("entropy", "host", None), ("scenecut", 0, None), ("min_keyint", 4, None), ("digest", False, bool),
                  ("coded_size", None, None), ("scale_filter", "lanczos3", None), ("film_grain", None, None))
@@ -673,6 +745,15 @@ def lookahead_kwargs(opts):
     """an options mapping -> run_one_point's keyword of the frame lookahead; missing or None: 0, off.  Like the pre-filter's it
     acts in front of the encoder and travels beside point_kwargs()"""
     return {"lookahead": opts.get("lookahead") or 0}
+
+
+def crop_kwargs(opts):
+    """an options mapping -> run_one_point's keywords of active-area coding: none at all where crop is missing or None (the
+    keywords of before the option), crop_tol only where it is set and not 0.  Like the pre-filter's it acts in front of the
+    encoder and travels beside point_kwargs()"""
+    if not opts.get("crop"):
+        return {}
+    return dict({"crop": opts["crop"]}, **({"crop_tol": opts["crop_tol"]} if opts.get("crop_tol") else {}))
 
 
 def run_sweep(make_nets, src_path, width, height, frame_num, rate_num=4, qp_i=None, qp_p=None, bin_prefix=None, **kw):
@@ -875,7 +956,7 @@ def run_job(nets, job, opts):
                         job["qp_i"], job["qp_p"], intra_period=job["intra_period"], reset_interval=job["reset_interval"],
                         bin_path=bin_path, rec_path=rec_path, device="cuda:0", src_type=job.get("src_type", "yuv420"),
                         target_bpp=target_bpp(opts, job["src_width"], job["src_height"]), **prefilter_kwargs(opts),
-                        **lookahead_kwargs(opts), **point_kwargs(opts))
+                        **lookahead_kwargs(opts), **crop_kwargs(opts), **point_kwargs(opts))
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -935,6 +1016,13 @@ def check_lookahead_options(args, ap):
         ap.error("--lookahead decides the scene cuts of --scenecut: give --scenecut too (150 is recommended)")
 
 
+def check_crop_options(args, ap):
+    if args.crop_tol is not None and args.crop != "auto":
+        ap.error("--crop-tol is the tolerance of --crop auto's bar detection: it has no effect without it")
+    if args.crop_tol is not None and not args.crop_tol >= 0:
+        ap.error("--crop-tol is in 8-bit codes, >= 0")
+
+
 def _str2bool(v):
     """the reference's str2bool (test_video.py:24-28): --flag 1 / true / yes / y / t"""
     if isinstance(v, bool):
@@ -948,7 +1036,7 @@ def _str2bool(v):
 
 def _add_extension_options(ap, flag):
     """this project's options beyond the reference's: adaptive I frames, rate control, digests, reduced resolution, film grain,
-    the temporal pre-filter, the frame lookahead"""
+    the temporal pre-filter, the frame lookahead, active-area coding"""
     from .resize import FILTERS, parse_size
     ap.add_argument("--scenecut", type=int, default=0, metavar="PCT",
                     help="adaptive I frames: a frame whose low-resolution difference to its predecessor is at least PCT percent "
@@ -987,6 +1075,15 @@ def _add_extension_options(ap, flag):
                          "synthesises anyway.  Metrics stay those against the unfiltered source")
     ap.add_argument("--tf-radius", "--tf_radius", type=int, default=2, choices=(1, 2), metavar="R",
                     help="with --temporal-filter: references up to R frames before and after a frame (the encoder reads R frames ahead)")
+    ap.add_argument("--crop", type=parse_crop, default=None, metavar="auto|T:B:L:R[:Y:U:V]",
+                    help="active-area coding: code only the picture between the black bars of letterboxed / pillarboxed "
+                         "material and paste it back behind the decoder.  auto: the bars are found on the device in a pass over "
+                         "every frame of the run; T:B:L:R: the rows / columns to leave out (even numbers), Y:U:V the bars' "
+                         "colour in 8-bit codes (16:128:128).  Metrics, bpp and --target-bpp stay those of the source "
+                         "(docs/active_area.md) - this project's extension, not readable by the reference")
+    ap.add_argument("--crop-tol", "--crop_tol", type=float, default=None, metavar="X",
+                    help="with --crop auto: a line is a bar while it stays within X 8-bit codes of the bars' colour (default 0: "
+                         "exactly flat bars, nothing can be lost; above 0 for noisy bars)")
     ap.add_argument("--tf-subpel", "--tf_subpel", type=int, default=0, choices=(0, 1, 2), metavar="S",
                     help="with --temporal-filter: refine the filter's motion vectors to half (1) or quarter pels (2) and gather "
                          "interpolated reference samples (0 = whole-pel vectors; 2 is recommended for camera material)")
@@ -1078,7 +1175,7 @@ def manifest_options(args, ap):
                                           "reset_interval", "model_i", "model_p", "force_zero_thres", "fp32", "target_bpp",
                                           "target_kbps", "fps", "force_intra", "check_existing", "save_decoded_frame",
                                           "temporal_filter", "tf_radius", "tf_subpel", "lookahead")}
-    opts.update(gpu_ids=gpu_ids, stream_path=stream_path, **point_kwargs(vars(args)))
+    opts.update(gpu_ids=gpu_ids, stream_path=stream_path, **crop_kwargs(vars(args)), **point_kwargs(vars(args)))
     return opts, gpus
 
 
@@ -1087,6 +1184,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     check_rate_options(args, ap)
     check_lookahead_options(args, ap)
+    check_crop_options(args, ap)
     if args.test_config:
         with open(args.test_config) as f:
             config = json.load(f)
@@ -1111,7 +1209,8 @@ def main(argv=None):
                     args.src, args.width, args.height, args.frames, args.rate_num, args.qp_i or None, args.qp_p or None,
                     bin_prefix=args.bin_prefix, intra_period=args.intra_period, reset_interval=args.reset_interval,
                     src_type=args.src_type, target_bpp=target_bpp(vars(args), args.width, args.height),
-                    **prefilter_kwargs(vars(args)), **lookahead_kwargs(vars(args)), **point_kwargs(vars(args)))
+                    **prefilter_kwargs(vars(args)), **lookahead_kwargs(vars(args)), **crop_kwargs(vars(args)),
+                    **point_kwargs(vars(args)))
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:

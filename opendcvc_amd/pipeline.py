@@ -325,13 +325,15 @@ class DecodedFrame:
     display: Optional[tuple]         # StreamReader.display / grain / grain_t behind this frame
     grain: Optional[object]
     grain_t: int
+    active: Optional[object] = None  # StreamReader.active behind this frame: x_hat and shown are then the full picture
 
 
 class StreamDecoder:
     """Container in, pictures out: the decode-side entry point.  Owns the StreamReader of the binary file-like `f`, the
     SequenceDecoder (sequential: defer_output=False; made at the first frame, from then on it follows every frame's SPS) and
     what the stream's extension units ask for behind it - the display unit's resample (docs/reduced_resolution.md) and the
-    grain unit's synthesis (docs/film_grain.md).  scaler / grainer: a resize.Resampler / grain.FilmGrain to use; otherwise
+    grain unit's synthesis (docs/film_grain.md), then the active-area unit's paste into the full picture
+    (docs/active_area.md; one paste without grain, shown is x_hat then as ever).  scaler / grainer: a resize.Resampler / grain.FilmGrain to use; otherwise
     each is made when the stream first needs one, so a stream without these units launches the decoder's own kernels only."""
 
     def __init__(self, f, i_net, p_net, device, scaler=None, grainer=None):
@@ -361,6 +363,11 @@ class StreamDecoder:
                 from .grain import FilmGrain
                 self.grainer = FilmGrain(self.device)
             shown = self.grainer.apply(x_hat, size, rd.grain, rd.grain_t)
+        if rd.active is not None:                    # the grain went onto the window's picture: the bars stay clean
+            from .bars import paste
+            full = paste(x_hat, rd.active)
+            x_hat, shown = full, (full if shown is x_hat else paste(shown, rd.active))
+            return DecodedFrame(x_hat, shown, sps, pkt.is_i, rd.display, rd.grain, rd.grain_t, rd.active)
         return DecodedFrame(x_hat, shown, sps, pkt.is_i, rd.display, rd.grain, rd.grain_t)
 
     def check_digests(self):
