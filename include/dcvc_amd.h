@@ -518,6 +518,27 @@ int dcvc_frame_window(int dtype, const void* x_nchw, int Hp, int Wp, int H, int 
 int dcvc_frame_paste(int dtype, const void* x_nchw, int Hp, int Wp, int H, int W, void* out_nchw, int HOp, int WOp, int HO,
                      int WO, int top, int left, const float* colour, void* stream);
 /* ------------------------------------------------------------------------------------------
+ * Repeated-frame coding (csrc/dcvc_repeat.hip; docs/frame_repeat.md is the normative text; no reference counterpart): is a
+ * frame the same picture as another one, within a tolerance?  a and b are model frames [3][Hp][Wp] of one dtype (DCVC_F16 /
+ * DCVC_F32) and one shape, the picture H x W at the top left.  For every sample of the valid H x W region of plane p:
+ *   d = fabsf((float)a - (float)b)   one fp32 subtraction, no fused multiply-add
+ *   key = the bits of d as uint32
+ * out4[p] = the maximum key over plane p, out4[3] = 0.  The keys of non-negative floats are monotonic, so the integer max is
+ * order independent and exact; +0 against -0 gives key 0; a NaN on either side, or inf - inf, gives a key above 0x7f800000,
+ * which no tolerance passes (the rule of the active-area entries).  Nothing outside H x W is read.  Each sample of both
+ * frames is read once, 16 bytes per access where BOTH addresses and the row length allow it, else element by element (chosen
+ * on the host); wave shuffles, LDS, then one integer atomicMax per plane and workgroup (at most 96 workgroups per plane,
+ * each striding over the plane's 256 x 32 tiles).
+ * workspace: device memory, 4-byte aligned, dcvc_frame_maxdiff_ws_bytes() = 32 bytes, ZERO before its first use; the kernel
+ * leaves it zero again (the workgroup that finishes last in a plane moves the plane's maximum to out4), so consecutive
+ * compares on one stream need no memset.  One compare at a time per workspace.  out4: dcvc_host_alloc memory, 4-byte aligned, valid for the host
+ * once the stream has passed that point; the call does not wait.  a == b is allowed (all zero unless a NaN is present).
+ * Argument errors (checked before any device work, nothing is launched): dtype; a size that is not positive or a frame that
+ * does not hold its picture; a NULL or misaligned pointer. */
+int64_t dcvc_frame_maxdiff_ws_bytes(void);
+int dcvc_frame_maxdiff(int dtype, const void* a_nchw, const void* b_nchw, int Hp, int Wp, int H, int W, void* workspace,
+                       uint32_t* out4, void* stream);
+/* ------------------------------------------------------------------------------------------
  * Film-grain synthesis and estimation on model frames (csrc/dcvc_grain.hip; docs/film_grain.md is the normative text; no
  * reference counterpart).  The parameters of a grain unit, passed by value: strengths are standard deviations in units of
  * 2^-11 of full scale, scale_y[k] the luma strength at intensity band k (centred at (k + 0.5) / 8). */

@@ -26,6 +26,10 @@ Layout:  NAL header byte = type(4 bits) | sps_id(4 bits)
          SPS's size - are the window at (top, left) of a full height x full width picture that is `colour` everywhere else.
          Written behind an SPS, after its display unit.  This project's extension (docs/active_area.md): the reference's
          reader rejects type 8, streams written without it are unchanged.
+  REPEAT: header (type 9) and nothing else: show the picture of the frame before once more.  sps_id is that frame's.  It
+         counts as a frame (a grain unit's counter goes on), changes no decoder state, and no SPS, digest or grain unit
+         is written for it.  This project's extension (docs/frame_repeat.md): the reference's reader rejects type 9,
+         streams written without it are unchanged.
 varint:  0xxxxxxx                      value < 2**7
          10xxxxxx xxxxxxxx             value < 2**14   (big endian)
          11xxxxxx + 3 bytes            value < 2**30   (big endian)
@@ -53,6 +57,8 @@ class NalType(enum.IntEnum):
     # this project's extension (docs/active_area.md), not readable by the reference: the full picture the pictures of an SPS
     # are a window of, and the colour of the rest
     NAL_ACTIVE = 8
+    # this project's extension (docs/frame_repeat.md), not readable by the reference: the picture of the frame before, again
+    NAL_REPEAT = 9
 
 
 DISPLAY_FILTERS = ("bilinear", "bicubic", "lanczos3")       # filter id = position (resize.FILTERS)
@@ -250,6 +256,17 @@ def _active_area(unit, size):
     return ActiveArea(full_h, full_w, top, left, size[0], size[1], tuple(colour))
 
 
+REPEAT_UNIT_BYTES = 1        # the header
+
+
+def write_repeat(f, sps_id):
+    """sps_id: that of the frame whose picture is repeated"""
+    if not 0 <= sps_id < 16:
+        raise ValueError(f"bad sps_id {sps_id}")
+    f.write(bytes(((int(NalType.NAL_REPEAT) << 4) | sps_id,)))
+    return REPEAT_UNIT_BYTES
+
+
 def frame_overhead_bytes(payload_len):
     """bytes write_ip puts in front of a payload of that length: NAL header, qp, the varint of the length (an SPS, written
     when a frame's parameters are new to the stream - twice in a typical one - is not counted)"""
@@ -272,7 +289,9 @@ class StreamWriter:
     whose `grain` is a grain.GrainParams gets a grain unit in front of its digest unit / its frame.  active = a
     bars.ActiveArea: the frames are the window of a larger picture (docs/active_area.md); an active-area unit follows every
     SPS the writer emits, after the display unit; its window must be the display size where there is one, else the frame's
-    size (None: no unit, the stream of before)."""
+    size (None: no unit, the stream of before).  A packet with repeat=True is written as the one-byte repeat unit
+    (docs/frame_repeat.md) under the SPS of the frame before it, which must be of the same size; nothing else is written
+    for it, and a repeat in front of any frame is a ValueError."""
 
     def __init__(self, f, display=None, active=None):
         self.f = f
@@ -283,8 +302,16 @@ class StreamWriter:
                 raise ValueError(f"display filter {display[2]!r}: one of {', '.join(DISPLAY_FILTERS)}")
         self.display = display
         self.active = active
+        self._last_sps = None        # the SPS of the frame written last
 
     def write_frame(self, height, width, use_two_entropy_coders, pkt):
+        if getattr(pkt, "repeat", False):
+            last = self._last_sps
+            if last is None:
+                raise ValueError("a repeat unit in front of any frame: there is no picture to repeat")
+            if (last["height"], last["width"]) != (height, width):
+                raise ValueError(f"a repeat of a {width}x{height} picture behind a frame of {last['width']}x{last['height']}")
+            return write_repeat(self.f, last["sps_id"])
         sps = {"sps_id": -1, "height": height, "width": width, "ec_part": 1 if use_two_entropy_coders else 0,
                "use_ada_i": pkt.use_ada_i}
         scaled = self.display is not None and self.display[:2] != (height, width)
@@ -292,6 +319,7 @@ class StreamWriter:
             raise ValueError(f"display {self.display[1]}x{self.display[0]} below the coded size {width}x{height}")
         sps_id, is_new = self.sps_helper.get_sps_id(sps)
         sps["sps_id"] = sps_id
+        self._last_sps = sps
         n = write_sps(self.f, sps) if is_new else 0
         if is_new and scaled:
             n += write_display(self.f, sps_id, *self.display)
@@ -316,7 +344,9 @@ class StreamReader:
     frame's SPS (None until a display unit was read), `grain` the grain.GrainParams in force for that frame (None: no grain
     unit so far, or the last one switched grain off) and `grain_t` the frame's counter since that unit (0 for the frame the
     unit stands in front of), `active` the bars.ActiveArea of the active-area unit that belongs to that frame's SPS (None until
-    such a unit was read; it follows the SPS exactly as `display` does).  read_packet() is read_frame() with the frame as a pipeline.FramePacket."""
+    such a unit was read; it follows the SPS exactly as `display` does), `repeat` whether the frame is a repeat unit
+    (docs/frame_repeat.md): read_frame() then returns (sps, False, 0, b"") with the SPS, `display` and `active` of the picture
+    it repeats, `digest` None and `grain_t` one further as for any frame.  read_packet() is read_frame() with the frame as a pipeline.FramePacket."""
 
     def __init__(self, f):
         self.f = f
@@ -331,6 +361,8 @@ class StreamReader:
         self.active = None
         self._actives = {}           # sps_id -> the active area behind that SPS
         self._active_seen = False
+        self.repeat = False
+        self._last_sps_id = None     # of the frame returned last
 
     def read_frame(self):
         header = read_header(self.f)
@@ -369,9 +401,24 @@ class StreamReader:
                 digest = read_digest_remaining(self.f)
             header = read_header(self.f)
         sps = self.sps_helper.get_sps_by_id(header["sps_id"])
-        if sps is None:
-            raise ValueError(f"frame refers to unknown SPS {header['sps_id']}")
-        qp, payload = read_ip_remaining(self.f)
+        repeat = header["nal_type"] == NalType.NAL_REPEAT
+        if repeat:
+            for unit, name in ((digest, "digest"), (grain, "grain")):
+                if unit is not None:
+                    raise ValueError(f"a {name} unit is followed by NAL_REPEAT, not by the frame it describes")
+            if sps is None:
+                raise ValueError(f"repeat unit refers to unknown SPS {header['sps_id']}")
+            if self._last_sps_id is None:
+                raise ValueError("a repeat unit stands before the first frame: there is no picture to repeat")
+            if header["sps_id"] != self._last_sps_id:
+                raise ValueError(f"repeat unit names SPS {header['sps_id']}, the frame before it has SPS {self._last_sps_id}")
+            qp, payload = 0, b""
+        else:
+            if sps is None:
+                raise ValueError(f"frame refers to unknown SPS {header['sps_id']}")
+            qp, payload = read_ip_remaining(self.f)
+        self.repeat = repeat
+        self._last_sps_id = header["sps_id"]
         self.digest = digest
         if grain is not None:
             self.grain, self.grain_t = (grain if grain.active else None), 0
@@ -386,7 +433,8 @@ class StreamReader:
 
     def read_packet(self):
         """read_frame() as what a decoder takes: -> (sps, pipeline.FramePacket), the packet with the frame's `chunked` and
-        `digest`; `display`, `grain` and `grain_t` are left as read_frame() leaves them"""
+        `digest` and `repeat`; `display`, `grain` and `grain_t` are left as read_frame() leaves them"""
         from .pipeline import FramePacket
         sps, is_i, qp, payload = self.read_frame()
-        return sps, FramePacket(is_i, qp, sps["use_ada_i"], payload, chunked=self.chunked, digest=self.digest)
+        return sps, FramePacket(is_i, qp, sps["use_ada_i"], payload, chunked=self.chunked, digest=self.digest,
+                                repeat=self.repeat)

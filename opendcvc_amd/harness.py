@@ -443,6 +443,14 @@ def check_crop(crop, crop_tol, height, width):
     return ActiveArea.from_manual(height, width, crop[:4], colour), tol
 
 
+def check_dup(frame_dup, dup_tol):
+    """run_one_point's frame_dup / dup_tol: ValueError for a dup_tol that is negative or NaN (8-bit codes, turned into the
+    kernel's unit as crop_tol is) or that is set without frame_dup"""
+    from .repeat import tol_fraction
+    if tol_fraction(dup_tol) and not frame_dup:
+        raise ValueError(f"dup_tol {dup_tol!r} is the tolerance of frame_dup: it has no effect without it")
+
+
 def _detect_area(src, frame_num, dev, dtype, tol):
     """--crop auto: every frame of the run through the loader into one bars.BarDetector envelope, then ONE read-back ->
     the bars.ActiveArea to code, or None.  With the envelope over all frames and tol 0 no content can lie outside it."""
@@ -458,7 +466,7 @@ def _detect_area(src, frame_num, dev, dtype, tol):
 
 
 def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, tf_level=0, tf_radius=2, tf_subpel=0,
-                 lookahead=0, area=None):
+                 lookahead=0, area=None, dup_tol=None):
     """every frame of `src` through a SequenceEncoder(**enc_kw) into the container; coded: None or the (height, width) the
     frames are resampled down to first; grain: None, a GrainParams, or "auto" (estimated at every I frame from the full-size
     input against the reconstruction at that size, the unit's seed the frame's index); tf_level 1 .. 5 or "auto": the frames pass
@@ -470,8 +478,15 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
     its cut decision; its delay adds to the temporal filter's, and a frame's clock and its unfiltered input follow it through
     both queues.  area (a bars.ActiveArea, docs/active_area.md): every frame is cut down to the area's window right behind the
     loader, everything above then works at the window's size, and the stream says what the window is a window of.
+    dup_tol (None: off, no detector is made; else 8-bit codes, docs/frame_repeat.md): right behind the loader and the window
+    a repeat.RepeatDetector holds every frame against the last frame that was no repeat.  A repeat goes no further - the
+    temporal filter, the down-resample, the lookahead and the encoder see the sequence without it - and is a trailer of the
+    frame it repeats: the record that travels with that frame through the queues counts it, emit writes that many repeat
+    units behind the frame's packet, and a repeat whose frame is already written is written at once.  Per repeat: 8 bits,
+    frame type 1 (a P frame), the time of loader + window + compare + unit write.  The loader and the window allocate their
+    output per frame, so the detector's reference is never overwritten and nothing is cloned.
     -> (encoder, stream bytes, frame types, bits, times, the Resampler, the FilmGrain and the TemporalFilter made here or None;
-    with lookahead the Lookahead as a ninth)"""
+    with lookahead the Lookahead as a ninth; with dup_tol the per-frame 0 / 1 list of the repeats as the last)"""
     import torch
     from .grain import FilmGrain
     from .resize import Resampler
@@ -499,30 +514,50 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
     if lookahead:
         from .lookahead import Lookahead
         la = Lookahead(dev, lookahead, enc.scenecut)
-        held = []                                        # (unfiltered input, seconds on the clock so far) of the frames held back
+        held = []                                        # (unfiltered input, seconds on the clock so far, record) of the frames held back
 
-    def code(x_source, x, t0):
-        """x (the frame as the encoder is to see it at source size) from the clock reading t0 on"""
+    det, repeated, last = None, [], None
+    if dup_tol is not None:
+        from .repeat import RepeatDetector
+        det = RepeatDetector(dev, dup_tol)               # last: the record of the last frame that was no repeat -
+                                                         # [written?, the seconds of each of its repeats not yet written]
+
+    def code(x_source, x, t0, rec=None):
+        """x (the frame as the encoder is to see it at source size) from the clock reading t0 on; rec: its record"""
         if scaler:
             x = scaler.resample(x, size, (ch, cw), scale_filter)
         if la is None:
-            return emit(x_source, x, t0)
+            return emit(x_source, x, t0, None, rec)
         if tf is not None and not scaler:
             x = x.clone()                                # (the filter's output buffers come round again before the frame is coded)
         done = la.push(x)
         torch.cuda.synchronize(dev)
-        held.append((x_source, time.time() - t0))
+        held.append((x_source, time.time() - t0, rec))
         for y, cut in done:
-            y_source, spent = held.pop(0)
-            emit(y_source, y, time.time() - spent, cut)
+            y_source, spent, r = held.pop(0)
+            emit(y_source, y, time.time() - spent, cut, r)
 
-    def emit(x_source, x, t0, cut=None):
+    def emit(x_source, x, t0, cut=None, rec=None):
         source[:] = [x_source]                           # "auto": the full-size unfiltered input of the frame being coded
         pkt = enc.encode(x) if cut is None else enc.encode(x, cut=cut)
         bits.append(8 * writer.write_frame(ch, cw, two, pkt))
         torch.cuda.synchronize(dev)
         times.append(time.time() - t0)
         frame_types.append(0 if pkt.is_i else 1)
+        if rec is not None:                              # the frame's trailer: the repeats found while it was queued
+            repeated.append(0)
+            rec[0] = True
+            for spent in rec[1]:
+                emit_repeat(spent)
+            del rec[1][:]
+
+    def emit_repeat(spent):
+        """a repeat unit behind the packet written last; spent: the seconds of its loader, window and compare"""
+        t1 = time.time()
+        bits.append(8 * writer.write_frame(ch, cw, two, enc.repeat()))
+        times.append(spent + time.time() - t1)
+        frame_types.append(1)                            # (a repeat counts as a P frame)
+        repeated.append(1)
 
     tf = None
     if tf_level:
@@ -536,29 +571,40 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
         x = src.to_input(planes, dtype)
         if area is not None:
             x = window(x, (src.h, src.w), area)
+        rec = None
+        if det is not None:
+            if det.is_repeat(x, size):                   # (has waited for its compare)
+                spent = time.time() - t0
+                if last[0]:
+                    emit_repeat(spent)
+                else:
+                    last[1].append(spent)
+                continue
+            last = rec = [False, []]
         if tf is None:
-            code(x, x, t0)
+            code(x, x, t0, rec)
             continue
         ready = tf.push(x, size)                         # frame t comes out when frame t + radius has gone in
         torch.cuda.synchronize(dev)
-        waiting.append((x, time.time() - t0))
+        waiting.append((x, time.time() - t0, rec))
         for y in ready:
-            x_source, spent = waiting.pop(0)
-            code(x_source, y, time.time() - spent)
+            x_source, spent, r = waiting.pop(0)
+            code(x_source, y, time.time() - spent, r)
     if tf is not None:
         t0 = time.time()
         for y in tf.flush():                             # (the last frames' blends are enqueued here: on the first one's clock)
-            x_source, spent = waiting.pop(0)
-            code(x_source, y, t0 - spent)
+            x_source, spent, r = waiting.pop(0)
+            code(x_source, y, t0 - spent, r)
             t0 = time.time()
     if la is not None:
         t0 = time.time()
         for y, cut in la.flush():
-            y_source, spent = held.pop(0)
-            emit(y_source, y, t0 - spent, cut)
+            y_source, spent, r = held.pop(0)
+            emit(y_source, y, t0 - spent, cut, r)
             t0 = time.time()
     reader.close()
-    return (enc, out.getvalue(), frame_types, bits, times, scaler, grainer, tf) + ((la,) if la is not None else ())
+    return ((enc, out.getvalue(), frame_types, bits, times, scaler, grainer, tf) + ((la,) if la is not None else ()) +
+            ((repeated,) if det is not None else ()))
 
 
 def _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, device_metrics, rec_path, scaler, grainer):
@@ -614,7 +660,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                   reset_interval=32, bin_path=None, rec_path=None, verbose=0, verbose_json=False, device="cuda:0",
                   src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
                   target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3", film_grain=None,
-                  temporal_filter=0, tf_radius=2, tf_subpel=0, lookahead=0, crop=None, crop_tol=0.0):
+                  temporal_filter=0, tf_radius=2, tf_subpel=0, lookahead=0, crop=None, crop_tol=0.0, frame_dup=False,
+                  dup_tol=0.0):
     """Encodes `frame_num` frames of a source (src_type: SRC_TYPES - a planar 8-bit YUV 4:2:0 file, a directory of PNGs, a raw
     file in a pipeline.PIXEL_FORMATS format) into the reference's container (optionally written to bin_path), decodes the
     container again and returns the reference-schema log (summarize) plus one group of keys per extension switched on.
@@ -633,7 +680,10 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
       tf_subpel                    its vectors in whole (0), half (1) or quarter pels (2)     log: + tf_subpel where not 0
       lookahead                    docs/lookahead.md (0 = off .. 16 frames; needs scenecut)   log: lookahead, flashes, fades
       crop, crop_tol               docs/active_area.md (None, "auto", (top, bottom, left, right, (y, u, v)) or its --crop spelling;
-                                   the colour and crop_tol in 8-bit codes)             log: active_area, bar_colour"""
+                                   the colour and crop_tol in 8-bit codes)             log: active_area, bar_colour
+      frame_dup, dup_tol           docs/frame_repeat.md (a frame within dup_tol 8-bit codes of the last coded frame is sent as a
+                                   one-byte repeat unit; bpp, target_bpp and the metrics stay per source frame, a repeat counts
+                                   as a P frame)                                        log: repeat_frames, dup_tol [, frame_repeat]"""
     from .grain import GrainParams
     from .lookahead import check_depth
     from .prefilter import check_options, check_subpel
@@ -643,6 +693,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         if value not in choices:
             raise ValueError(f"{name} {value!r}: one of {', '.join(choices)}")
     area, tol = check_crop(crop, crop_tol, height, width)
+    check_dup(frame_dup, dup_tol)
     coded_size = check_coded_size(coded_size, *(area.size if area not in (None, "auto") else (height, width)))
     if not (film_grain is None or film_grain == "auto" or isinstance(film_grain, GrainParams)):
         raise ValueError(f"film_grain {film_grain!r}: None, 'auto' or a GrainParams")
@@ -674,9 +725,13 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     extra = dict({"tf_subpel": tf_subpel} if tf_subpel else {}, **({"lookahead": lookahead} if lookahead else {}))
     if area is not None:
         extra["area"] = area
+    if frame_dup:
+        extra["dup_tol"] = dup_tol
     enc, stream, frame_types, bits, enc_time, scaler, grainer, tf, *la = _encode_pass(nets, src, frame_num, dev, coded_size,
                                                                                       scale_filter, film_grain, enc_kw,
                                                                                       temporal_filter, tf_radius, **extra)
+    repeated = la.pop() if frame_dup else None
+    coded_num = frame_num - sum(repeated) if frame_dup else frame_num         # the frames the filter and the encoder saw
     if bin_path:
         with open(bin_path, "wb") as f:
             f.write(stream)
@@ -703,7 +758,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                    grain_corr=last.corr if last else 0)
     if tf is not None:
         log.update(tf_level=temporal_filter, tf_radius=tf_radius,
-                   tf_mean_weight=tf.weight_sum() / (256.0 * (area.height * area.width if area else height * width) * frame_num))
+                   tf_mean_weight=tf.weight_sum() / (256.0 * (area.height * area.width if area else height * width) * coded_num))
         if temporal_filter == "auto":                     # frames per level 0 .. 5; the mean N as white noise's sigma in 8-bit codes
             totals = tf.levels()
             log.update(tf_levels=totals[:6], tf_noise=totals[6] / max(totals[7], 1) * (255.0 / (68.0 * 1023.0)))
@@ -712,6 +767,10 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     if crop is not None:
         log["active_area"] = area.extents if area is not None else [0, 0, 0, 0]
         log["bar_colour"] = list(area.colour) if area is not None else None
+    if frame_dup:
+        log.update(repeat_frames=sum(repeated), dup_tol=float(dup_tol))
+        if verbose_json:
+            log["frame_repeat"] = list(repeated)
     return log
 
 
@@ -719,7 +778,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
 # manifest_options all go through point_kwargs, so a new option is one row here, one build_parser line under the same name and
 # its hook in run_one_point.  target_bpp is not one of them: it is worked out per sequence (target_bpp()).  Nor
 # are temporal_filter / tf_radius / tf_subpel: they act in front of the encoder, not on a rate point, and the table's names are pinned
-# (tests/test_harness_options.py), so they travel target_bpp's way - prefilter_kwargs(), passed beside point_kwargs().  lookahead goes the same way: lookahead_kwargs().  So does crop / crop_tol: crop_kwargs(), which hands on nothing at all where the option is not set.
+# (tests/test_harness_options.py), so they travel target_bpp's way - prefilter_kwargs(), passed beside point_kwargs().  lookahead goes the same way: lookahead_kwargs().  So does crop / crop_tol: crop_kwargs(), which hands on nothing at all where the option is not set, and frame_dup / dup_tol: dup_kwargs(), likewise.
 POINT_OPTIONS = (("verbose", 0, None), ("verbose_json", False, bool), ("calc_ssim", False, bool), ("metrics", "host", None),
                  ("entropy", "host", None), ("scenecut", 0, None), ("min_keyint", 4, None), ("digest", False, bool),
                  ("coded_size", None, None), ("scale_filter", "lanczos3", None), ("film_grain", None, None))
@@ -754,6 +813,15 @@ def crop_kwargs(opts):
     if not opts.get("crop"):
         return {}
     return dict({"crop": opts["crop"]}, **({"crop_tol": opts["crop_tol"]} if opts.get("crop_tol") else {}))
+
+
+def dup_kwargs(opts):
+    """an options mapping -> run_one_point's keywords of repeated-frame coding: none at all where frame_dup is missing or
+    false (the keywords of before the option), dup_tol only where it is set and not 0.  It acts in front of the encoder and
+    travels beside point_kwargs(), as crop_kwargs() does"""
+    if not opts.get("frame_dup"):
+        return {}
+    return dict({"frame_dup": True}, **({"dup_tol": opts["dup_tol"]} if opts.get("dup_tol") else {}))
 
 
 def run_sweep(make_nets, src_path, width, height, frame_num, rate_num=4, qp_i=None, qp_p=None, bin_prefix=None, **kw):
@@ -956,7 +1024,7 @@ def run_job(nets, job, opts):
                         job["qp_i"], job["qp_p"], intra_period=job["intra_period"], reset_interval=job["reset_interval"],
                         bin_path=bin_path, rec_path=rec_path, device="cuda:0", src_type=job.get("src_type", "yuv420"),
                         target_bpp=target_bpp(opts, job["src_width"], job["src_height"]), **prefilter_kwargs(opts),
-                        **lookahead_kwargs(opts), **crop_kwargs(opts), **point_kwargs(opts))
+                        **lookahead_kwargs(opts), **crop_kwargs(opts), **dup_kwargs(opts), **point_kwargs(opts))
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -1023,6 +1091,13 @@ def check_crop_options(args, ap):
         ap.error("--crop-tol is in 8-bit codes, >= 0")
 
 
+def check_dup_options(args, ap):
+    if args.dup_tol is not None and not args.frame_dup:
+        ap.error("--dup-tol is the tolerance of --frame-dup: it has no effect without it")
+    if args.dup_tol is not None and not args.dup_tol >= 0:
+        ap.error("--dup-tol is in 8-bit codes, >= 0")
+
+
 def _str2bool(v):
     """the reference's str2bool (test_video.py:24-28): --flag 1 / true / yes / y / t"""
     if isinstance(v, bool):
@@ -1036,7 +1111,7 @@ def _str2bool(v):
 
 def _add_extension_options(ap, flag):
     """this project's options beyond the reference's: adaptive I frames, rate control, digests, reduced resolution, film grain,
-    the temporal pre-filter, the frame lookahead, active-area coding"""
+    the temporal pre-filter, the frame lookahead, active-area coding, repeated-frame coding"""
     from .resize import FILTERS, parse_size
     ap.add_argument("--scenecut", type=int, default=0, metavar="PCT",
                     help="adaptive I frames: a frame whose low-resolution difference to its predecessor is at least PCT percent "
@@ -1084,6 +1159,14 @@ def _add_extension_options(ap, flag):
     ap.add_argument("--crop-tol", "--crop_tol", type=float, default=None, metavar="X",
                     help="with --crop auto: a line is a bar while it stays within X 8-bit codes of the bars' colour (default 0: "
                          "exactly flat bars, nothing can be lost; above 0 for noisy bars)")
+    ap.add_argument("--frame-dup", "--frame_dup", **flag,
+                    help="repeated-frame coding: a frame that is the picture of the last coded frame (screen and slide capture, "
+                         "animation on twos, 24 -> 30 fps conversions, frozen feeds) is found on the device and sent as a "
+                         "one-byte repeat unit; the encoder sees the sequence without it (docs/frame_repeat.md) - this "
+                         "project's extension, not readable by the reference")
+    ap.add_argument("--dup-tol", "--dup_tol", type=float, default=None, metavar="X",
+                    help="with --frame-dup: a frame is a repeat while every sample stays within X 8-bit codes of the last coded "
+                         "frame (default 0: equal frames only; above 0 for material that went through a dithered stage)")
     ap.add_argument("--tf-subpel", "--tf_subpel", type=int, default=0, choices=(0, 1, 2), metavar="S",
                     help="with --temporal-filter: refine the filter's motion vectors to half (1) or quarter pels (2) and gather "
                          "interpolated reference samples (0 = whole-pel vectors; 2 is recommended for camera material)")
@@ -1175,7 +1258,8 @@ def manifest_options(args, ap):
                                           "reset_interval", "model_i", "model_p", "force_zero_thres", "fp32", "target_bpp",
                                           "target_kbps", "fps", "force_intra", "check_existing", "save_decoded_frame",
                                           "temporal_filter", "tf_radius", "tf_subpel", "lookahead")}
-    opts.update(gpu_ids=gpu_ids, stream_path=stream_path, **crop_kwargs(vars(args)), **point_kwargs(vars(args)))
+    opts.update(gpu_ids=gpu_ids, stream_path=stream_path, **crop_kwargs(vars(args)), **dup_kwargs(vars(args)),
+                **point_kwargs(vars(args)))
     return opts, gpus
 
 
@@ -1185,6 +1269,7 @@ def main(argv=None):
     check_rate_options(args, ap)
     check_lookahead_options(args, ap)
     check_crop_options(args, ap)
+    check_dup_options(args, ap)
     if args.test_config:
         with open(args.test_config) as f:
             config = json.load(f)
@@ -1210,7 +1295,7 @@ def main(argv=None):
                     bin_prefix=args.bin_prefix, intra_period=args.intra_period, reset_interval=args.reset_interval,
                     src_type=args.src_type, target_bpp=target_bpp(vars(args), args.width, args.height),
                     **prefilter_kwargs(vars(args)), **lookahead_kwargs(vars(args)), **crop_kwargs(vars(args)),
-                    **point_kwargs(vars(args)))
+                    **dup_kwargs(vars(args)), **point_kwargs(vars(args)))
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:

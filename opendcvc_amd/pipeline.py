@@ -7,6 +7,7 @@ from dataclasses import dataclass
 from typing import Optional
 
 INDEX_MAP = (0, 1, 0, 2, 0, 2, 0, 2)          # test_video.py:164
+REPEAT = object()                             # in EncodeDecodePipeline.run's frames: "the picture of the frame before, again"
 
 
 @dataclass
@@ -18,6 +19,7 @@ class FramePacket:
     chunked: bool = False        # chunked payload (the models' entropy="device" mode): written as NAL_I_CHUNKED / NAL_P_CHUNKED
     grain: Optional[object] = None   # grain.GrainParams in force from this frame on (docs/film_grain.md): a NAL_GRAIN unit,
                                      # written in front of the digest unit as it stands in front of it here
+    repeat: bool = False             # the picture of the frame before, again (docs/frame_repeat.md): a NAL_REPEAT unit, no payload
     digest: Optional[int] = None     # digest of the entry the frame puts into the DPB (docs/state_digest.md): a NAL_DIGEST unit
 
 
@@ -112,9 +114,13 @@ class SequenceEncoder:
         """rate control's log: the exact size of every packet handed out (never fed back to the controller)"""
         if self.rate is not None:
             from .bitstream import frame_overhead_bytes
+            from .bitstream import REPEAT_UNIT_BYTES
             for pkt in (pkts if isinstance(pkts, list) else [pkts]):
                 n = len(pkt.bit_stream)
-                self.rc_bytes.append(n + frame_overhead_bytes(n) + self._unit_bytes(getattr(pkt, "grain", None)))
+                if getattr(pkt, "repeat", False):        # (the unit is its header: no qp, no length, no digest)
+                    self.rc_bytes.append(REPEAT_UNIT_BYTES)
+                else:
+                    self.rc_bytes.append(n + frame_overhead_bytes(n) + self._unit_bytes(getattr(pkt, "grain", None)))
                 self.rate.record_exact(self._rc_out, n)
                 self._rc_out += 1
         return pkts
@@ -226,6 +232,32 @@ class SequenceEncoder:
         self._held = (qp, use_ada_i, chunked, handle)
         return done
 
+    def repeat(self):
+        """the frame is the picture of the frame before (docs/frame_repeat.md) -> its repeat packet; with defer_stream a
+        list: the held P packet, finished first so that the order is kept, then the repeat packet.  ValueError before the
+        first frame.  Nothing is launched and no counter moves: frame_idx, the GOP position, reset_interval and the
+        INDEX_MAP cycle are untouched, so the coded frames are exactly the sequence they would be with the repeated frames
+        deleted from the source - intra_period and min_keyint thereby count CODED frames.  With rate control the pending
+        observation is fed first, then the controller is told of a frame of 8 bits that was not coded
+        (RateController.skip: the budget a repeat frees goes to its neighbours, the model learns nothing); rc_qp repeats
+        the last qp, rc_est_bytes and rc_bytes get the unit's one byte."""
+        from .bitstream import REPEAT_UNIT_BYTES
+        from .models import CAPTURE_GUARD
+        if self.frame_idx == 0:
+            raise ValueError("repeat() before the first frame: there is no picture to repeat")
+        with CAPTURE_GUARD.frame():
+            done = self._take_held(self.p_net.finish_stream()) if self.defer else []
+            if self.rate is not None:
+                if self._rc_pending is not None:
+                    klass, base, est = self._rc_pending
+                    self.rate.observe(klass, base, 8 * est)
+                    self._rc_pending = None
+                self.rate.skip(8 * REPEAT_UNIT_BYTES)
+                self.rc_qp.append(self.rc_qp[-1])
+                self.rc_est_bytes.append(REPEAT_UNIT_BYTES)
+            pkt = FramePacket(False, 0, 0, b"", repeat=True)
+            return self._sized(done + [pkt] if self.defer else pkt)
+
     def flush(self):
         """defer_stream: the packet still pending (empty list otherwise)"""
         from .models import CAPTURE_GUARD
@@ -243,7 +275,11 @@ class SequenceDecoder:
     DPB the device forms the entry's digest and compares it with the packet's.  The result is read lazily - at the start of
     the next decode(), in flush() (so call it at the end of a stream, deferring or not) and in check_digests() for callers
     that have synchronised anyway - and a difference raises _lib.DigestMismatch naming the frame's index in decode order;
-    digests_checked counts the frames that passed.  After a mismatch resume at the next I frame, as after DcvcError."""
+    digests_checked counts the frames that passed.  After a mismatch resume at the next I frame, as after DcvcError.
+
+    A repeat packet (docs/frame_repeat.md) gives the previous picture, the same tensor: nothing is launched, the DPB and the
+    digests are not touched, frame_idx counts it; with defer_output the pending picture is finished first and both come out
+    in order.  Before any picture it raises DcvcError."""
 
     def __init__(self, i_net, p_net, height, width, use_two, defer_output=False):
         self.i_net, self.p_net = i_net, p_net
@@ -253,6 +289,7 @@ class SequenceDecoder:
         self.digests_checked = 0
         self._digester = None        # (made at the first packet with a digest, on the entry's device)
         self._unchecked = []         # (index, is_i, expected, handle) of the digests enqueued and not yet read
+        self._last_pic = None        # the picture handed out last: what a repeat packet shows again
         p_net.set_curr_poc(0)
 
     def decode(self, pkt):
@@ -260,7 +297,12 @@ class SequenceDecoder:
         with CAPTURE_GUARD.frame():
             self._check_digests()
             index, self.frame_idx = self.frame_idx, self.frame_idx + 1
+            if getattr(pkt, "repeat", False):
+                return self._repeat()
             out = self._decode(pkt)
+            last = out[-1:] if self.defer else [out]
+            if last:
+                self._last_pic = last[0]
             expected = getattr(pkt, "digest", None)
             if expected is not None:
                 entry = _dpb_entry(self.p_net)
@@ -278,6 +320,21 @@ class SequenceDecoder:
             if handle.status() != EQUAL:
                 raise DigestMismatch(index, is_i, expected, handle.value())
             self.digests_checked += 1
+
+    def _repeat(self):
+        """a repeat packet: the previous picture, the same tensor; nothing is launched, the DPB and the digests stay as they
+        are.  defer_output: the pending picture is finished first, as an I frame finishes it, and both are returned"""
+        from ._lib import DcvcError
+        done = []
+        if self.defer:
+            last = self.p_net.finish_output()
+            if last is not None:
+                done.append(last)
+                self._last_pic = last
+        if self._last_pic is None:
+            raise DcvcError("a repeat packet before any picture: there is nothing to repeat")
+        done.append(self._last_pic)
+        return done if self.defer else done[-1]
 
     def check_digests(self):
         """reads the digests enqueued so far (waits for the newest one's event: free behind a synchronisation)"""
@@ -313,6 +370,8 @@ class SequenceDecoder:
         with CAPTURE_GUARD.frame():
             last = self.p_net.finish_output() if self.defer else None
             self._check_digests()
+        if last is not None:
+            self._last_pic = last
         return [] if last is None else [last]
 
 
@@ -326,6 +385,7 @@ class DecodedFrame:
     grain: Optional[object]
     grain_t: int
     active: Optional[object] = None  # StreamReader.active behind this frame: x_hat and shown are then the full picture
+    repeat: bool = False             # a repeat unit (docs/frame_repeat.md): the picture of the frame before, its own grain_t
 
 
 class StreamDecoder:
@@ -334,7 +394,9 @@ class StreamDecoder:
     what the stream's extension units ask for behind it - the display unit's resample (docs/reduced_resolution.md) and the
     grain unit's synthesis (docs/film_grain.md), then the active-area unit's paste into the full picture
     (docs/active_area.md; one paste without grain, shown is x_hat then as ever).  scaler / grainer: a resize.Resampler / grain.FilmGrain to use; otherwise
-    each is made when the stream first needs one, so a stream without these units launches the decoder's own kernels only."""
+    each is made when the stream first needs one, so a stream without these units launches the decoder's own kernels only.
+    A repeat unit (docs/frame_repeat.md) decodes and resamples nothing: the frame keeps the last resampled picture, gets the
+    grain of its own grain_t - the grain moves on a still picture - and is pasted as any frame; DecodedFrame.repeat says so."""
 
     def __init__(self, f, i_net, p_net, device, scaler=None, grainer=None):
         from .bitstream import StreamReader
@@ -342,6 +404,7 @@ class StreamDecoder:
         self.i_net, self.p_net, self.device = i_net, p_net, device
         self.scaler, self.grainer = scaler, grainer
         self.dec = None
+        self._resampled = None       # (picture at its display size, that size) of the frame before: what a repeat unit shows
 
     def next(self):
         """the next frame of the stream -> DecodedFrame; everything is enqueued on the current stream, nothing is waited for"""
@@ -352,11 +415,14 @@ class StreamDecoder:
             self.dec = SequenceDecoder(self.i_net, self.p_net, *size, bool(sps["ec_part"]))
         self.dec.h, self.dec.w, self.dec.two = *size, bool(sps["ec_part"])
         x_hat = self.dec.decode(pkt)
-        if rd.display is not None:
+        if pkt.repeat:                               # the picture as it was resampled for the frame it repeats
+            x_hat, size = self._resampled
+        elif rd.display is not None:
             if self.scaler is None:
                 from .resize import Resampler
                 self.scaler = Resampler(self.device)
             x_hat, size = self.scaler.resample(x_hat, size, rd.display[:2], rd.display[2]), rd.display[:2]
+        self._resampled = (x_hat, size)
         shown = x_hat
         if rd.grain is not None:
             if self.grainer is None:
@@ -367,8 +433,8 @@ class StreamDecoder:
             from .bars import paste
             full = paste(x_hat, rd.active)
             x_hat, shown = full, (full if shown is x_hat else paste(shown, rd.active))
-            return DecodedFrame(x_hat, shown, sps, pkt.is_i, rd.display, rd.grain, rd.grain_t, rd.active)
-        return DecodedFrame(x_hat, shown, sps, pkt.is_i, rd.display, rd.grain, rd.grain_t)
+            return DecodedFrame(x_hat, shown, sps, pkt.is_i, rd.display, rd.grain, rd.grain_t, rd.active, repeat=pkt.repeat)
+        return DecodedFrame(x_hat, shown, sps, pkt.is_i, rd.display, rd.grain, rd.grain_t, repeat=pkt.repeat)
 
     def check_digests(self):
         if self.dec is not None:
@@ -406,7 +472,8 @@ class EncodeDecodePipeline:
                 on_frame(x)
 
     def run(self, frames, on_packet=None, on_frame=None):
-        """frames: iterable of padded model inputs (device tensors, ready on the calling stream).
+        """frames: iterable of padded model inputs (device tensors, ready on the calling stream); REPEAT in place of a frame
+        that is the picture of the one before (docs/frame_repeat.md): its repeat packet travels in order like any other.
         on_packet(pkt) is called on the encoder thread, on_frame(x_hat) on the decoder thread with the
         decoder stream current.  Returns when every frame has been encoded and decoded."""
         import queue
@@ -435,7 +502,7 @@ class EncodeDecodePipeline:
 
                     for x in frames:
                         with CAPTURE_GUARD.frame():
-                            pkts = self.encoder.encode(x)
+                            pkts = self.encoder.repeat() if x is REPEAT else self.encoder.encode(x)
                         emit(pkts)
                     if getattr(self.encoder, "defer", False):
                         with CAPTURE_GUARD.frame():

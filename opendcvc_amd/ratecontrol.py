@@ -117,5 +117,11 @@ class RateController:
         self._level, self._anchor = at + LEVEL_GAIN * resid, base
         self._class[klass] = self._class.get(klass, 0.0) + CLASS_GAIN * resid
 
+    def skip(self, bits):
+        """one frame that was not coded (a repeat unit of `bits` bits, docs/frame_repeat.md): it counts and pays into the
+        debt like any frame - the budget it leaves goes to its neighbours - and teaches the model nothing"""
+        self.frames += 1
+        self.debt += bits - self.target
+
     def record_exact(self, frame_idx, nbytes):
         self.exact_bytes.append((int(frame_idx), int(nbytes)))
