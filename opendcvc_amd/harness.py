@@ -32,6 +32,7 @@ import numpy as np
 from .bitstream import StreamWriter
 from .pipeline import (PIXEL_FORMATS, PixelFormat, SequenceEncoder, StreamDecoder, load_frame, load_yuv420_frame, store_frame,
                        store_yuv420_frame, use_two_entropy_coders)
+from .repeat import tol_fraction
 
 SRC_TYPES = ("yuv420", "png") + tuple(PIXEL_FORMATS)     # "yuv420": planar 8-bit 4:2:0 with the reference harness's arithmetic
 
@@ -426,10 +427,8 @@ def parse_crop(text):
 
 def check_crop(crop, crop_tol, height, width):
     """run_one_point's crop / crop_tol -> (None | 'auto' | the bars.ActiveArea of a manual crop, tol as the kernels take it:
-    crop_tol 8-bit codes as an fp32 fraction of 255)"""
-    tol = float(np.float32(crop_tol) / np.float32(255.0))
-    if not tol >= 0.0:
-        raise ValueError(f"crop_tol {crop_tol!r}: 8-bit codes, >= 0")
+    crop_tol 8-bit codes as repeat.tol_fraction turns them)"""
+    tol = tol_fraction(crop_tol, "crop_tol")
     if tol and crop != "auto":
         raise ValueError(f"crop_tol {crop_tol!r} is the tolerance of crop='auto': it has no effect on crop {crop!r}")
     if crop is None or crop == "auto":
@@ -444,10 +443,8 @@ def check_crop(crop, crop_tol, height, width):
 
 
 def check_dup(frame_dup, dup_tol):
-    """run_one_point's frame_dup / dup_tol: ValueError for a dup_tol that is negative or NaN (8-bit codes, turned into the
-    kernel's unit as crop_tol is) or that is set without frame_dup"""
-    from .repeat import tol_fraction
-    if tol_fraction(dup_tol) and not frame_dup:
+    """run_one_point's frame_dup / dup_tol: ValueError for a dup_tol that repeat.tol_fraction refuses or that is set without frame_dup"""
+    if tol_fraction(dup_tol, "dup_tol") and not frame_dup:
         raise ValueError(f"dup_tol {dup_tol!r} is the tolerance of frame_dup: it has no effect without it")
 
 
@@ -467,144 +464,56 @@ def _detect_area(src, frame_num, dev, dtype, tol):
 
 def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, tf_level=0, tf_radius=2, tf_subpel=0,
                  lookahead=0, area=None, dup_tol=None):
-    """every frame of `src` through a SequenceEncoder(**enc_kw) into the container; coded: None or the (height, width) the
-    frames are resampled down to first; grain: None, a GrainParams, or "auto" (estimated at every I frame from the full-size
-    input against the reconstruction at that size, the unit's seed the frame's index); tf_level 1 .. 5 or "auto": the frames pass
-    a prefilter.TemporalFilter (vectors refined to half / quarter pels with tf_subpel 1 / 2) at source size first, which reads
-    tf_radius frames ahead - grain "auto" is still given the UNFILTERED
-    input of the frame being coded.  The clock of a frame spans loader, temporal filter, down-resample, encode and
-    write_frame; the file read and the copy to the device stay outside.  lookahead N > 0: the frames the encoder is to see
-    (filtered, resampled) pass a lookahead.Lookahead of depth N, which holds N of them back and hands each to the encoder with
-    its cut decision; its delay adds to the temporal filter's, and a frame's clock and its unfiltered input follow it through
-    both queues.  area (a bars.ActiveArea, docs/active_area.md): every frame is cut down to the area's window right behind the
-    loader, everything above then works at the window's size, and the stream says what the window is a window of.
-    dup_tol (None: off, no detector is made; else 8-bit codes, docs/frame_repeat.md): right behind the loader and the window
-    a repeat.RepeatDetector holds every frame against the last frame that was no repeat.  A repeat goes no further - the
-    temporal filter, the down-resample, the lookahead and the encoder see the sequence without it - and is a trailer of the
-    frame it repeats: the record that travels with that frame through the queues counts it, emit writes that many repeat
-    units behind the frame's packet, and a repeat whose frame is already written is written at once.  Per repeat: 8 bits,
-    frame type 1 (a P frame), the time of loader + window + compare + unit write.  The loader and the window allocate their
-    output per frame, so the detector's reference is never overwritten and nothing is cloned.
-    -> (encoder, stream bytes, frame types, bits, times, the Resampler, the FilmGrain and the TemporalFilter made here or None;
-    with lookahead the Lookahead as a ninth; with dup_tol the per-frame 0 / 1 list of the repeats as the last)"""
+    """every frame of `src` through a frontend.FrontEnd into the container -> a frontend.EncodePass.  A frame goes loader -> area
+    (a bars.ActiveArea): its window, whose size all behind it works at -> dup_tol (None: off; else 8-bit codes): a
+    repeat.RepeatDetector -> tf_level 1 .. 5 or "auto": a prefilter.TemporalFilter tf_radius frames deep -> coded (height, width):
+    the down-resample -> lookahead N > 0: a lookahead.Lookahead N frames deep -> SequenceEncoder(**enc_kw) -> write_frame; what is
+    off is not made.  grain: None, a GrainParams, or "auto": estimated at every I frame from the UNFILTERED input of the frame being
+    coded against the reconstruction at that size, seeded with the count of frames written so far.  A frame's clock: frontend.py."""
     import torch
+    from .frontend import EncodePass, FrontEnd
     from .grain import FilmGrain
     from .resize import Resampler
     size = area.size if area is not None else (src.h, src.w)
-    ch, cw = coded or size
-    dtype = next(nets[1].parameters()).dtype
-    scaler = Resampler(dev) if coded else None
-    reader = src.reader()
-    grainer = FilmGrain(dev) if grain is not None else None
-    source, frame_types, bits, times = [], [], [], []
+    dtype, (ch, cw) = next(nets[1].parameters()).dtype, coded or size
+    sync, clock = (lambda: torch.cuda.synchronize(dev)), time.time
+    scaler, grainer = Resampler(dev) if coded else None, FilmGrain(dev) if grain is not None else None
     if grain is not None:
         def estimate(x_coded, x_hat):
-            if scaler:
-                x_hat = scaler.resample(x_hat, (ch, cw), size, scale_filter)
-            return grainer.estimate(source[0], x_hat, size, len(frame_types))
+            x_hat = scaler.resample(x_hat, (ch, cw), size, scale_filter) if scaler else x_hat
+            return grainer.estimate(front.coding.source, x_hat, size, len(front.units))
         enc_kw = dict(enc_kw, grain=estimate if grain == "auto" else grain)
     enc = SequenceEncoder(*nets, **enc_kw)
-    out = io.BytesIO()
-    if area is not None:
-        from .bars import window
-    writer = StreamWriter(out, display=size + (scale_filter,) if coded else None, active=area)
-    two = use_two_entropy_coders(ch, cw)
-
-    la = None
-    if lookahead:
-        from .lookahead import Lookahead
-        la = Lookahead(dev, lookahead, enc.scenecut)
-        held = []                                        # (unfiltered input, seconds on the clock so far, record) of the frames held back
-
-    det, repeated, last = None, [], None
-    if dup_tol is not None:
-        from .repeat import RepeatDetector
-        det = RepeatDetector(dev, dup_tol)               # last: the record of the last frame that was no repeat -
-                                                         # [written?, the seconds of each of its repeats not yet written]
-
-    def code(x_source, x, t0, rec=None):
-        """x (the frame as the encoder is to see it at source size) from the clock reading t0 on; rec: its record"""
-        if scaler:
-            x = scaler.resample(x, size, (ch, cw), scale_filter)
-        if la is None:
-            return emit(x_source, x, t0, None, rec)
-        if tf is not None and not scaler:
-            x = x.clone()                                # (the filter's output buffers come round again before the frame is coded)
-        done = la.push(x)
-        torch.cuda.synchronize(dev)
-        held.append((x_source, time.time() - t0, rec))
-        for y, cut in done:
-            y_source, spent, r = held.pop(0)
-            emit(y_source, y, time.time() - spent, cut, r)
-
-    def emit(x_source, x, t0, cut=None, rec=None):
-        source[:] = [x_source]                           # "auto": the full-size unfiltered input of the frame being coded
-        pkt = enc.encode(x) if cut is None else enc.encode(x, cut=cut)
-        bits.append(8 * writer.write_frame(ch, cw, two, pkt))
-        torch.cuda.synchronize(dev)
-        times.append(time.time() - t0)
-        frame_types.append(0 if pkt.is_i else 1)
-        if rec is not None:                              # the frame's trailer: the repeats found while it was queued
-            repeated.append(0)
-            rec[0] = True
-            for spent in rec[1]:
-                emit_repeat(spent)
-            del rec[1][:]
-
-    def emit_repeat(spent):
-        """a repeat unit behind the packet written last; spent: the seconds of its loader, window and compare"""
-        t1 = time.time()
-        bits.append(8 * writer.write_frame(ch, cw, two, enc.repeat()))
-        times.append(spent + time.time() - t1)
-        frame_types.append(1)                            # (a repeat counts as a P frame)
-        repeated.append(1)
-
-    tf = None
+    det = tf = la = None
+    if dup_tol is not None:                              # (the loader and the window allocate their output per frame: the
+        from .repeat import RepeatDetector               # detector's reference is never overwritten, nothing is cloned for it)
+        det = RepeatDetector(dev, dup_tol)
     if tf_level:
         from .prefilter import TemporalFilter
         tf = TemporalFilter(dev, tf_level, tf_radius, tf_subpel)
-        waiting = []                                     # (unfiltered input, seconds on the clock so far) of the frames read ahead
+    if lookahead:
+        from .lookahead import Lookahead
+        la = Lookahead(dev, lookahead, enc.scenecut)
+    if area is not None:
+        from .bars import window
+    out = io.BytesIO()
+    writer = StreamWriter(out, display=size + (scale_filter,) if coded else None, active=area)
+    front = FrontEnd(enc, writer, (ch, cw, use_two_entropy_coders(ch, cw)), sync, clock, size, det, tf,
+                     (lambda x: scaler.resample(x, size, (ch, cw), scale_filter)) if scaler else None, la)
+
+    reader = src.reader()
     for _ in range(frame_num):
         planes = _to_device(reader.read(), dev)
-        torch.cuda.synchronize(dev)
-        t0 = time.time()
+        sync()
+        t0 = clock()
         x = src.to_input(planes, dtype)
         if area is not None:
             x = window(x, (src.h, src.w), area)
-        rec = None
-        if det is not None:
-            if det.is_repeat(x, size):                   # (has waited for its compare)
-                spent = time.time() - t0
-                if last[0]:
-                    emit_repeat(spent)
-                else:
-                    last[1].append(spent)
-                continue
-            last = rec = [False, []]
-        if tf is None:
-            code(x, x, t0, rec)
-            continue
-        ready = tf.push(x, size)                         # frame t comes out when frame t + radius has gone in
-        torch.cuda.synchronize(dev)
-        waiting.append((x, time.time() - t0, rec))
-        for y in ready:
-            x_source, spent, r = waiting.pop(0)
-            code(x_source, y, time.time() - spent, r)
-    if tf is not None:
-        t0 = time.time()
-        for y in tf.flush():                             # (the last frames' blends are enqueued here: on the first one's clock)
-            x_source, spent, r = waiting.pop(0)
-            code(x_source, y, t0 - spent, r)
-            t0 = time.time()
-    if la is not None:
-        t0 = time.time()
-        for y, cut in la.flush():
-            y_source, spent, r = held.pop(0)
-            emit(y_source, y, t0 - spent, cut, r)
-            t0 = time.time()
+        front.feed(x, t0)
+    front.flush()
     reader.close()
-    return ((enc, out.getvalue(), frame_types, bits, times, scaler, grainer, tf) + ((la,) if la is not None else ()) +
-            ((repeated,) if det is not None else ()))
+    frame_types, bits, times, repeated = ([unit[i] for unit in front.units] for i in range(4))
+    return EncodePass(enc, out.getvalue(), frame_types, bits, times, scaler, grainer, tf, la, repeated if det is not None else None)
 
 
 def _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, device_metrics, rec_path, scaler, grainer):
@@ -727,40 +636,37 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         extra["area"] = area
     if frame_dup:
         extra["dup_tol"] = dup_tol
-    enc, stream, frame_types, bits, enc_time, scaler, grainer, tf, *la = _encode_pass(nets, src, frame_num, dev, coded_size,
-                                                                                      scale_filter, film_grain, enc_kw,
-                                                                                      temporal_filter, tf_radius, **extra)
-    repeated = la.pop() if frame_dup else None
-    coded_num = frame_num - sum(repeated) if frame_dup else frame_num         # the frames the filter and the encoder saw
+    done = _encode_pass(nets, src, frame_num, dev, coded_size, scale_filter, film_grain, enc_kw, temporal_filter, tf_radius, **extra)
+    coded_num = frame_num - sum(done.repeated) if frame_dup else frame_num         # the frames the filter and the encoder saw
     if bin_path:
         with open(bin_path, "wb") as f:
-            f.write(stream)
-    decoder, dec_time, psnrs, ssims = _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, metrics == "device", rec_path,
-                                                   scaler, grainer)
+            f.write(done.stream)
+    decoder, dec_time, psnrs, ssims = _decode_pass(nets, src, done.stream, frame_num, dev, calc_ssim, metrics == "device", rec_path,
+                                                   done.scaler, done.grainer)
     test_time = time.time() - t_start
     timed = verbose >= 1 and frame_num > 10     # the first 10 frames are warm-up (test_video.py:328-333)
-    log = summarize(height * width, test_time, frame_types, bits, psnrs, ssims, verbose=verbose_json,
-                    avg_encoding_time=sum(enc_time[10:]) / len(enc_time[10:]) if timed else None,
+    log = summarize(height * width, test_time, done.frame_types, done.bits, psnrs, ssims, verbose=verbose_json,
+                    avg_encoding_time=sum(done.times[10:]) / len(done.times[10:]) if timed else None,
                     avg_decoding_time=sum(dec_time[10:]) / len(dec_time[10:]) if timed else None)
     if scenecut:
-        log["scene_cuts"] = list(enc.scene_cuts)
-    if la:
-        log.update(lookahead=lookahead, flashes=list(la[0].flashes), fades=list(la[0].fades))
+        log["scene_cuts"] = list(done.enc.scene_cuts)
+    if done.lookahead is not None:
+        log.update(lookahead=lookahead, flashes=list(done.lookahead.flashes), fades=list(done.lookahead.fades))
     if target_bpp:
-        log.update(_rate_log(enc, float(target_bpp), frame_num, height * width, verbose_json))
+        log.update(_rate_log(done.enc, float(target_bpp), frame_num, height * width, verbose_json))
     if digest:
         log["digests_checked"] = decoder.digests_checked
     if coded_size:
         log["coded_height"], log["coded_width"], log["scale_filter"] = *coded_size, scale_filter
     if film_grain is not None:
-        last = enc.grain_units[-1] if enc.grain_units else None
-        log.update(grain_units=len(enc.grain_units), grain_scale_y=list(last.scale_y) if last else [],
+        last = done.enc.grain_units[-1] if done.enc.grain_units else None
+        log.update(grain_units=len(done.enc.grain_units), grain_scale_y=list(last.scale_y) if last else [],
                    grain_corr=last.corr if last else 0)
-    if tf is not None:
+    if done.tf is not None:
         log.update(tf_level=temporal_filter, tf_radius=tf_radius,
-                   tf_mean_weight=tf.weight_sum() / (256.0 * (area.height * area.width if area else height * width) * coded_num))
+                   tf_mean_weight=done.tf.weight_sum() / (256.0 * (area.height * area.width if area else height * width) * coded_num))
         if temporal_filter == "auto":                     # frames per level 0 .. 5; the mean N as white noise's sigma in 8-bit codes
-            totals = tf.levels()
+            totals = done.tf.levels()
             log.update(tf_levels=totals[:6], tf_noise=totals[6] / max(totals[7], 1) * (255.0 / (68.0 * 1023.0)))
         if tf_subpel:
             log["tf_subpel"] = tf_subpel
@@ -768,9 +674,9 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         log["active_area"] = area.extents if area is not None else [0, 0, 0, 0]
         log["bar_colour"] = list(area.colour) if area is not None else None
     if frame_dup:
-        log.update(repeat_frames=sum(repeated), dup_tol=float(dup_tol))
+        log.update(repeat_frames=sum(done.repeated), dup_tol=float(dup_tol))
         if verbose_json:
-            log["frame_repeat"] = list(repeated)
+            log["frame_repeat"] = list(done.repeated)
     return log
 
 

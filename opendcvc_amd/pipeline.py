@@ -125,12 +125,16 @@ class SequenceEncoder:
                 self._rc_out += 1
         return pkts
 
-    def _rc_base(self):
-        """feeds the previous frame's estimate to the controller and returns the base qp of this frame"""
+    def _rc_feed(self):
+        """feeds the estimate of the frame coded last to the controller, once"""
         if self._rc_pending is not None:
             klass, base, est = self._rc_pending
             self.rate.observe(klass, base, 8 * est)
             self._rc_pending = None
+
+    def _rc_base(self):
+        """feeds the previous frame's estimate to the controller and returns the base qp of this frame"""
+        self._rc_feed()
         return self.rate.base_qp()
 
     def _rc_note(self, klass, base, qp, enc, grain=None):
@@ -248,10 +252,7 @@ class SequenceEncoder:
         with CAPTURE_GUARD.frame():
             done = self._take_held(self.p_net.finish_stream()) if self.defer else []
             if self.rate is not None:
-                if self._rc_pending is not None:
-                    klass, base, est = self._rc_pending
-                    self.rate.observe(klass, base, 8 * est)
-                    self._rc_pending = None
+                self._rc_feed()
                 self.rate.skip(8 * REPEAT_UNIT_BYTES)
                 self.rc_qp.append(self.rc_qp[-1])
                 self.rc_est_bytes.append(REPEAT_UNIT_BYTES)

@@ -8,13 +8,13 @@ kernel in numpy."""
 import ctypes
 
 
-def tol_fraction(tol):
-    """a tolerance in 8-bit codes -> the kernels' unit, an fp32 fraction of 255 (what harness.check_crop does with crop_tol);
-    ValueError for a negative or NaN one"""
+def tol_fraction(tol, name="dup_tol"):
+    """a tolerance in 8-bit codes -> the kernels' unit, an fp32 fraction of 255; ValueError, under the option's name, for a
+    negative or NaN one.  The one conversion: harness.check_crop turns crop_tol with it too"""
     import numpy as np
     frac = float(np.float32(tol) / np.float32(255.0))
     if not frac >= 0.0:
-        raise ValueError(f"dup_tol {tol!r}: 8-bit codes, >= 0")
+        raise ValueError(f"{name} {tol!r}: 8-bit codes, >= 0")
     return frac
 
 
