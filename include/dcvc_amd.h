@@ -539,6 +539,37 @@ int64_t dcvc_frame_maxdiff_ws_bytes(void);
 int dcvc_frame_maxdiff(int dtype, const void* a_nchw, const void* b_nchw, int Hp, int Wp, int H, int W, void* workspace,
                        uint32_t* out4, void* stream);
 /* ------------------------------------------------------------------------------------------
+ * Deinterlacing in front of the encoder (csrc/dcvc_deint.hip; docs/deinterlace.md is the normative text, which states every
+ * operation; no reference counterpart).  cur, prev and out are model frames [3][Hp][Wp] of one dtype (DCVC_F16 / DCVC_F32) and
+ * one shape, the picture H x W at the top left.  keep_parity: 0 keeps the even lines (top field first), 1 the odd ones.
+ * Lines are counted per plane in units of L rows: 1 for luma, chroma_lines (1 or 2) for the two chroma planes; row y is kept
+ * iff (y / L) % 2 == keep_parity.  H must be a multiple of 2 * chroma_lines.
+ * dcvc_deinterlace: a kept row of out is the bits of cur.  A sample of a missing row is the edge-directed mean of the lines
+ * above and below it (directions -2 .. 2, the straight one preferred by 1 / 255; row offsets that leave the picture are
+ * reflected, columns clamped) and, with prev not NULL, is held to d +- diff around the temporal mean d = (prev + cur) / 2, diff
+ * from the differences of the two frames on the five lines around it.  fp32 on widened samples, no fused multiply-add, one
+ * rounding to the dtype.  Output rows and columns past H x W are the replicate pad of the result.  Nothing outside H x W of
+ * cur or prev is read.  decision: NULL, or a word of device memory read ON THE DEVICE when the kernel runs (the call does
+ * not wait for it): 0 - out is cur's picture and its replicate pad, bit for bit; anything else - the filter.  One launch for
+ * the three planes; 16-byte accesses where cur, prev, out and the row length allow it (chosen on the host).
+ * dcvc_comb_detect: is the luma picture interlaced?  q = clamp(rint(x * 1023), 0, 1023) (a NaN counts as 0); over the kept rows
+ * 1 <= y <= H - 2 and all columns, 64-bit integer sums  dc = sum |2 q_cur[y] - q_cur[y-1] - q_cur[y+1]|,  with prev
+ * dp = sum |2 q_cur[y] - q_prev[y-1] - q_prev[y+1]|,  without  ds = sum |2 q_cur[y] - q_cur[y-2] - q_cur[y+2]| (offsets
+ * reflected).  *decision = with prev: 8 * dc < 7 * dp ? 0 : 1;  without: dc > ds ? 1 : 0  (1: interlaced).  Integer atomics only:
+ * exact whatever the order.  workspace: device memory, 8-byte aligned, dcvc_comb_ws_bytes() = 64 bytes, ZERO before its first
+ * use, eight 64-bit words: [0 .. 2] the sums and the count of finished workgroups, zero again when the kernel ends (no memset
+ * between two calls); [3] frames judged, [4] frames found interlaced, both running.  One call at a time per workspace;
+ * decision: device memory, 4-byte aligned.  H must be even.
+ * Argument errors (checked before any device work, nothing is launched): dtype; a size that is not positive or a frame that
+ * does not hold its picture; keep_parity outside 0 / 1; chroma_lines outside 1 / 2; H no multiple of 2 * chroma_lines (of 2:
+ * dcvc_comb_detect); a NULL cur, out, workspace or decision (dcvc_comb_detect); a pointer not aligned to its element size; out
+ * overlapping cur or prev. */
+int dcvc_deinterlace(int dtype, const void* cur_nchw, const void* prev_nchw, int Hp, int Wp, int H, int W, int keep_parity,
+                     int chroma_lines, const uint32_t* decision, void* out_nchw, void* stream);
+int64_t dcvc_comb_ws_bytes(void);
+int dcvc_comb_detect(int dtype, const void* cur_nchw, const void* prev_nchw, int Hp, int Wp, int H, int W, int keep_parity,
+                     void* workspace, uint32_t* decision, void* stream);
+/* ------------------------------------------------------------------------------------------
  * Film-grain synthesis and estimation on model frames (csrc/dcvc_grain.hip; docs/film_grain.md is the normative text; no
  * reference counterpart).  The parameters of a grain unit, passed by value: strengths are standard deviations in units of
  * 2^-11 of full scale, scale_y[k] the luma strength at intensity band k (centred at (k + 0.5) / 8). */

@@ -165,6 +165,9 @@ _SIGS = {
     "dcvc_frame_paste": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, POINTER(c_float), _P]),
     "dcvc_frame_maxdiff_ws_bytes": (_L, []),
     "dcvc_frame_maxdiff": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "dcvc_deinterlace": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "dcvc_comb_ws_bytes": (_L, []),
+    "dcvc_comb_detect": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dcvc_grain_apply": (_I, [_I, _P, _I, _I, _I, _I, _P, GrainParamsC, c_uint32, _P]),
     "dcvc_grain_stats": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "dcvc_tf_pyramid_bytes": (_L, [_I, _I]),

@@ -1,0 +1,107 @@
+"""Deinterlacing in front of the encoder (docs/deinterlace.md; csrc/dcvc_deint.hip): an interlaced source frame - two fields
+woven into one picture - becomes a progressive picture at the same frame rate before anything else looks at it.  The first
+field's rows are kept bit for bit, the second field's are rebuilt from the current and the previous frame.  No reference
+counterpart: the reference codes the comb.  tests/deint_ref.py restates the kernels in numpy."""
+import ctypes
+
+MODES = ("on", "auto")
+ORDERS = ("tff", "bff")
+
+
+def check_deinterlace(mode, order="tff"):
+    """run_one_point's deinterlace / field_order -> (mode or None, keep_parity); ValueError under the option's name, also for a
+    field_order that is set while deinterlace is not"""
+    if order not in ORDERS:
+        raise ValueError(f"field_order {order!r}: one of {', '.join(ORDERS)}")
+    if mode is None:
+        if order != "tff":
+            raise ValueError(f"field_order {order!r} is the field order of deinterlace: it has no effect without it")
+        return None, 0
+    if mode not in MODES:
+        raise ValueError(f"deinterlace {mode!r}: None or one of {', '.join(MODES)}")
+    return mode, ORDERS.index(order)
+
+
+def check_height(height, chroma_lines, name="deinterlace"):
+    """two fields of whole lines: the height is a multiple of 2 * chroma_lines"""
+    if chroma_lines not in (1, 2):
+        raise ValueError(f"{name}: chroma_lines {chroma_lines!r} is not 1 or 2")
+    if height <= 0 or height % (2 * chroma_lines):
+        raise ValueError(f"{name}: height {height} is not a multiple of {2 * chroma_lines} (two fields of "
+                         f"{chroma_lines}-row lines)")
+
+
+class Deinterlacer:
+    """Deinterlacer(device, mode="on" | "auto", order="tff" | "bff", chroma_lines=1).  order: the field whose rows are kept
+    (tff: the even lines); chroma_lines: rows per chroma line of the model frame - 2 where the loader doubled the rows of a
+    4:2:0 source, else 1.
+
+    filter(x, size) -> a NEW tensor of x's shape: the size = (H, W) picture of the model frame x [1, 3, Hp, Wp] deinterlaced,
+    with its replicate pad.  "on" filters every frame; "auto" asks dcvc_comb_detect first and a frame found progressive
+    passes bit for bit - the decision stays on the device, the filter's launch reads it there, and the call waits for nothing.
+    The first frame, the first one after reset(), and a frame whose size, shape or dtype differs from the one before it have
+    no previous frame (the spatial predictor alone; auto's weaker rule).
+
+    The object HOLDS the previous INPUT tensor, it does not copy it: the caller must not overwrite a tensor it has passed to
+    filter() before the next call (the harness's loader allocates a tensor per frame).
+
+    counts() -> (frames judged, frames found interlaced) of mode "auto", ONE read-back, for the log after the pass;
+    frames: the calls of filter() so far."""
+
+    def __init__(self, device="cuda:0", mode="on", order="tff", chroma_lines=1):
+        import torch
+        from . import _lib
+        self.mode, self.parity = check_deinterlace(mode, order)
+        if self.mode is None:
+            raise ValueError("deinterlace None: a Deinterlacer is not made where the option is off")
+        if chroma_lines not in (1, 2):
+            raise ValueError(f"chroma_lines {chroma_lines!r} is not 1 or 2")
+        self.order, self.chroma_lines = order, int(chroma_lines)
+        self.device = torch.device(device)
+        self._lib = _lib.lib()
+        self._ws = None
+        if self.mode == "auto":          # the workspace and, behind it, the decision word (zero once: every call leaves its sums zero)
+            need = _lib.check(self._lib.dcvc_comb_ws_bytes(), "dcvc_comb_ws_bytes")
+            self._ws = torch.zeros(need + 8, dtype=torch.uint8, device=self.device)
+            self._decision = ctypes.c_void_p(self._ws.data_ptr() + need)
+        self._prev = None                # (tensor, size) of the last input
+        self.frames = 0
+
+    def reset(self):
+        self._prev = None
+
+    def filter(self, x, size):
+        import torch
+        from . import _lib
+        from . import nn as L
+        size = (int(size[0]), int(size[1]))
+        check_height(size[0], self.chroma_lines)
+        x = L.frame(x)
+        prev = self._prev
+        if prev is not None and (prev[1] != size or prev[0].shape != x.shape or prev[0].dtype != x.dtype):
+            prev = None
+        p = L._p(prev[0]) if prev is not None else None
+        out = torch.empty_like(x)
+        st = L._stream(self.device)
+        args = L.frame_args(x, size)
+        decision = None
+        if self.mode == "auto":
+            decision = self._decision
+            _lib.check(self._lib.dcvc_comb_detect(args[0], args[1], p, *args[2:], self.parity, L._p(self._ws), decision, st),
+                       "dcvc_comb_detect")
+        _lib.check(self._lib.dcvc_deinterlace(args[0], args[1], p, *args[2:], self.parity, self.chroma_lines, decision,
+                                              L._p(out), st), "dcvc_deinterlace")
+        self._prev = (x, size)
+        self.frames += 1
+        return out
+
+    def counts(self):
+        import numpy as np
+        if self._ws is None:
+            return (0, 0)
+        words = self._ws.cpu().numpy()[:64].view(np.uint64)
+        return int(words[3]), int(words[4])
+
+    def filtered(self):
+        """the frames that went through the filter: every frame with 'on', those found interlaced with 'auto'"""
+        return self.frames if self.mode == "on" else self.counts()[1]

@@ -348,12 +348,18 @@ class _Source:
     """One source family as run_one_point needs it, put together by make_source: reader(), to_input(planes, dtype) -> the padded
     model input, distortion(x_hat, planes, calc_ssim, dm) -> (psnr, ssim) of one frame as summarize() takes them (dm: a
     metrics.DeviceMetrics, None: the host path) and the reconstruction writer - open_rec / write_rec / close_rec put the
-    planes of stored_planes(shown) into one raw file."""
+    planes of stored_planes(shown) into one raw file.  chroma_lines: the rows of the model frame one chroma line of the source
+    covers (2 where the loader doubles the rows of a 4:2:0 source, else 1).  stored(x) -> the planes a file of the picture x
+    would hold, as reader() + _to_device hand them on and distortion() takes them (docs/deinterlace.md: the reference picture
+    of a deinterlacing run)."""
     rec = None
 
-    def __init__(self, width, height, make_reader, to_input, distortion, stored_planes=None):
+    def __init__(self, width, height, make_reader, to_input, distortion, stored_planes=None, chroma_lines=1):
         self.w, self.h, self.make_reader, self.to_input = width, height, make_reader, to_input
-        self.distortion, self.stored_planes = distortion, stored_planes
+        self.distortion, self.stored_planes, self.chroma_lines = distortion, stored_planes, chroma_lines
+
+    def stored(self, x):
+        return list(self.stored_planes(x))
 
     def reader(self):
         self.last_reader = self.make_reader()
@@ -373,6 +379,10 @@ class _Source:
 
 
 class _PNGSource(_Source):      # the reconstruction: PNGs named like the source's, clamp * 255 rounded to uint8 (test_video.py:314-318)
+    def stored(self, x):
+        import torch
+        return [reconstruct_rgb(x, self.h, self.w).float().round().to(torch.uint8)]
+
     def open_rec(self, rec_path):
         self.rec_dir = rec_path
         if rec_path:
@@ -380,9 +390,8 @@ class _PNGSource(_Source):      # the reconstruction: PNGs named like the source
 
     def write_rec(self, shown, fi):
         if self.rec_dir:
-            import torch
             from PIL import Image
-            rgb8 = reconstruct_rgb(shown, self.h, self.w).float().round().to(torch.uint8).cpu().numpy()
+            rgb8 = self.stored(shown)[0].cpu().numpy()
             name = "im%s.png" % str(fi + 1).zfill(self.last_reader.digits)
             Image.fromarray(rgb8.transpose(1, 2, 0)).save(os.path.join(self.rec_dir, name))
 
@@ -395,7 +404,8 @@ def make_source(src_type, path, width, height):
         fmt.plane_shapes(height, width)        # (4:2:0 with an odd size is refused here)
         return _Source(width, height, lambda: RawVideoReader(path, width, height, fmt), lambda p, dt: load_frame(p, fmt, dt),
                        lambda x, p, ssim, dm: dm.yuv(x, p, fmt, ssim) if dm else pixfmt_distortion(x, p, fmt, ssim),
-                       lambda shown: store_frame(shown, height, width, fmt))          # the source's own format
+                       lambda shown: store_frame(shown, height, width, fmt),           # the source's own format
+                       2 if fmt.chroma == 420 else 1)
     if src_type == "png":
         # (the PNG reader's planes are a transposed view: the kernels read them planar, as load_rgb_frame does)
         return _PNGSource(width, height, lambda: PNGSequenceReader(path, width, height), lambda p, dt: load_rgb_frame(p[0], dt),
@@ -406,7 +416,7 @@ def make_source(src_type, path, width, height):
             return dm.yuv420(x, *p, ssim)
         return yuv420_distortion(x, *p), (yuv420_msssim(x, *p) if ssim else [0.0, 0.0, 0.0, 0.0])
     return _Source(width, height, lambda: YUV420FileReader(path, width, height), lambda p, dt: load_yuv420_frame(*p, dt),
-                   distortion, lambda shown: store_yuv420_frame(shown, height, width))
+                   distortion, lambda shown: store_yuv420_frame(shown, height, width), 2)
 
 
 # ---------------------------------------------------------------------------------- one rate point
@@ -462,9 +472,30 @@ def _detect_area(src, frame_num, dev, dtype, tol):
     return ActiveArea.from_extents(*size, det.extents(tol))
 
 
+def _front_input(src, planes, dtype, deint=None, area=None):
+    """one source frame as the front end is fed it: loader -> deint (a deinterlace.Deinterlacer): its filter on the FULL frame, so
+    that a crop's odd top offset can never flip the parity -> area (a bars.ActiveArea): its window.  What is None is off"""
+    x = src.to_input(planes, dtype)
+    if deint is not None:
+        x = deint.filter(x, (src.h, src.w))
+    if area is not None:
+        from .bars import window
+        x = window(x, (src.h, src.w), area)
+    return x
+
+
+def _reference_planes(src, planes, dtype, deint=None):
+    """the planes a decoded frame is measured against: the source's own, or in a deinterlacing run (deint: a Deinterlacer of the
+    decode pass's own, fed every source frame in order) the deinterlaced picture as a file of the source's format would hold it"""
+    if deint is None:
+        return planes
+    return src.stored(deint.filter(src.to_input(planes, dtype), (src.h, src.w)))
+
+
 def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, tf_level=0, tf_radius=2, tf_subpel=0,
-                 lookahead=0, area=None, dup_tol=None):
-    """every frame of `src` through a frontend.FrontEnd into the container -> a frontend.EncodePass.  A frame goes loader -> area
+                 lookahead=0, area=None, dup_tol=None, deint=None):
+    """every frame of `src` through a frontend.FrontEnd into the container -> a frontend.EncodePass.  A frame goes loader -> deint
+    (a deinterlace.Deinterlacer, made by the caller, who reads its counts afterwards): its filter, on the frame's clock -> area
     (a bars.ActiveArea): its window, whose size all behind it works at -> dup_tol (None: off; else 8-bit codes): a
     repeat.RepeatDetector -> tf_level 1 .. 5 or "auto": a prefilter.TemporalFilter tf_radius frames deep -> coded (height, width):
     the down-resample -> lookahead N > 0: a lookahead.Lookahead N frames deep -> SequenceEncoder(**enc_kw) -> write_frame; what is
@@ -494,8 +525,6 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
     if lookahead:
         from .lookahead import Lookahead
         la = Lookahead(dev, lookahead, enc.scenecut)
-    if area is not None:
-        from .bars import window
     out = io.BytesIO()
     writer = StreamWriter(out, display=size + (scale_filter,) if coded else None, active=area)
     front = FrontEnd(enc, writer, (ch, cw, use_two_entropy_coders(ch, cw)), sync, clock, size, det, tf,
@@ -506,21 +535,20 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
         planes = _to_device(reader.read(), dev)
         sync()
         t0 = clock()
-        x = src.to_input(planes, dtype)
-        if area is not None:
-            x = window(x, (src.h, src.w), area)
-        front.feed(x, t0)
+        front.feed(_front_input(src, planes, dtype, deint, area), t0)
     front.flush()
     reader.close()
     frame_types, bits, times, repeated = ([unit[i] for unit in front.units] for i in range(4))
     return EncodePass(enc, out.getvalue(), frame_types, bits, times, scaler, grainer, tf, la, repeated if det is not None else None)
 
 
-def _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, device_metrics, rec_path, scaler, grainer):
+def _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, device_metrics, rec_path, scaler, grainer, deint=None):
     """the container back through a StreamDecoder, frame by frame against the source: metrics of the decoded picture,
     rec_path gets the shown one.  The clock of a frame spans the container read, the decoder's work, the synchronisation and
-    the digest check.  -> (decoder, times, psnrs, ssims)"""
+    the digest check.  deint: in a deinterlacing run a Deinterlacer of this pass's own - the metrics are then against
+    _reference_planes, outside the clock.  -> (decoder, times, psnrs, ssims)"""
     import torch
+    dtype = next(nets[1].parameters()).dtype if deint is not None else None
     reader = src.reader()
     decoder = StreamDecoder(io.BytesIO(stream), *nets, dev, scaler=scaler, grainer=grainer)
     src.open_rec(rec_path)
@@ -530,7 +558,7 @@ def _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, device_metrics, r
         dm = DeviceMetrics(dev)
     times, psnrs, ssims = [], [], []
     for fi in range(frame_num):
-        planes = _to_device(reader.read(), dev)
+        planes = _reference_planes(src, _to_device(reader.read(), dev), dtype, deint)
         torch.cuda.synchronize(dev)
         t0 = time.time()
         frame = decoder.next()
@@ -570,7 +598,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                   src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
                   target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3", film_grain=None,
                   temporal_filter=0, tf_radius=2, tf_subpel=0, lookahead=0, crop=None, crop_tol=0.0, frame_dup=False,
-                  dup_tol=0.0):
+                  dup_tol=0.0, deinterlace=None, field_order="tff"):
     """Encodes `frame_num` frames of a source (src_type: SRC_TYPES - a planar 8-bit YUV 4:2:0 file, a directory of PNGs, a raw
     file in a pipeline.PIXEL_FORMATS format) into the reference's container (optionally written to bin_path), decodes the
     container again and returns the reference-schema log (summarize) plus one group of keys per extension switched on.
@@ -592,7 +620,12 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                                    the colour and crop_tol in 8-bit codes)             log: active_area, bar_colour
       frame_dup, dup_tol           docs/frame_repeat.md (a frame within dup_tol 8-bit codes of the last coded frame is sent as a
                                    one-byte repeat unit; bpp, target_bpp and the metrics stay per source frame, a repeat counts
-                                   as a P frame)                                        log: repeat_frames, dup_tol [, frame_repeat]"""
+                                   as a P frame)                                        log: repeat_frames, dup_tol [, frame_repeat]
+      deinterlace, field_order     docs/deinterlace.md (None, "on", "auto"; "tff", "bff": the field that is kept).  The source's
+                                   frames are deinterlaced on the device in front of everything else, the crop included; PSNR /
+                                   MS-SSIM are then against the DEINTERLACED source, quantised to the source's format - not
+                                   against the woven frames               log: deinterlace, field_order, deint_frames"""
+    from .deinterlace import check_deinterlace, check_height
     from .grain import GrainParams
     from .lookahead import check_depth
     from .prefilter import check_options, check_subpel
@@ -603,6 +636,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
             raise ValueError(f"{name} {value!r}: one of {', '.join(choices)}")
     area, tol = check_crop(crop, crop_tol, height, width)
     check_dup(frame_dup, dup_tol)
+    deinterlace, _ = check_deinterlace(deinterlace, field_order)
     coded_size = check_coded_size(coded_size, *(area.size if area not in (None, "auto") else (height, width)))
     if not (film_grain is None or film_grain == "auto" or isinstance(film_grain, GrainParams)):
         raise ValueError(f"film_grain {film_grain!r}: None, 'auto' or a GrainParams")
@@ -611,6 +645,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     if check_depth(lookahead) and not scenecut:
         raise ValueError("lookahead decides the scene cuts of scenecut: give scenecut too")
     src = make_source(src_type, src_path, width, height)
+    if deinterlace:
+        check_height(height, src.chroma_lines, f"deinterlace of a {src_type} source")
     import torch
     dev, nets = torch.device(device), (i_net, p_net)
     t_start = time.time()
@@ -636,13 +672,17 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         extra["area"] = area
     if frame_dup:
         extra["dup_tol"] = dup_tol
+    dec_extra = {}
+    if deinterlace:                  # one for each pass: the same frames in the same order, the same pictures and decisions
+        from .deinterlace import Deinterlacer
+        extra["deint"], dec_extra["deint"] = (Deinterlacer(dev, deinterlace, field_order, src.chroma_lines) for _ in range(2))
     done = _encode_pass(nets, src, frame_num, dev, coded_size, scale_filter, film_grain, enc_kw, temporal_filter, tf_radius, **extra)
     coded_num = frame_num - sum(done.repeated) if frame_dup else frame_num         # the frames the filter and the encoder saw
     if bin_path:
         with open(bin_path, "wb") as f:
             f.write(done.stream)
     decoder, dec_time, psnrs, ssims = _decode_pass(nets, src, done.stream, frame_num, dev, calc_ssim, metrics == "device", rec_path,
-                                                   done.scaler, done.grainer)
+                                                   done.scaler, done.grainer, **dec_extra)
     test_time = time.time() - t_start
     timed = verbose >= 1 and frame_num > 10     # the first 10 frames are warm-up (test_video.py:328-333)
     log = summarize(height * width, test_time, done.frame_types, done.bits, psnrs, ssims, verbose=verbose_json,
@@ -677,6 +717,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         log.update(repeat_frames=sum(done.repeated), dup_tol=float(dup_tol))
         if verbose_json:
             log["frame_repeat"] = list(done.repeated)
+    if deinterlace:
+        log.update(deinterlace=deinterlace, field_order=field_order, deint_frames=extra["deint"].filtered())
     return log
 
 
@@ -684,7 +726,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
 # manifest_options all go through point_kwargs, so a new option is one row here, one build_parser line under the same name and
 # its hook in run_one_point.  target_bpp is not one of them: it is worked out per sequence (target_bpp()).  Nor
 # are temporal_filter / tf_radius / tf_subpel: they act in front of the encoder, not on a rate point, and the table's names are pinned
-# (tests/test_harness_options.py), so they travel target_bpp's way - prefilter_kwargs(), passed beside point_kwargs().  lookahead goes the same way: lookahead_kwargs().  So does crop / crop_tol: crop_kwargs(), which hands on nothing at all where the option is not set, and frame_dup / dup_tol: dup_kwargs(), likewise.
+# (tests/test_harness_options.py), so they travel target_bpp's way - prefilter_kwargs(), passed beside point_kwargs().  lookahead goes the same way: lookahead_kwargs().  So does crop / crop_tol: crop_kwargs(), which hands on nothing at all where the option is not set, and frame_dup / dup_tol: dup_kwargs(), likewise, and deinterlace / field_order: deint_kwargs().
 POINT_OPTIONS = (("verbose", 0, None), ("verbose_json", False, bool), ("calc_ssim", False, bool), ("metrics", "host", None),
                  ("entropy", "host", None), ("scenecut", 0, None), ("min_keyint", 4, None), ("digest", False, bool),
                  ("coded_size", None, None), ("scale_filter", "lanczos3", None), ("film_grain", None, None))
@@ -728,6 +770,15 @@ def dup_kwargs(opts):
     if not opts.get("frame_dup"):
         return {}
     return dict({"frame_dup": True}, **({"dup_tol": opts["dup_tol"]} if opts.get("dup_tol") else {}))
+
+
+def deint_kwargs(opts):
+    """an options mapping -> run_one_point's keywords of deinterlacing: none at all where deinterlace is missing or None (the
+    keywords of before the option), field_order only where it is set.  It acts in front of the encoder and travels beside
+    point_kwargs(), as crop_kwargs() does"""
+    if not opts.get("deinterlace"):
+        return {}
+    return dict({"deinterlace": opts["deinterlace"]}, **({"field_order": opts["field_order"]} if opts.get("field_order") else {}))
 
 
 def run_sweep(make_nets, src_path, width, height, frame_num, rate_num=4, qp_i=None, qp_p=None, bin_prefix=None, **kw):
@@ -930,7 +981,8 @@ def run_job(nets, job, opts):
                         job["qp_i"], job["qp_p"], intra_period=job["intra_period"], reset_interval=job["reset_interval"],
                         bin_path=bin_path, rec_path=rec_path, device="cuda:0", src_type=job.get("src_type", "yuv420"),
                         target_bpp=target_bpp(opts, job["src_width"], job["src_height"]), **prefilter_kwargs(opts),
-                        **lookahead_kwargs(opts), **crop_kwargs(opts), **dup_kwargs(opts), **point_kwargs(opts))
+                        **lookahead_kwargs(opts), **crop_kwargs(opts), **dup_kwargs(opts), **deint_kwargs(opts),
+                        **point_kwargs(opts))
     if json_path:
         with open(json_path, "w") as f:
             json.dump(log, f, indent=2)
@@ -1004,6 +1056,11 @@ def check_dup_options(args, ap):
         ap.error("--dup-tol is in 8-bit codes, >= 0")
 
 
+def check_deint_options(args, ap):
+    if args.field_order is not None and not args.deinterlace:
+        ap.error("--field-order is the field order of --deinterlace: it has no effect without it")
+
+
 def _str2bool(v):
     """the reference's str2bool (test_video.py:24-28): --flag 1 / true / yes / y / t"""
     if isinstance(v, bool):
@@ -1017,7 +1074,7 @@ def _str2bool(v):
 
 def _add_extension_options(ap, flag):
     """this project's options beyond the reference's: adaptive I frames, rate control, digests, reduced resolution, film grain,
-    the temporal pre-filter, the frame lookahead, active-area coding, repeated-frame coding"""
+    the temporal pre-filter, the frame lookahead, active-area coding, repeated-frame coding, deinterlacing"""
     from .resize import FILTERS, parse_size
     ap.add_argument("--scenecut", type=int, default=0, metavar="PCT",
                     help="adaptive I frames: a frame whose low-resolution difference to its predecessor is at least PCT percent "
@@ -1073,6 +1130,15 @@ def _add_extension_options(ap, flag):
     ap.add_argument("--dup-tol", "--dup_tol", type=float, default=None, metavar="X",
                     help="with --frame-dup: a frame is a repeat while every sample stays within X 8-bit codes of the last coded "
                          "frame (default 0: equal frames only; above 0 for material that went through a dithered stage)")
+    ap.add_argument("--deinterlace", choices=("on", "auto"), default=None,
+                    help="the source is interlaced (1080i, DVD, archive material): every frame is deinterlaced on the device in "
+                         "front of everything else - the first field's lines are kept, the second field's rebuilt from the "
+                         "current and the previous frame, motion-adaptive and edge-directed, same frame rate "
+                         "(docs/deinterlace.md).  auto: decided per frame on the device, a progressive frame passes bit for "
+                         "bit.  Encoder side only, the stream format is unchanged.  PSNR / MS-SSIM are then against the "
+                         "deinterlaced source, quantised to the source's format")
+    ap.add_argument("--field-order", "--field_order", choices=("tff", "bff"), default=None,
+                    help="with --deinterlace: the field that comes first and is kept - tff: the even lines (default), bff: the odd ones")
     ap.add_argument("--tf-subpel", "--tf_subpel", type=int, default=0, choices=(0, 1, 2), metavar="S",
                     help="with --temporal-filter: refine the filter's motion vectors to half (1) or quarter pels (2) and gather "
                          "interpolated reference samples (0 = whole-pel vectors; 2 is recommended for camera material)")
@@ -1165,7 +1231,7 @@ def manifest_options(args, ap):
                                           "target_kbps", "fps", "force_intra", "check_existing", "save_decoded_frame",
                                           "temporal_filter", "tf_radius", "tf_subpel", "lookahead")}
     opts.update(gpu_ids=gpu_ids, stream_path=stream_path, **crop_kwargs(vars(args)), **dup_kwargs(vars(args)),
-                **point_kwargs(vars(args)))
+                **deint_kwargs(vars(args)), **point_kwargs(vars(args)))
     return opts, gpus
 
 
@@ -1176,6 +1242,7 @@ def main(argv=None):
     check_lookahead_options(args, ap)
     check_crop_options(args, ap)
     check_dup_options(args, ap)
+    check_deint_options(args, ap)
     if args.test_config:
         with open(args.test_config) as f:
             config = json.load(f)
@@ -1201,7 +1268,7 @@ def main(argv=None):
                     bin_prefix=args.bin_prefix, intra_period=args.intra_period, reset_interval=args.reset_interval,
                     src_type=args.src_type, target_bpp=target_bpp(vars(args), args.width, args.height),
                     **prefilter_kwargs(vars(args)), **lookahead_kwargs(vars(args)), **crop_kwargs(vars(args)),
-                    **dup_kwargs(vars(args)), **point_kwargs(vars(args)))
+                    **dup_kwargs(vars(args)), **deint_kwargs(vars(args)), **point_kwargs(vars(args)))
     text = json.dumps({str(k): v for k, v in res.items()}, indent=2)
     if args.out:
         with open(args.out, "w") as f:
