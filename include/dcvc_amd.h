@@ -569,6 +569,33 @@ int dcvc_deinterlace(int dtype, const void* cur_nchw, const void* prev_nchw, int
 int64_t dcvc_comb_ws_bytes(void);
 int dcvc_comb_detect(int dtype, const void* cur_nchw, const void* prev_nchw, int Hp, int Wp, int H, int W, int keep_parity,
                      void* workspace, uint32_t* decision, void* stream);
+/* Film mode: field matching (csrc/dcvc_fieldmatch.hip; docs/deinterlace.md, "Film mode", is the normative text).  Frames,
+ * keep_parity and chroma_lines as above.  The kept field of cur is completed by one of two candidates: c, the other field of
+ * cur, or p, the other field of prev.
+ * dcvc_field_match: luma only, q as dcvc_comb_detect's.  For candidate m with o = cur (c) or prev (p), over the rows y that are
+ * not kept with 2 <= y <= H - 3 and all columns: a = o[y-2], b = cur[y-1], s = o[y], d = cur[y+1], e = o[y+2]; the sample is
+ * combed iff (s - b and s - d are both > T or both < -T) and |a + 4 s + e - 3 (b + d)| > 6 T, T = 36.  max_m: the largest number
+ * of combed samples in one 16 x 16 block (y / 16, x / 16); m is combed iff max_m > 20.  decision2[0] = filter, decision2[1] =
+ * weave:  c not combed: (0, 0), the frame passes;  else prev given and p not combed: (0, 1);  else (1, 0).  Without prev, or
+ * with H < 5, max_p = 0 resp. both are 0.  One launch; integer atomics only: exact whatever the order.  workspace: device memory,
+ * 8-byte aligned, dcvc_field_match_ws_bytes() = 64 bytes, ZERO before its first use, sixteen 32-bit words: [0 .. 2] the two
+ * maxima and the count of finished workgroups, zero again when the kernel ends (no memset between two calls); running:
+ * [4] frames judged, [5] passed, [6] woven, [7] filtered; [8], [9] max_c and max_p of the last call.  One call at a time per
+ * workspace; decision2: two words of device memory, 4-byte aligned, written on the device - the call does not wait.  H must
+ * be even.  Nothing outside H x W is read.
+ * dcvc_field_weave: in place on out.  *weave is read ON THE DEVICE: 0 - nothing is written; else in every plane every row of the
+ * picture that is not kept takes prev's W samples, and out's replicate pad follows (to the right of those rows from
+ * prev[y][W-1]; the rows below the picture where row H - 1 is not kept).  A copy of bits: a NaN arrives as it is.  One launch
+ * for the three planes; 16-byte accesses where prev, out and the row length allow it (chosen on the host).
+ * Argument errors (checked before any device work, nothing is launched): dtype; a size that is not positive or a frame that
+ * does not hold its picture; keep_parity outside 0 / 1; chroma_lines outside 1 / 2; H no multiple of 2 (dcvc_field_match) or of
+ * 2 * chroma_lines (dcvc_field_weave); a NULL cur, out, workspace, decision2 or weave, a NULL prev (dcvc_field_weave); a
+ * pointer not aligned to its element size (workspace: 8 bytes, the words: 4); out overlapping prev. */
+int64_t dcvc_field_match_ws_bytes(void);
+int dcvc_field_match(int dtype, const void* cur_nchw, const void* prev_nchw, int Hp, int Wp, int H, int W, int keep_parity,
+                     void* workspace, uint32_t* decision2, void* stream);
+int dcvc_field_weave(int dtype, const void* prev_nchw, int Hp, int Wp, int H, int W, int keep_parity, int chroma_lines,
+                     const uint32_t* weave, void* out_nchw, void* stream);
 /* ------------------------------------------------------------------------------------------
  * Film-grain synthesis and estimation on model frames (csrc/dcvc_grain.hip; docs/film_grain.md is the normative text; no
  * reference counterpart).  The parameters of a grain unit, passed by value: strengths are standard deviations in units of

@@ -168,6 +168,9 @@ _SIGS = {
     "dcvc_deinterlace": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dcvc_comb_ws_bytes": (_L, []),
     "dcvc_comb_detect": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "dcvc_field_match_ws_bytes": (_L, []),
+    "dcvc_field_match": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "dcvc_field_weave": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dcvc_grain_apply": (_I, [_I, _P, _I, _I, _I, _I, _P, GrainParamsC, c_uint32, _P]),
     "dcvc_grain_stats": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "dcvc_tf_pyramid_bytes": (_L, [_I, _I]),

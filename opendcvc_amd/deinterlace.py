@@ -1,10 +1,11 @@
 """Deinterlacing in front of the encoder (docs/deinterlace.md; csrc/dcvc_deint.hip): an interlaced source frame - two fields
 woven into one picture - becomes a progressive picture at the same frame rate before anything else looks at it.  The first
-field's rows are kept bit for bit, the second field's are rebuilt from the current and the previous frame.  No reference
-counterpart: the reference codes the comb.  tests/deint_ref.py restates the kernels in numpy."""
+field's rows are kept bit for bit, the second field's are rebuilt from the current and the previous frame - or, in film mode
+(csrc/dcvc_fieldmatch.hip), taken from wherever the matching field lies.  No reference counterpart: the reference codes the
+comb.  tests/deint_ref.py and tests/fieldmatch_ref.py restate the kernels in numpy."""
 import ctypes
 
-MODES = ("on", "auto")
+MODES = ("on", "auto", "film")
 ORDERS = ("tff", "bff")
 
 
@@ -32,7 +33,7 @@ def check_height(height, chroma_lines, name="deinterlace"):
 
 
 class Deinterlacer:
-    """Deinterlacer(device, mode="on" | "auto", order="tff" | "bff", chroma_lines=1).  order: the field whose rows are kept
+    """Deinterlacer(device, mode="on" | "auto" | "film", order="tff" | "bff", chroma_lines=1).  order: the field whose rows are kept
     (tff: the even lines); chroma_lines: rows per chroma line of the model frame - 2 where the loader doubled the rows of a
     4:2:0 source, else 1.
 
@@ -40,13 +41,16 @@ class Deinterlacer:
     with its replicate pad.  "on" filters every frame; "auto" asks dcvc_comb_detect first and a frame found progressive
     passes bit for bit - the decision stays on the device, the filter's launch reads it there, and the call waits for nothing.
     The first frame, the first one after reset(), and a frame whose size, shape or dtype differs from the one before it have
-    no previous frame (the spatial predictor alone; auto's weaker rule).
+    no previous frame (the spatial predictor alone; auto's weaker rule).  "film" asks dcvc_field_match which field completes
+    the kept one: the frame's own - it passes bit for bit -, the previous frame's - dcvc_field_weave puts its rows in - or
+    neither - the filter, as with "on".  Its two decision words stay on the device in the same way.
 
     The object HOLDS the previous INPUT tensor, it does not copy it: the caller must not overwrite a tensor it has passed to
     filter() before the next call (the harness's loader allocates a tensor per frame).
 
-    counts() -> (frames judged, frames found interlaced) of mode "auto", ONE read-back, for the log after the pass;
-    frames: the calls of filter() so far."""
+    counts() -> (frames judged, frames found interlaced) of mode "auto", (frames judged, frames filtered) of mode "film", ONE
+    read-back, for the log after the pass; matches() -> (passed, woven, filtered) of mode "film", likewise; frames: the calls
+    of filter() so far."""
 
     def __init__(self, device="cuda:0", mode="on", order="tff", chroma_lines=1):
         import torch
@@ -64,6 +68,11 @@ class Deinterlacer:
             need = _lib.check(self._lib.dcvc_comb_ws_bytes(), "dcvc_comb_ws_bytes")
             self._ws = torch.zeros(need + 8, dtype=torch.uint8, device=self.device)
             self._decision = ctypes.c_void_p(self._ws.data_ptr() + need)
+        if self.mode == "film":          # the same, with two words behind it: filter, weave
+            need = _lib.check(self._lib.dcvc_field_match_ws_bytes(), "dcvc_field_match_ws_bytes")
+            self._ws = torch.zeros(need + 8, dtype=torch.uint8, device=self.device)
+            self._decision = ctypes.c_void_p(self._ws.data_ptr() + need)
+            self._weave = ctypes.c_void_p(self._ws.data_ptr() + need + 4)
         self._prev = None                # (tensor, size) of the last input
         self.frames = 0
 
@@ -89,8 +98,15 @@ class Deinterlacer:
             decision = self._decision
             _lib.check(self._lib.dcvc_comb_detect(args[0], args[1], p, *args[2:], self.parity, L._p(self._ws), decision, st),
                        "dcvc_comb_detect")
+        if self.mode == "film":
+            decision = self._decision
+            _lib.check(self._lib.dcvc_field_match(args[0], args[1], p, *args[2:], self.parity, L._p(self._ws), decision, st),
+                       "dcvc_field_match")
         _lib.check(self._lib.dcvc_deinterlace(args[0], args[1], p, *args[2:], self.parity, self.chroma_lines, decision,
                                               L._p(out), st), "dcvc_deinterlace")
+        if self.mode == "film" and p is not None:
+            _lib.check(self._lib.dcvc_field_weave(args[0], p, *args[2:], self.parity, self.chroma_lines, self._weave, L._p(out),
+                                                  st), "dcvc_field_weave")
         self._prev = (x, size)
         self.frames += 1
         return out
@@ -99,9 +115,22 @@ class Deinterlacer:
         import numpy as np
         if self._ws is None:
             return (0, 0)
+        if self.mode == "film":
+            judged, _, _, filtered = self._film_words()
+            return judged, filtered
         words = self._ws.cpu().numpy()[:64].view(np.uint64)
         return int(words[3]), int(words[4])
 
+    def _film_words(self):
+        """dcvc_field_match's running counters: judged, passed, woven, filtered"""
+        import numpy as np
+        return [int(w) for w in self._ws.cpu().numpy()[:64].view(np.uint32)[4:8]]
+
+    def matches(self):
+        """(frames passed, frames woven, frames filtered) of mode 'film'; (0, 0, 0) in the other modes"""
+        return tuple(self._film_words()[1:]) if self.mode == "film" else (0, 0, 0)
+
     def filtered(self):
-        """the frames that went through the filter: every frame with 'on', those found interlaced with 'auto'"""
+        """the frames that went through the filter: every frame with 'on', those found interlaced with 'auto', those
+        that matched neither field with 'film'"""
         return self.frames if self.mode == "on" else self.counts()[1]

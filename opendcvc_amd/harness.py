@@ -621,10 +621,13 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
       frame_dup, dup_tol           docs/frame_repeat.md (a frame within dup_tol 8-bit codes of the last coded frame is sent as a
                                    one-byte repeat unit; bpp, target_bpp and the metrics stay per source frame, a repeat counts
                                    as a P frame)                                        log: repeat_frames, dup_tol [, frame_repeat]
-      deinterlace, field_order     docs/deinterlace.md (None, "on", "auto"; "tff", "bff": the field that is kept).  The source's
+      deinterlace, field_order     docs/deinterlace.md (None, "on", "auto", "film"; "tff", "bff": the field that is kept).  The source's
                                    frames are deinterlaced on the device in front of everything else, the crop included; PSNR /
                                    MS-SSIM are then against the DEINTERLACED source, quantised to the source's format - not
-                                   against the woven frames               log: deinterlace, field_order, deint_frames"""
+                                   against the woven frames               log: deinterlace, field_order, deint_frames
+                                   "film": telecined film - a frame whose fields fit passes, one whose kept field fits the
+                                   previous frame's other field is woven from the two, the rest is filtered; with frame_dup
+                                   the repeated pictures of the pulldown become repeat units     log: + field_matches"""
     from .deinterlace import check_deinterlace, check_height
     from .grain import GrainParams
     from .lookahead import check_depth
@@ -717,7 +720,11 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         log.update(repeat_frames=sum(done.repeated), dup_tol=float(dup_tol))
         if verbose_json:
             log["frame_repeat"] = list(done.repeated)
-    if deinterlace:
+    if deinterlace == "film":        # one read-back of the four device counters
+        passed, woven, filtered = extra["deint"].matches()
+        log.update(deinterlace=deinterlace, field_order=field_order, deint_frames=filtered,
+                   field_matches={"pass": passed, "weave": woven})
+    elif deinterlace:
         log.update(deinterlace=deinterlace, field_order=field_order, deint_frames=extra["deint"].filtered())
     return log
 
@@ -1130,12 +1137,14 @@ def _add_extension_options(ap, flag):
     ap.add_argument("--dup-tol", "--dup_tol", type=float, default=None, metavar="X",
                     help="with --frame-dup: a frame is a repeat while every sample stays within X 8-bit codes of the last coded "
                          "frame (default 0: equal frames only; above 0 for material that went through a dithered stage)")
-    ap.add_argument("--deinterlace", choices=("on", "auto"), default=None,
+    ap.add_argument("--deinterlace", choices=("on", "auto", "film"), default=None,
                     help="the source is interlaced (1080i, DVD, archive material): every frame is deinterlaced on the device in "
                          "front of everything else - the first field's lines are kept, the second field's rebuilt from the "
                          "current and the previous frame, motion-adaptive and edge-directed, same frame rate "
                          "(docs/deinterlace.md).  auto: decided per frame on the device, a progressive frame passes bit for "
-                         "bit.  Encoder side only, the stream format is unchanged.  PSNR / MS-SSIM are then against the "
+                         "bit.  film: telecined film - per frame the device finds the field that completes the first one, in the "
+                         "same frame (it passes bit for bit) or in the previous one (the two are woven); a frame that matches "
+                         "neither is filtered; with --frame-dup the pulldown's repeated pictures cost a byte each.  Encoder side only, the stream format is unchanged.  PSNR / MS-SSIM are then against the "
                          "deinterlaced source, quantised to the source's format")
     ap.add_argument("--field-order", "--field_order", choices=("tff", "bff"), default=None,
                     help="with --deinterlace: the field that comes first and is kept - tff: the even lines (default), bff: the odd ones")
