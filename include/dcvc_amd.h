@@ -569,6 +569,19 @@ int dcvc_deinterlace(int dtype, const void* cur_nchw, const void* prev_nchw, int
 int64_t dcvc_comb_ws_bytes(void);
 int dcvc_comb_detect(int dtype, const void* cur_nchw, const void* prev_nchw, int Hp, int Wp, int H, int W, int keep_parity,
                      void* workspace, uint32_t* decision, void* stream);
+/* Field-rate output (csrc/dcvc_deint_field.hip; docs/deinterlace.md, "Field-rate output", is the normative text).  Frames,
+ * keep_parity (the SOURCE's: the entry flips it itself) and chroma_lines as above.  out is B_n, the picture of cur's second
+ * field with its replicate pad: dcvc_deinterlace's filter with the other parity kept, on the field-shifted frame S_n - per
+ * plane the rows with (y / L) % 2 != keep_parity from cur, the others from after - with S_(n-1), the same of before and cur,
+ * as its previous frame.  Neither is materialised: one launch, the frame a staged row is read from chosen by the row's parity.
+ * The rows of cur's second field arrive bit for bit.  before or after NULL: the spatial predictor alone, from cur's second
+ * field; then neither neighbour is read.  Nothing outside H x W is read; of before only the second field's rows are, of after
+ * only the first field's.  16-byte accesses where every frame given, out and the row length allow it (chosen on the host).
+ * Argument errors (checked before any device work, nothing is launched): dtype; a size that is not positive or a frame that
+ * does not hold its picture; keep_parity outside 0 / 1; chroma_lines outside 1 / 2; H no multiple of 2 * chroma_lines; a NULL
+ * cur or out; a pointer not aligned to its element size; out overlapping before, cur or after. */
+int dcvc_deinterlace_field(int dtype, const void* before_nchw, const void* cur_nchw, const void* after_nchw, int Hp, int Wp, int H,
+                           int W, int keep_parity, int chroma_lines, void* out_nchw, void* stream);
 /* Film mode: field matching (csrc/dcvc_fieldmatch.hip; docs/deinterlace.md, "Film mode", is the normative text).  Frames,
  * keep_parity and chroma_lines as above.  The kept field of cur is completed by one of two candidates: c, the other field of
  * cur, or p, the other field of prev.

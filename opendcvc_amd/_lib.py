@@ -166,6 +166,7 @@ _SIGS = {
     "dcvc_frame_maxdiff_ws_bytes": (_L, []),
     "dcvc_frame_maxdiff": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "dcvc_deinterlace": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "dcvc_deinterlace_field": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "dcvc_comb_ws_bytes": (_L, []),
     "dcvc_comb_detect": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dcvc_field_match_ws_bytes": (_L, []),

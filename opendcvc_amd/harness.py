@@ -478,10 +478,19 @@ def _front_input(src, planes, dtype, deint=None, area=None):
     x = src.to_input(planes, dtype)
     if deint is not None:
         x = deint.filter(x, (src.h, src.w))
+    return _windowed(src, x, area)
+
+
+def _windowed(src, x, area):
     if area is not None:
         from .bars import window
         x = window(x, (src.h, src.w), area)
     return x
+
+
+def _field_rate(deint):
+    """is deint a Deinterlacer that makes two pictures per frame (docs/deinterlace.md, "Field-rate output")"""
+    return getattr(deint, "rate", None) == "field"
 
 
 def _reference_planes(src, planes, dtype, deint=None):
@@ -492,6 +501,21 @@ def _reference_planes(src, planes, dtype, deint=None):
     return src.stored(deint.filter(src.to_input(planes, dtype), (src.h, src.w)))
 
 
+def _references(src, reader, frame_num, dev, dtype, deint=None):
+    """the reference planes of every picture the decode pass is to meet, in order, each made when it is asked for: one per source
+    frame (_reference_planes), or at field rate the two pictures of every frame - deint.fields() per frame read, deint.drain()
+    behind the last - as files of the source's format would hold them"""
+    if not _field_rate(deint):
+        for _ in range(frame_num):
+            yield _reference_planes(src, _to_device(reader.read(), dev), dtype, deint)
+        return
+    for _ in range(frame_num):
+        for pic in deint.fields(src.to_input(_to_device(reader.read(), dev), dtype), (src.h, src.w)):
+            yield src.stored(pic)
+    for pic in deint.drain():
+        yield src.stored(pic)
+
+
 def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, tf_level=0, tf_radius=2, tf_subpel=0,
                  lookahead=0, area=None, dup_tol=None, deint=None):
     """every frame of `src` through a frontend.FrontEnd into the container -> a frontend.EncodePass.  A frame goes loader -> deint
@@ -500,7 +524,10 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
     repeat.RepeatDetector -> tf_level 1 .. 5 or "auto": a prefilter.TemporalFilter tf_radius frames deep -> coded (height, width):
     the down-resample -> lookahead N > 0: a lookahead.Lookahead N frames deep -> SequenceEncoder(**enc_kw) -> write_frame; what is
     off is not made.  grain: None, a GrainParams, or "auto": estimated at every I frame from the UNFILTERED input of the frame being
-    coded against the reconstruction at that size, seeded with the count of frames written so far.  A frame's clock: frontend.py."""
+    coded against the reconstruction at that size, seeded with the count of frames written so far.  A frame's clock: frontend.py.
+    A field-rate deint gives the front end TWO pictures per frame read - fields()'s, then drain()'s behind the last read - and
+    everything behind it counts pictures: the first picture of a read starts its clock at the read, every further one,
+    drain()'s included, when it is made or handed over."""
     import torch
     from .frontend import EncodePass, FrontEnd
     from .grain import FilmGrain
@@ -530,12 +557,25 @@ def _encode_pass(nets, src, frame_num, dev, coded, scale_filter, grain, enc_kw, 
     front = FrontEnd(enc, writer, (ch, cw, use_two_entropy_coders(ch, cw)), sync, clock, size, det, tf,
                      (lambda x: scaler.resample(x, size, (ch, cw), scale_filter)) if scaler else None, la)
 
+    field_rate = _field_rate(deint)
     reader = src.reader()
     for _ in range(frame_num):
         planes = _to_device(reader.read(), dev)
         sync()
         t0 = clock()
-        front.feed(_front_input(src, planes, dtype, deint, area), t0)
+        if not field_rate:
+            front.feed(_front_input(src, planes, dtype, deint, area), t0)
+            continue
+        for k, pic in enumerate(deint.fields(src.to_input(planes, dtype), (src.h, src.w))):
+            if k:
+                sync()
+                t0 = clock()
+            front.feed(_windowed(src, pic, area), t0)
+    if field_rate:                                       # the last frame's second picture: its launch is on its own clock
+        sync()
+        t0 = clock()
+        for pic in deint.drain():
+            front.feed(_windowed(src, pic, area), t0)
     front.flush()
     reader.close()
     frame_types, bits, times, repeated = ([unit[i] for unit in front.units] for i in range(4))
@@ -546,7 +586,8 @@ def _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, device_metrics, r
     """the container back through a StreamDecoder, frame by frame against the source: metrics of the decoded picture,
     rec_path gets the shown one.  The clock of a frame spans the container read, the decoder's work, the synchronisation and
     the digest check.  deint: in a deinterlacing run a Deinterlacer of this pass's own - the metrics are then against
-    _reference_planes, outside the clock.  -> (decoder, times, psnrs, ssims)"""
+    _reference_planes, outside the clock; at field rate there are two of them per source frame, and as many pictures are
+    decoded as there are references (_references).  -> (decoder, times, psnrs, ssims)"""
     import torch
     dtype = next(nets[1].parameters()).dtype if deint is not None else None
     reader = src.reader()
@@ -557,8 +598,7 @@ def _decode_pass(nets, src, stream, frame_num, dev, calc_ssim, device_metrics, r
         from .metrics import DeviceMetrics
         dm = DeviceMetrics(dev)
     times, psnrs, ssims = [], [], []
-    for fi in range(frame_num):
-        planes = _reference_planes(src, _to_device(reader.read(), dev), dtype, deint)
+    for fi, planes in enumerate(_references(src, reader, frame_num, dev, dtype, deint)):
         torch.cuda.synchronize(dev)
         t0 = time.time()
         frame = decoder.next()
@@ -598,7 +638,9 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                   src_type="yuv420", calc_ssim=False, metrics="host", entropy="host", scenecut=0, min_keyint=4,
                   target_bpp=None, digest=False, coded_size=None, scale_filter="lanczos3", film_grain=None,
                   temporal_filter=0, tf_radius=2, tf_subpel=0, lookahead=0, crop=None, crop_tol=0.0, frame_dup=False,
-                  dup_tol=0.0, deinterlace=None, field_order="tff"):
+                  dup_tol=0.0, deint_rate=None, deinterlace=None, field_order="tff"):
+    # (deint_rate stands in FRONT of deinterlace / field_order, not behind them where it was added: tests/test_deint_host.py pins
+    # those two as the last names.  Every option from device on is meant to be given by keyword, and every caller here does)
     """Encodes `frame_num` frames of a source (src_type: SRC_TYPES - a planar 8-bit YUV 4:2:0 file, a directory of PNGs, a raw
     file in a pipeline.PIXEL_FORMATS format) into the reference's container (optionally written to bin_path), decodes the
     container again and returns the reference-schema log (summarize) plus one group of keys per extension switched on.
@@ -627,8 +669,13 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
                                    against the woven frames               log: deinterlace, field_order, deint_frames
                                    "film": telecined film - a frame whose fields fit passes, one whose kept field fits the
                                    previous frame's other field is woven from the two, the rest is filtered; with frame_dup
-                                   the repeated pictures of the pulldown become repeat units     log: + field_matches"""
-    from .deinterlace import check_deinterlace, check_height
+                                   the repeated pictures of the pulldown become repeat units     log: + field_matches
+      deint_rate                   None / "frame": a picture per source frame.  "field" (deinterlace "on" only): TWO pictures per
+                                   source frame, one per field - 50i becomes 50p.  frame_num stays the count of SOURCE frames; the
+                                   run codes and decodes 2 * frame_num pictures, and everything behind the filter - intra_period,
+                                   reset_interval, min_keyint, lookahead, tf_radius, frame_dup, the digests, target_bpp, the
+                                   per-frame lists - counts pictures           log: + deint_rate; deint_frames: the pictures"""
+    from .deinterlace import check_deinterlace, check_height, check_rate
     from .grain import GrainParams
     from .lookahead import check_depth
     from .prefilter import check_options, check_subpel
@@ -640,6 +687,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     area, tol = check_crop(crop, crop_tol, height, width)
     check_dup(frame_dup, dup_tol)
     deinterlace, _ = check_deinterlace(deinterlace, field_order)
+    field_rate = check_rate(deint_rate, deinterlace) == "field"
     coded_size = check_coded_size(coded_size, *(area.size if area not in (None, "auto") else (height, width)))
     if not (film_grain is None or film_grain == "auto" or isinstance(film_grain, GrainParams)):
         raise ValueError(f"film_grain {film_grain!r}: None, 'auto' or a GrainParams")
@@ -678,9 +726,11 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     dec_extra = {}
     if deinterlace:                  # one for each pass: the same frames in the same order, the same pictures and decisions
         from .deinterlace import Deinterlacer
-        extra["deint"], dec_extra["deint"] = (Deinterlacer(dev, deinterlace, field_order, src.chroma_lines) for _ in range(2))
+        rate = ("field",) if field_rate else ()          # (frame rate: the call of before the option)
+        extra["deint"], dec_extra["deint"] = (Deinterlacer(dev, deinterlace, field_order, src.chroma_lines, *rate) for _ in range(2))
     done = _encode_pass(nets, src, frame_num, dev, coded_size, scale_filter, film_grain, enc_kw, temporal_filter, tf_radius, **extra)
-    coded_num = frame_num - sum(done.repeated) if frame_dup else frame_num         # the frames the filter and the encoder saw
+    picture_num = 2 * frame_num if field_rate else frame_num
+    coded_num = picture_num - sum(done.repeated) if frame_dup else picture_num     # the pictures the filter and the encoder saw
     if bin_path:
         with open(bin_path, "wb") as f:
             f.write(done.stream)
@@ -696,7 +746,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     if done.lookahead is not None:
         log.update(lookahead=lookahead, flashes=list(done.lookahead.flashes), fades=list(done.lookahead.fades))
     if target_bpp:
-        log.update(_rate_log(done.enc, float(target_bpp), frame_num, height * width, verbose_json))
+        log.update(_rate_log(done.enc, float(target_bpp), picture_num, height * width, verbose_json))
     if digest:
         log["digests_checked"] = decoder.digests_checked
     if coded_size:
@@ -725,7 +775,8 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
         log.update(deinterlace=deinterlace, field_order=field_order, deint_frames=filtered,
                    field_matches={"pass": passed, "weave": woven})
     elif deinterlace:
-        log.update(deinterlace=deinterlace, field_order=field_order, deint_frames=extra["deint"].filtered())
+        log.update(deinterlace=deinterlace, field_order=field_order, **({"deint_rate": "field"} if field_rate else {}),
+                   deint_frames=extra["deint"].filtered())
     return log
 
 
@@ -733,7 +784,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
 # manifest_options all go through point_kwargs, so a new option is one row here, one build_parser line under the same name and
 # its hook in run_one_point.  target_bpp is not one of them: it is worked out per sequence (target_bpp()).  Nor
 # are temporal_filter / tf_radius / tf_subpel: they act in front of the encoder, not on a rate point, and the table's names are pinned
-# (tests/test_harness_options.py), so they travel target_bpp's way - prefilter_kwargs(), passed beside point_kwargs().  lookahead goes the same way: lookahead_kwargs().  So does crop / crop_tol: crop_kwargs(), which hands on nothing at all where the option is not set, and frame_dup / dup_tol: dup_kwargs(), likewise, and deinterlace / field_order: deint_kwargs().
+# (tests/test_harness_options.py), so they travel target_bpp's way - prefilter_kwargs(), passed beside point_kwargs().  lookahead goes the same way: lookahead_kwargs().  So does crop / crop_tol: crop_kwargs(), which hands on nothing at all where the option is not set, and frame_dup / dup_tol: dup_kwargs(), likewise, and deinterlace / field_order / deint_rate: deint_kwargs().
 POINT_OPTIONS = (("verbose", 0, None), ("verbose_json", False, bool), ("calc_ssim", False, bool), ("metrics", "host", None),
                  ("entropy", "host", None), ("scenecut", 0, None), ("min_keyint", 4, None), ("digest", False, bool),
                  ("coded_size", None, None), ("scale_filter", "lanczos3", None), ("film_grain", None, None))
@@ -781,11 +832,11 @@ def dup_kwargs(opts):
 
 def deint_kwargs(opts):
     """an options mapping -> run_one_point's keywords of deinterlacing: none at all where deinterlace is missing or None (the
-    keywords of before the option), field_order only where it is set.  It acts in front of the encoder and travels beside
-    point_kwargs(), as crop_kwargs() does"""
+    keywords of before the option), field_order and deint_rate only where they are set.  It acts in front of the encoder and
+    travels beside point_kwargs(), as crop_kwargs() does"""
     if not opts.get("deinterlace"):
         return {}
-    return dict({"deinterlace": opts["deinterlace"]}, **({"field_order": opts["field_order"]} if opts.get("field_order") else {}))
+    return dict({"deinterlace": opts["deinterlace"]}, **{k: opts[k] for k in ("field_order", "deint_rate") if opts.get(k)})
 
 
 def run_sweep(make_nets, src_path, width, height, frame_num, rate_num=4, qp_i=None, qp_p=None, bin_prefix=None, **kw):
@@ -981,7 +1032,8 @@ def run_job(nets, job, opts):
         if opts.get("check_existing") and os.path.exists(json_path) and os.path.exists(bin_path):
             with open(json_path) as f:
                 log = json.load(f)
-            if log.get("i_frame_num", 0) + log.get("p_frame_num", 0) == job["frame_num"]:
+            pictures = job["frame_num"] * (2 if opts.get("deint_rate") == "field" else 1)      # field rate: two per frame
+            if log.get("i_frame_num", 0) + log.get("p_frame_num", 0) == pictures:
                 return log
             print(f"incorrect log for {json_path}, try to rerun.")
     log = run_one_point(nets[0], nets[1], job["src_path"], job["src_width"], job["src_height"], job["frame_num"],
@@ -1021,11 +1073,13 @@ def run_config(config, opts, workers=1, gpus=1):
 
 
 def target_bpp(opts, width, height):
-    """--target-bpp, or --target-kbps with --fps, as bits per pixel of a width x height sequence (None: no rate control)"""
+    """--target-bpp, or --target-kbps with --fps, as bits per pixel of a width x height sequence (None: no rate control).  Per
+    coded picture: --fps is the SOURCE's frame rate, and at --deint-rate field a second carries twice as many pictures"""
     if opts.get("target_bpp"):
         return float(opts["target_bpp"])
     if opts.get("target_kbps"):
-        return float(opts["target_kbps"]) * 1000.0 / (float(opts["fps"]) * width * height)
+        pictures = 2.0 if opts.get("deint_rate") == "field" else 1.0
+        return float(opts["target_kbps"]) * 1000.0 / (pictures * float(opts["fps"]) * width * height)
     return None
 
 
@@ -1066,6 +1120,9 @@ def check_dup_options(args, ap):
 def check_deint_options(args, ap):
     if args.field_order is not None and not args.deinterlace:
         ap.error("--field-order is the field order of --deinterlace: it has no effect without it")
+    if args.deint_rate == "field" and args.deinterlace != "on":
+        ap.error("--deint-rate field is the field-rate output of --deinterlace on: it cannot go with --deinterlace "
+                 f"{args.deinterlace or 'unset'}")
 
 
 def _str2bool(v):
@@ -1148,6 +1205,12 @@ def _add_extension_options(ap, flag):
                          "deinterlaced source, quantised to the source's format")
     ap.add_argument("--field-order", "--field_order", choices=("tff", "bff"), default=None,
                     help="with --deinterlace: the field that comes first and is kept - tff: the even lines (default), bff: the odd ones")
+    ap.add_argument("--deint-rate", "--deint_rate", choices=("frame", "field"), default=None,
+                    help="with --deinterlace on: frame - one picture per source frame, the field that comes first (default); "
+                         "field - TWO pictures per source frame, one per field, 50i becomes 50p: --frames stays the count of "
+                         "source frames, twice as many pictures are coded and decoded, and --intra-period, --reset-interval, "
+                         "--min-keyint, --lookahead, --tf-radius and --target-bpp count pictures; --fps stays the source's "
+                         "frame rate (docs/deinterlace.md, \"Field-rate output\")")
     ap.add_argument("--tf-subpel", "--tf_subpel", type=int, default=0, choices=(0, 1, 2), metavar="S",
                     help="with --temporal-filter: refine the filter's motion vectors to half (1) or quarter pels (2) and gather "
                          "interpolated reference samples (0 = whole-pel vectors; 2 is recommended for camera material)")
