@@ -456,9 +456,33 @@ int dcvc_frame_to_planes(int dtype, int chroma, int bit_depth, int semi_planar, 
                          void* stream);
 /* the values dcvc_frame_to_planes rounds, NOT rounded: clip(., 0, 1) * max_val as fp32 planes y [H][W], u / v [H/2][W/2]
  * (4:2:0) or [H][W] (4:4:4), whatever the storage type - what PSNR and MS-SSIM (data_range = max_val) compare with the
- * source's samples (DCVC_U8 / DCVC_U16 operands of dcvc_sse / dcvc_msssim_stats). */
+ * source's samples (DCVC_U8 / DCVC_U16 operands of dcvc_sse / dcvc_msssim_stats).  chroma = 422: the values
+ * dcvc_frame_to_yuv422 rounds, u / v [H][W/2] (an even W). */
 int dcvc_frame_to_metric_planes(int dtype, int chroma, int max_val, const void* x_nchw, int Hp, int Wp, int H, int W,
                                 float* y, float* u, float* v, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * 4:2:2 frame I/O (csrc/dcvc_pix422.hip, docs/pixel_formats_422.md): what SDI capture and mezzanine files deliver.  The
+ * arithmetic continues the entries above: load (float)sample / (float)max_val as one fp32 division, one rounding to the
+ * storage type, chroma columns doubled (nearest), replicate pad to [3][H+pad_b][W+pad_r]; store fp32 chroma
+ * (a + b) * 0.5f over the pixel pair, clip(., 0, 1) * max_val, round to nearest even, clip.  W is even, H any positive
+ * number.  The model frame is 16-byte aligned and its row length a multiple of 8.
+ *   DCVC_422_PLANAR  planes y [H][W], u / v [H][W/2], 8 .. 16 bits, value in the low bits; strides in SAMPLES
+ *   DCVC_422_UYVY    8 bits, ONE surface (u, v and c_stride are ignored), bytes U Y0 V Y1 per pixel pair; y_stride is the
+ *   DCVC_422_YUYV    pitch in BYTES, at least 2 W; bytes Y0 U Y1 V.  Base and pitch are multiples of 4 (one macropixel)
+ *   DCVC_422_V210    10 bits, ONE surface, pitch in BYTES, at least dcvc_v210_row_bytes(W); base and pitch are multiples
+ *                    of 16.  Six pixels are four little-endian 32-bit words, bits 30 and 31 zero:
+ *                      w0 = Cb0 | Y0 << 10 | Cr0 << 20     w1 = Y1 | Cb1 << 10 | Y2 << 20
+ *                      w2 = Cr1 | Y3 << 10 | Cb2 << 20     w3 = Y4 | Cr2 << 10 | Y5 << 20      (Cbk / Crk: pixels 2k, 2k + 1)
+ * The writer writes a v210 row for exactly dcvc_v210_row_bytes(W) bytes: samples of pixels at or beyond W, the filler
+ * groups up to the 128-byte multiple and bits 30 and 31 are zero; nothing of a pitch gap is touched by any layout.  The
+ * loader lets nothing of a row past pixel W - 1 reach the frame.
+ * All argument checks come before any launch and need no device. */
+enum { DCVC_422_PLANAR = 0, DCVC_422_UYVY = 1, DCVC_422_YUYV = 2, DCVC_422_V210 = 3 };
+int64_t dcvc_v210_row_bytes(int W);          /* ((W + 47) / 48) * 128; <= 0 for W <= 0 */
+int dcvc_yuv422_to_frame(int dtype, int layout, int bit_depth, const void* y_or_packed, const void* u, const void* v,
+                         int64_t y_stride, int64_t c_stride, int H, int W, int pad_b, int pad_r, void* out_nchw, void* stream);
+int dcvc_frame_to_yuv422(int dtype, int layout, int bit_depth, const void* x_nchw, int Hp, int Wp, int H, int W,
+                         void* y_or_packed, void* u, void* v, int64_t y_stride, int64_t c_stride, void* stream);
 /* ------------------------------------------------------------------------------------------
  * Separable polyphase resampler on model frames (csrc/dcvc_resize.hip, docs/reduced_resolution.md; no reference
  * counterpart): the scaler of a reduced-resolution run.  x_nchw [3][Hp][Wp] with the valid region H x W at its top left ->

@@ -156,6 +156,9 @@ _SIGS = {
     "dcvc_planes_to_frame": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _I, _I, _I, _I, _P, _P]),
     "dcvc_frame_to_planes": (_I, [_I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _L, _P]),
     "dcvc_frame_to_metric_planes": (_I, [_I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dcvc_v210_row_bytes": (_L, [_I]),
+    "dcvc_yuv422_to_frame": (_I, [_I, _I, _I, _P, _P, _P, _L, _L, _I, _I, _I, _I, _P, _P]),
+    "dcvc_frame_to_yuv422": (_I, [_I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _L, _L, _P]),
     "dcvc_resize_frame": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "dcvc_bars_ws_bytes": (_L, [_I, _I]),
     "dcvc_bars_reset": (_I, [_P, _I, _I, _P]),

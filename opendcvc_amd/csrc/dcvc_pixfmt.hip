@@ -14,21 +14,22 @@
 #include "common.hpp"
 #include "dcvc_math.h"
 #include "frame_host.hpp"
+#include "pix_shared.hpp"
 #include "plane_math.hpp"
 
 #include <algorithm>
 #include <cstdint>
 #include <type_traits>
 
+namespace dcvc {
+// 4:2:2 metric planes: dcvc_pix422.hip's kernel behind dcvc_frame_to_metric_planes (arguments already checked)
+int metric_planes_422(int dtype, int max_val, const void* x_nchw, int Hp, int Wp, int H, int W, float* y, float* u, float* v,
+                      hipStream_t stream);
+}  // namespace dcvc
+
 namespace {
 
-constexpr int PB = 256;                       // threads per block
 enum { L_420P = 0, L_420SP = 1, L_444P = 2 }; // plane layout of a launch
-
-template <typename E, int VW>
-struct alignas(sizeof(E) * VW) Pack {
-    E v[VW];
-};
 
 // an interleaved (U, V) pair of samples as one element: U in the low half (little-endian memory order U, V)
 template <typename S>
@@ -42,59 +43,7 @@ struct PairOf<uint16_t> {
     typedef uint32_t type;
 };
 
-constexpr int cmin(int a, int b) { return a < b ? a : b; }
-constexpr int cmax(int a, int b) { return a > b ? a : b; }
-// elements per access of an 8-element (luma, 4:4:4 chroma, UV pairs seen as samples) and of a 4-element (4:2:0 chroma
-// samples or pairs) piece of a row at access class A (8, 4, 2, 1): at most 16 bytes
-template <typename E>
-constexpr int vw8(int A) { return cmin(A, 16 / (int)sizeof(E)); }
-template <typename E>
-constexpr int vw4(int A) { return cmin(cmax(A / 2, 1), 16 / (int)sizeof(E)); }
-
-// o[0..N) = row[x .. x + N), columns past n - 1 clamped to n - 1 (replicate pad); VW elements per access where the
-// whole piece lies inside the row
-template <typename E, int N, int VW>
-__device__ __forceinline__ void load_row(const E* row, int x, int n, E (&o)[N])
-{
-#pragma unroll
-    for (int c = 0; c < N; c += VW) {
-        if (x + c + VW <= n) {
-            const Pack<E, VW> p = *reinterpret_cast<const Pack<E, VW>*>(row + x + c);
-#pragma unroll
-            for (int k = 0; k < VW; ++k) o[c + k] = p.v[k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < VW; ++k) o[c + k] = row[min(x + c + k, n - 1)];
-        }
-    }
-}
-
-// row[x .. x + N) = v[0..N) for the columns below n
-template <typename E, int N, int VW>
-__device__ __forceinline__ void store_row(E* row, int x, int n, const E (&v)[N])
-{
-#pragma unroll
-    for (int c = 0; c < N; c += VW) {
-        if (x + c + VW <= n) {
-            Pack<E, VW> p;
-#pragma unroll
-            for (int k = 0; k < VW; ++k) p.v[k] = v[c + k];
-            *reinterpret_cast<Pack<E, VW>*>(row + x + c) = p;
-        } else {
-#pragma unroll
-            for (int k = 0; k < VW; ++k)
-                if (x + c + k < n) row[x + c + k] = v[c + k];
-        }
-    }
-}
-
 // ------------------------------------------------------------------ planes -> padded model frame
-template <typename T, typename S>
-__device__ __forceinline__ T norm_sample(S s, int shift, float maxf)
-{
-    return to_t<T>((float)((unsigned)s >> shift) / maxf);
-}
-
 template <typename T, typename S, int N, int VW>
 __device__ __forceinline__ void load_plane_row(const S* row, int x0, int W, int shift, float maxf, T* dst)
 {
@@ -161,34 +110,7 @@ __global__ __launch_bounds__(PB) void planes_to_frame_kernel(const S* yp, const 
 }
 
 // ------------------------------------------------------------------ model frame -> planes / metric planes
-// what becomes of an fp32 plane value: the integer sample of a file ...
-template <typename S>
-struct Quant {
-    typedef S E;
-    int shift;
-    float maxf;
-    __device__ __forceinline__ S operator()(float v) const
-    {
-        v = clampf(v, 0.f, 1.f) * maxf;
-        v = clampf(rintf(v), 0.f, maxf);
-        return (S)((unsigned)v << shift);
-    }
-};
-// ... or the value the metrics compare: the same product, not rounded
-struct Metric {
-    typedef float E;
-    float maxf;
-    __device__ __forceinline__ float operator()(float v) const { return clampf(v, 0.f, 1.f) * maxf; }
-};
-
-template <typename T>
-__device__ __forceinline__ void load_pix8(const T* p, float (&f)[8])
-{
-    const Pix8<T> a = *reinterpret_cast<const Pix8<T>*>(p);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) f[k] = (float)a.v[k];
-}
-
+// (what becomes of an fp32 plane value, Quant or Metric: pix_shared.hpp)
 template <typename T, typename C, int LAYOUT, int A>
 __global__ __launch_bounds__(PB) void frame_to_planes_kernel(const T* x, int HP, int WP, int H, int W, C cvt, typename C::E* yp,
                                                              void* up_, typename C::E* vp, int64_t ys, int64_t cs)
@@ -415,17 +337,6 @@ int check_planes(const char* who, const Fmt& f, const void* y, const void* u, co
     return 0;
 }
 
-// the frame the streaming storers read, 8 pixels per access
-int check_frame8(const char* who, int dtype, const void* x, int Hp, int Wp, int H, int W)
-{
-    if (int rc = dcvc::check_frame(who, "the frame", dtype, x, Hp, Wp, H, W)) return rc;
-    DCVC_REQUIRE(Wp % 8 == 0 && ((uintptr_t)x & 15) == 0,
-                 "%s: the frame (%d x %d) must be 16-byte aligned and have a width that is a multiple of 8", who, Hp, Wp);
-    return 0;
-}
-
-inline unsigned blocks_for(int64_t threads) { return (unsigned)((threads + PB - 1) / PB); }
-
 // f(S{}) with S the sample type of `ss` bytes
 template <typename F>
 void with_sample(int ss, F&& f)
@@ -509,11 +420,13 @@ int dcvc_frame_to_metric_planes(int dtype, int chroma, int max_val, const void* 
                                 float* u, float* v, void* stream)
 {
     const char* who = "dcvc_frame_to_metric_planes";
-    DCVC_REQUIRE(chroma == 420 || chroma == 444, "%s: chroma %d (420 or 444)", who, chroma);
+    DCVC_REQUIRE(chroma == 420 || chroma == 422 || chroma == 444, "%s: chroma %d (420, 422 or 444)", who, chroma);
     DCVC_REQUIRE(max_val >= 255 && max_val <= 65535, "%s: max_val %d outside 255 .. 65535", who, max_val);
-    DCVC_REQUIRE(chroma == 444 || (H % 2 == 0 && W % 2 == 0), "%s: 4:2:0 needs an even height and width (got %d x %d)", who, H, W);
+    DCVC_REQUIRE(chroma != 420 || (H % 2 == 0 && W % 2 == 0), "%s: 4:2:0 needs an even height and width (got %d x %d)", who, H, W);
+    DCVC_REQUIRE(chroma != 422 || W % 2 == 0, "%s: 4:2:2 needs an even width (got %d x %d)", who, H, W);
     DCVC_REQUIRE(y && u && v && (((uintptr_t)y | (uintptr_t)u | (uintptr_t)v) & 3) == 0, "%s: null or misaligned plane", who);
     if (int rc = check_frame8(who, dtype, x_nchw, Hp, Wp, H, W)) return rc;
+    if (chroma == 422) return dcvc::metric_planes_422(dtype, max_val, x_nchw, Hp, Wp, H, W, y, u, v, (hipStream_t)stream);
     const int layout = chroma == 444 ? L_444P : L_420P;
     const int64_t cs = chroma == 444 ? W : W / 2;
     const Metric m{(float)max_val};

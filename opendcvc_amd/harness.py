@@ -32,9 +32,11 @@ import numpy as np
 from .bitstream import StreamWriter
 from .pipeline import (PIXEL_FORMATS, PixelFormat, SequenceEncoder, StreamDecoder, load_frame, load_yuv420_frame, store_frame,
                        store_yuv420_frame, use_two_entropy_coders)
+from .pix422 import FORMATS_422
 from .repeat import tol_fraction
 
 SRC_TYPES = ("yuv420", "png") + tuple(PIXEL_FORMATS)     # "yuv420": planar 8-bit 4:2:0 with the reference harness's arithmetic
+SRC_TYPES_422 = tuple(FORMATS_422)                       # the 4:2:2 formats (pix422.py): planar, uyvy422, yuyv422, v210
 
 
 # ---------------------------------------------------------------------------------- metrics / log
@@ -165,11 +167,15 @@ def yuv420_msssim(x_hat, y, u, v):
     return [(6 * vals[0] + vals[1] + vals[2]) / 8] + vals
 
 
-def source_planes(planes, fmt):
-    """the planes of a PixelFormat source as the metrics read them: planar (y, u, v), value in the LOW bits.  Planar
+def source_planes(planes, fmt, width=None):
+    """the planes of a PixelFormat or Format422 source as the metrics read them: planar (y, u, v), value in the LOW bits
+    (width: the picture's, which a v210 surface does not tell; by default what a tight surface holds).  Planar
     low-aligned formats pass through; the chroma of a semi-planar source is de-interleaved and msb-aligned words are
     shifted down (torch glue through int16 / int32 views: the measuring side, not the codec's path)"""
     import torch
+    if fmt.chroma == 422:                      # a pix422.Format422: a packed surface is taken apart, the width is the picture's
+        from .pix422 import unpack_422
+        return unpack_422(planes, fmt, width)
     planes = list(planes)
     if fmt.semi_planar:
         uv = planes[1].view(torch.int16) if fmt.sample_bytes == 2 else planes[1]
@@ -181,22 +187,25 @@ def source_planes(planes, fmt):
 
 
 def pixfmt_metric_planes(x_hat, height, width, fmt):
-    """the planes the metrics of a PixelFormat source compare, in torch: crop, fp32, 4:2:0 chroma the explicit fp32
-    ((a + b) + (d + e)) * 0.25 over the 2x2 block, clip(., 0, 1) * max_val, NOT rounded -> fp32 (y, u, v)"""
+    """the planes the metrics of a PixelFormat / Format422 source compare, in torch: crop, fp32, 4:2:0 chroma the explicit fp32
+    ((a + b) + (d + e)) * 0.25 over the 2x2 block, 4:2:2 chroma (a + b) * 0.5 over the pixel pair, clip(., 0, 1) * max_val,
+    NOT rounded -> fp32 (y, u, v)"""
     import torch
     x = x_hat[0, :, :height, :width].float()
     y, c = x[0], x[1:]
     if fmt.chroma == 420:
         c = ((c[:, 0::2, 0::2] + c[:, 0::2, 1::2]) + (c[:, 1::2, 0::2] + c[:, 1::2, 1::2])) * 0.25
+    elif fmt.chroma == 422:
+        c = (c[:, :, 0::2] + c[:, :, 1::2]) * 0.5
     scale = lambda p: torch.clamp(p, 0.0, 1.0) * float(fmt.max_val)
     return scale(y), scale(c[0]), scale(c[1])
 
 
-def pixfmt_distortion(x_hat, planes, fmt, calc_ssim=False):
+def pixfmt_distortion(x_hat, planes, fmt, calc_ssim=False, width=None):
     """host-path metrics of a PixelFormat source (the reference family's writer arithmetic before its rounding, PSNR and
     MS-SSIM with data_range = max_val): -> (psnr, msssim), each [(6 Y + U + V) / 8, Y, U, V]; squared errors and MS-SSIM
     in float64 on the host"""
-    src = [p.cpu().numpy().astype(np.float64) for p in source_planes(planes, fmt)]
+    src = [p.cpu().numpy().astype(np.float64) for p in source_planes(planes, fmt, width)]
     H, W = src[0].shape
     rec = [p.cpu().numpy().astype(np.float64) for p in pixfmt_metric_planes(x_hat, H, W, fmt)]
     dr = float(fmt.max_val)
@@ -397,8 +406,17 @@ class _PNGSource(_Source):      # the reconstruction: PNGs named like the source
 
 
 def make_source(src_type, path, width, height):
-    """the source object of a src_type (SRC_TYPES); touches no file.  The host metrics are looked up in this module when
+    """the source object of a src_type (SRC_TYPES, SRC_TYPES_422); touches no file.  The host metrics are looked up in this module when
     they are called."""
+    if src_type in FORMATS_422:
+        from .pix422 import Raw422Reader, load_frame_422, store_frame_422
+        f422 = FORMATS_422[src_type]
+        f422.check_width(width)                # (an odd width is refused here)
+        # every chroma line is one row high; a packed frame travels as its one surface, whose width the picture's is
+        return _Source(width, height, lambda: Raw422Reader(path, width, height, f422),
+                       lambda p, dt: load_frame_422(p, f422, dt, width=width),
+                       lambda x, p, ssim, dm: (dm.yuv(x, p, f422, ssim, width) if dm else pixfmt_distortion(x, p, f422, ssim, width)),
+                       lambda shown: store_frame_422(shown, height, width, f422), 1)
     fmt = PIXEL_FORMATS.get(src_type)          # None: the reference harness's own two source types
     if fmt is not None:
         fmt.plane_shapes(height, width)        # (4:2:0 with an odd size is refused here)
@@ -681,7 +699,7 @@ def run_one_point(i_net, p_net, src_path, width, height, frame_num, qp_i, qp_p=N
     from .prefilter import check_options, check_subpel
     from .resize import FILTERS, check_coded_size
     for name, value, choices in (("metrics", metrics, ("host", "device")), ("entropy", entropy, ("host", "device")),
-                                 ("src_type", src_type, SRC_TYPES), ("scale_filter", scale_filter, FILTERS)):
+                                 ("src_type", src_type, SRC_TYPES + SRC_TYPES_422), ("scale_filter", scale_filter, FILTERS)):
         if value not in choices:
             raise ValueError(f"{name} {value!r}: one of {', '.join(choices)}")
     area, tol = check_crop(crop, crop_tol, height, width)
@@ -876,8 +894,8 @@ def jobs_from_config(config, opts):
     for ds_name, ds in config["test_classes"].items():
         if ds["test"] == 0:
             continue
-        if ds["src_type"] not in SRC_TYPES:
-            raise ValueError(f"{ds_name}: src_type {ds['src_type']!r} (one of {', '.join(SRC_TYPES)})")
+        if ds["src_type"] not in SRC_TYPES + SRC_TYPES_422:
+            raise ValueError(f"{ds_name}: src_type {ds['src_type']!r} (one of {', '.join(SRC_TYPES + SRC_TYPES_422)})")
         for seq, info in ds["sequences"].items():
             for rate_idx, (q, qq) in enumerate(zip(qi, qp)):
                 ip = info["intra_period"]
@@ -1265,9 +1283,10 @@ def build_parser():
                     help="with --stream-path: do not code a point again whose .bin and .json exist (reference --check_existing)")
     ap.add_argument("--save-decoded-frame", "--save_decoded_frame", **flag,
                     help="with --stream-path: write the reconstruction beside the .bin (reference --save_decoded_frame)")
-    ap.add_argument("--src-type", "--src_type", choices=SRC_TYPES, default="yuv420",
+    ap.add_argument("--src-type", "--src_type", choices=SRC_TYPES + SRC_TYPES_422, default="yuv420",
                     help="--src is a planar 8-bit YUV 4:2:0 file (yuv420), a directory of im1.png ... / im00001.png ... (RGB), or a "
-                         "raw file in one of the other formats under its ffmpeg name (10 / 12 / 16 bits, 4:4:4, NV12, P010)")
+                         "raw file in one of the other formats under its ffmpeg name (10 / 12 / 16 bits, 4:4:4, NV12, P010; 4:2:2: "
+                         "yuv422p .. yuv422p16le, uyvy422, yuyv422, v210)")
     ap.add_argument("--src")
     ap.add_argument("--width", type=int)
     ap.add_argument("--height", type=int)

@@ -153,7 +153,7 @@ class DeviceMetrics:
         key = ("pix", height, width, fmt.chroma)
         planes = self._planes.get(key)
         if planes is None:
-            ch, cw = (height, width) if fmt.chroma == 444 else (height // 2, width // 2)
+            ch, cw = {444: (height, width), 422: (height, width // 2)}.get(fmt.chroma, (height // 2, width // 2))
             planes = self._planes[key] = (torch.empty((height, width), dtype=torch.float32, device=self.device),
                                           torch.empty((ch, cw), dtype=torch.float32, device=self.device),
                                           torch.empty((ch, cw), dtype=torch.float32, device=self.device))
@@ -162,12 +162,12 @@ class DeviceMetrics:
                                                          L._p(planes[2]), self._stream()), "dcvc_frame_to_metric_planes")
         return planes
 
-    def yuv(self, x_hat, planes, fmt, calc_ssim=False):
+    def yuv(self, x_hat, planes, fmt, calc_ssim=False, width=None):
         """harness.pixfmt_distortion on the device: x_hat [1,3,H',W'] (model dtype), planes: the source's device planes as
         its reader delivers them (uint8 / uint16; the chroma of NV12 / P010 is de-interleaved and P010's words are
         shifted down here by harness.source_planes, torch glue on the measuring side) -> (psnr, msssim), each
         [(6 Y + U + V) / 8, Y, U, V] with data_range = max_val; msssim zeros without calc_ssim"""
-        y, u, v = source_planes(planes, fmt)
+        y, u, v = source_planes(planes, fmt, width)     # (width: the picture's, for a packed 4:2:2 surface)
         H, W = y.shape
         st = self._stream()
         rec = self.metric_planes(x_hat, H, W, fmt)
